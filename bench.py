@@ -16,6 +16,9 @@ timesteps, and `diffusion_steps` graph-replayed denoiser evaluations + scheduler
 resident in HBM.  Faces are independent, so ranks shard the batch with no collective inside the loop;
 RCCL is used only for the final gather of the latents (inside the timed region) and the timing reduce.
 
+`--dump-outputs DIR` writes what the timed path returned in its last timed step (the final latents of the whole batch, after the
+gather) to DIR/latents.npy as float32; inputs and seeds depend only on the arguments, so two builds can be compared output for output.
+
 Prints ONE JSON line (rank 0).  `roofline`: one launch = one captured step graph (one denoiser
 evaluation of the whole batch); algorithmic bytes per launch = the bf16 weights every step must stream
 (0.7227 GB at latent 16), duration = HIP-event time of the replay loop / diffusion steps.
@@ -299,6 +302,24 @@ def measure_config3(dev, passes=3, reuse=None):
     return res
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """What the timed path returned in its last step, as float32 .npy files: the whole array when every file fits in
+    DUMP_LIMIT_BYTES together, otherwise a fixed, seeded sample of faces (rows of dim 0) of each, in face order."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    total = sum(v.numel() * 4 for v in arrays.values())
+    for name, v in arrays.items():
+        v = v.detach().float().cpu()
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, int(v.shape[0] * DUMP_LIMIT_BYTES // total))
+            idx = torch.randperm(v.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            v = v[idx]
+        np.save(os.path.join(d, name + ".npy"), v.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -310,6 +331,8 @@ def main():
     ap.add_argument("--kind", default="ddpm", choices=["ddpm", "ddim"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the configs[3] passes that follow the headline's timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the final latents of the last timed step to DIR/latents.npy (float32, rank 0, at most 64 MB)")
     a = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -409,6 +432,8 @@ def main():
         rccl_world = dist.get_world_size()
     dt = float(tt.item())
     finite = bool(torch.isfinite(out).all().item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"latents": out})
 
     if rank == 0:
         faces_per_rank = [int(v) for v in per_rank.tolist()]

@@ -253,6 +253,27 @@ def test_bench_latency_floor_adds_up_its_terms():
         assert os.path.exists(os.path.join(ROOT, src[1])), src
 
 
+def test_bench_dump_outputs_writes_float32_within_the_limit(tmp_path):
+    """bench.py --dump-outputs: the last step's latents as float32 .npy, whole when they fit in 64 MB, otherwise a fixed, seeded sample
+    of faces in face order that does fit -- the same sample on every run, so two builds can be compared output for output."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    assert b.DUMP_LIMIT_BYTES == 64 << 20
+    x = torch.randn(64, 4, 16, 16, dtype=torch.float64)
+    b.dump_outputs(str(tmp_path / "a"), {"latents": x})
+    y = np.load(tmp_path / "a" / "latents.npy")
+    assert y.dtype == np.float32 and np.array_equal(y, x.float().numpy())
+    b.DUMP_LIMIT_BYTES = x[0].numel() * 4 * 10                         # room for 10 faces
+    b.dump_outputs(str(tmp_path / "b"), {"latents": x})
+    b.dump_outputs(str(tmp_path / "c"), {"latents": x})
+    y, z = np.load(tmp_path / "b" / "latents.npy"), np.load(tmp_path / "c" / "latents.npy")
+    assert y.shape == (10, 4, 16, 16) and y.nbytes <= b.DUMP_LIMIT_BYTES and np.array_equal(y, z)
+    rows = [int(np.flatnonzero((x.float().numpy() == r).all(axis=(1, 2, 3)))[0]) for r in y]
+    assert rows == sorted(rows)
+
+
 def test_synthetic_weights_can_be_reused_across_latent_sides():
     """bench.py's `secondary` (latent 32) takes every tensor whose spec does not depend on the latent side from the headline's state dict:
     a tensor is a pure function of (name, shape, kind, fan_in, seed), so only idc_conv is generated again and the values are the same."""

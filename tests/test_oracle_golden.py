@@ -12,6 +12,7 @@ from oracle import hifidiff_oracle as O
 
 T = lambda a: torch.from_numpy(np.ascontiguousarray(a))  # noqa: E731
 TOL32 = 2e-6   # fp32 oracle vs reference (different BLAS threading may reorder sums)
+TOL32_DEEP = 4e-6   # the same at the coarse restoration's middle_blocks, where the golden itself is 3.2e-6 from exact arithmetic
 BLOCKS = ["encoders.0.0", "encoders.1.0", "encoders.2.0", "encoders.3.0", "middle_blks.0"]
 
 
@@ -128,10 +129,16 @@ def test_coarse_restoration():
     g = golden("coarse_restoration.npz")
     P = synth.cr_state_dict()
     x = torch.from_numpy(np.stack([synth.rand(f"ln_face/{f}", (3, 128, 128)) for f in range(2)]))
-    taps = {}
+    taps, taps64 = {}, {}
     assert rel_l2(O.coarse_restoration(P, x, taps=taps), g["out"]) <= TOL32
-    for k in ("encoders.3", "middle_blocks"):
-        assert rel_l2(taps[k], g["feat." + k]) <= TOL32, k
+    assert rel_l2(taps["encoders.3"], g["feat.encoders.3"]) <= TOL32
+    # middle_blocks is the deepest tap: the golden's own fp32 rounding sits 3.2e-6 from exact arithmetic there (the oracle in fp64),
+    # and fp32 oracles that sum in another order than the fixture's machine land 1.1e-6 .. 2.4e-6 from it -- over TOL32 on some CPUs
+    assert rel_l2(taps["middle_blocks"], g["feat.middle_blocks"]) <= TOL32_DEEP
+    # the same restatement in fp64 (no summation-order noise of its own) under the same fixed ceiling
+    out64 = O.coarse_restoration({k: v.double() if v.is_floating_point() else v for k, v in P.items()}, x.double(), taps=taps64)
+    for k, a in (("out", out64), ("feat.encoders.3", taps64["encoders.3"]), ("feat.middle_blocks", taps64["middle_blocks"])):
+        assert rel_l2(a, g[k]) <= TOL32_DEEP, k
     assert rel_l2(O.coarse_restoration(P, x, prec=O.BF16), g["out"]) <= 1e-2
 
 
