@@ -4,9 +4,10 @@
     cr_face   = CoarseRestoration()(ln_face)                 # hifidiff_amd.cr          (test_refiner.py:77)
     cr_latent = vae.encode(bicubic(cr_face)).latent_dist.sample() * 0.18215   # hifidiff_amd.vae (test_refiner.py:78-83)
     latent    = 50-step DDIM with FacialRefiner              # hifidiff_amd.refiner + sampling (test_refiner.py:85-91)
+                (or --scheduler dpmpp2m: DPM-Solver++ 2M, the usual diffusers swap for fewer evaluations, e.g. --steps 20)
     images    = vae.decode(latent / 0.18215).sample          # hifidiff_amd.vae         (test_refiner.py:93)
 
-    python examples/pipeline.py [--batch 8] [--steps 50]
+    python examples/pipeline.py [--batch 8] [--scheduler ddim|dpmpp2m] [--steps 50]
 """
 import argparse
 import os
@@ -26,7 +27,8 @@ from hifidiff_amd.vae import AutoencoderKL                               # noqa:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--scheduler", choices=("ddim", "dpmpp2m"), default="ddim")
+    ap.add_argument("--steps", type=int, default=None, help="denoiser evaluations per face (default: 50 for ddim, 20 for dpmpp2m)")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     dev = torch.device("cuda", 0)
@@ -40,8 +42,13 @@ def main():
     model = FacialRefiner(latent_res=16)
     model.load_state_dict(synth.refiner_state_dict(16))  # real use: safetensors.torch.load_file(refiner_ckpt)
     model.to(dev)
-    sch = schedulers.DDIMScheduler(num_train_timesteps=1000, beta_schedule="scaled_linear", prediction_type="epsilon",
-                                   clip_sample_range=3.0)
+    if a.scheduler == "ddim":
+        sch = schedulers.DDIMScheduler(num_train_timesteps=1000, beta_schedule="scaled_linear", prediction_type="epsilon",
+                                       clip_sample_range=3.0)
+    else:                                                # same network, same ODE, second-order multistep solver
+        sch = schedulers.DPMSolverMultistepScheduler(num_train_timesteps=1000, beta_schedule="scaled_linear",
+                                                     prediction_type="epsilon", solver_order=2, algorithm_type="dpmsolver++")
+    steps = a.steps or (50 if a.scheduler == "ddim" else 20)
 
     B = a.batch
     ln_face = torch.from_numpy(np.stack([synth.rand(f"ln_face/{f}", (3, 128, 128)) for f in range(B)])).to(dev)
@@ -52,12 +59,12 @@ def main():
     torch.cuda.synchronize(); t1 = time.time()
     cr_latent = vae.encode_scaled(cr_face, 128, seed=7)                # bicubic (identity at 128) + encode + sample + x 0.18215
     torch.cuda.synchronize(); t2 = time.time()
-    sch.set_timesteps(a.steps)
+    sch.set_timesteps(steps)
     out = sampling.sample(model, latent, cr_face, cr_latent, sch)      # conditioning once + graph-replayed loop
     torch.cuda.synchronize(); t3 = time.time()
     images = vae.decode(out / 0.18215).sample                          # the reference's call form; decode_scaled(out) is the fused one
     torch.cuda.synchronize(); t4 = time.time()
-    print(f"batch {B}: coarse restoration {1e3 * (t1 - t0):.1f} ms, VAE encode {1e3 * (t2 - t1):.1f} ms, {a.steps}-step DDIM "
+    print(f"batch {B}: coarse restoration {1e3 * (t1 - t0):.1f} ms, VAE encode {1e3 * (t2 - t1):.1f} ms, {steps}-step {a.scheduler} "
           f"{1e3 * (t3 - t2):.1f} ms, VAE decode {1e3 * (t4 - t3):.1f} ms; latent range [{float(out.min()):.2f}, {float(out.max()):.2f}], "
           f"images {tuple(images.shape)} finite {bool(torch.isfinite(images).all())}")
 

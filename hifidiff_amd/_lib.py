@@ -38,7 +38,8 @@ def unit_deps(unit):
 
 EXPORTS = [
     "hd_create", "hd_create_unconditional", "hd_prepare_unconditional", "hd_cr_create", "hd_cr_forward", "hd_vae_create", "hd_vae_encode", "hd_vae_decode", "hd_destroy", "hd_last_error", "hd_load_weights", "hd_finalize_weights", "hd_prepare",
-    "hd_prepare_from_priors", "hd_fpg", "hd_idc", "hd_eps", "hd_sample", "hd_scheduler_step", "hd_num_ops", "hd_num_chains",
+    "hd_prepare_from_priors", "hd_fpg", "hd_idc", "hd_eps", "hd_sample", "hd_sample_multistep", "hd_scheduler_step",
+    "hd_scheduler_step_multistep", "hd_num_ops", "hd_num_chains",
     "hd_debug_limit_ops", "hd_debug_op_name", "hd_debug_read_op", "hd_debug_read", "hd_debug_write", "hd_set_option", "hd_get_option", "hd_check",
     "hd_set_profiling", "hd_get_profile",
 ]
@@ -50,6 +51,11 @@ class TensorDesc(ctypes.Structure):
 
 
 class Schedule(ctypes.Structure):
+    _fields_ = [("n_steps", ctypes.c_int32), ("timesteps", ctypes.POINTER(ctypes.c_float)),
+                ("coef", ctypes.POINTER(ctypes.c_float))]
+
+
+class ScheduleMS(ctypes.Structure):
     _fields_ = [("n_steps", ctypes.c_int32), ("timesteps", ctypes.POINTER(ctypes.c_float)),
                 ("coef", ctypes.POINTER(ctypes.c_float))]
 
@@ -113,6 +119,8 @@ def lib():
     L.hd_eps.argtypes = [vp, vp, vp, i32, vp, vp]
     L.hd_sample.argtypes = [vp, vp, ctypes.POINTER(Schedule), vp, u64, vp]
     L.hd_scheduler_step.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_float), vp, u64, i32, i64, vp]
+    L.hd_sample_multistep.argtypes = [vp, vp, ctypes.POINTER(ScheduleMS), vp, u64, vp]
+    L.hd_scheduler_step_multistep.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_float), vp, vp, u64, i32, i64, vp]
     L.hd_num_ops.argtypes = [vp, i32]
     L.hd_num_chains.argtypes = [vp]
     L.hd_debug_limit_ops.argtypes = [vp, i32, i32]

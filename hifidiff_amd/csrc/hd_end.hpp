@@ -211,7 +211,7 @@ static __global__ __launch_bounds__(EndCfg::THREADS) void hca_ending_conv_kernel
     p.eps[o] = e;
     if (p.sa.lat) {
         const int step = p.sa.st->step;
-        p.sa.lat[o] = sched_update(p.sa.lat[o], e, p.sa.coef + (size_t)step * 7, p.sa.st, step, (size_t)p.sa.elem0 + o, p.sa.n_total);
+        p.sa.lat[o] = sched_update(p.sa.lat[o], e, p.sa.coef + (size_t)step * 7, p.sa.st, step, (size_t)p.sa.elem0 + o, p.sa.n_total, o);
     }
 }
 

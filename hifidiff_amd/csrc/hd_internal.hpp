@@ -91,7 +91,7 @@ using namespace hdi;
 struct Chain {
     int B = 0, face0 = 0, index = 0;
     Level lv[5];
-    float *lat = nullptr, *eps = nullptr, *prior[5] = {}, *gate_c[5] = {}, *gate_s[5] = {}, *idc_term = nullptr;
+    float *lat = nullptr, *eps = nullptr, *x0_hist = nullptr, *prior[5] = {}, *gate_c[5] = {}, *gate_s[5] = {}, *idc_term = nullptr;
     float *id_emb = nullptr, *pool_tmp = nullptr, *mlp_tmp = nullptr, *sp_tmp = nullptr;
     unsigned short* res_buf[4] = {};
     uint4* face8 = nullptr;
@@ -120,7 +120,7 @@ struct SavedWs {
     int B = 0;
     uint64_t stamp = 0;
     std::vector<Chain> chains;
-    float *lat = nullptr, *eps = nullptr;
+    float *lat = nullptr, *eps = nullptr, *x0_hist = nullptr;
     std::vector<void*> allocs;
     std::map<std::string, std::pair<void*, std::pair<size_t, int>>> dbg;
     bool graphs_valid = false;
@@ -175,6 +175,7 @@ struct hd_ctx {
     std::vector<Chain> chains;
     Chain* ch = nullptr;                     // chain the builder functions currently work on
     float *lat = nullptr, *eps = nullptr;    // [B,4,L,L] of the whole batch; chains own contiguous face ranges
+    float* x0_hist = nullptr;                // [B,4,L,L]: previous step's x0 of a multistep schedule (hd_sample_multistep)
     bool prepared = false;
 
     // FiLM / schedule
@@ -184,6 +185,8 @@ struct hd_ctx {
     bool film_from_cur = false;               // sampling loop: LayerNorm loaders read Chain::film_cur
     float* coef_dev = nullptr;
     int coef_cap = 0;
+    float* c7_dev = nullptr;                  // [n] history coefficients of a multistep schedule (StepState::c7, not captured)
+    int c7_cap = 0;
     int advance = 0;
     hipEvent_t fork_ev = nullptr;
     // hd_sample never blocks on the caller's stream: the schedule is staged through two pinned buffers owned by the
@@ -308,7 +311,7 @@ void park_workspace(hd_ctx* c) {
     if (c->B == 0) return;
     SavedWs w;
     w.B = c->B; w.stamp = ++c->ws_clock;
-    w.chains = std::move(c->chains); w.lat = c->lat; w.eps = c->eps;
+    w.chains = std::move(c->chains); w.lat = c->lat; w.eps = c->eps; w.x0_hist = c->x0_hist;
     w.allocs = std::move(c->ws_allocs);
     w.dbg = c->dbg;
     w.graphs_valid = c->graphs_valid; w.graph_film = c->graph_film; w.graph_B = c->graph_B;
@@ -322,7 +325,7 @@ void park_workspace(hd_ctx* c) {
     w.cr_loc1 = c->cr_loc1; w.cr_loc2 = c->cr_loc2; w.cr_theta = c->cr_theta;
     c->cr_loc1 = c->cr_loc2 = c->cr_theta = nullptr; c->cr_in = nullptr; c->cr_out = nullptr;
     c->chains.clear(); c->ws_allocs.clear(); c->cr_program.clear();
-    c->lat = c->eps = nullptr; c->ch = nullptr;
+    c->lat = c->eps = c->x0_hist = nullptr; c->ch = nullptr;
     for (auto it = c->dbg.begin(); it != c->dbg.end();) it = (it->first == "film" || it->first == "temb") ? std::next(it) : c->dbg.erase(it);
     c->graphs_valid = false; c->prepared = false;
     const int B = c->B;
@@ -342,7 +345,7 @@ bool unpark_workspace(hd_ctx* c, int B) {
     auto it = c->ws_cache.find(B);
     if (it == c->ws_cache.end()) return false;
     SavedWs& w = it->second;
-    c->chains = std::move(w.chains); c->lat = w.lat; c->eps = w.eps;
+    c->chains = std::move(w.chains); c->lat = w.lat; c->eps = w.eps; c->x0_hist = w.x0_hist;
     c->ws_allocs = std::move(w.allocs);
     for (auto& kv : w.dbg) if (kv.first != "film" && kv.first != "temb") c->dbg[kv.first] = kv.second;
     c->graphs_valid = w.graphs_valid; c->graph_film = w.graph_film; c->graph_B = w.graph_B;

@@ -14,6 +14,10 @@ struct StepState {
     int n_steps;              // length of the schedule (0: single evaluation)
     const float* noise;       // [n_steps][n_elems] or NULL -> Philox
     unsigned long long seed;
+    // multistep schedules (hd_sample_multistep): this chain's x0 history [B_chain,4,L,L] and the [n_steps] table of the
+    // history coefficient c7.  NULL: single-step schedule (hd_sample) -- the update reads and writes nothing more.
+    float* x0_hist;
+    const float* c7;
 };
 
 // ----------------------------------------------------------------------------------- weight packing
@@ -160,7 +164,11 @@ struct SchedArgs {
 };
 __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned step, unsigned idx);
 // x0 = clamp((x - c0*eps)/c1, +-c2);  x <- c3*x0 + c4*x + c5*eps + c6*z      (hd_schedule in the C-ABI)
-__device__ __forceinline__ float sched_update(float xv, float e, const float* c, const StepState* st, int step, size_t gi, int n_total) {
+// and, with a history (st->x0_hist != NULL, hd_schedule_ms):  x <- ... + c7*h;  h <- x0.  gi: element index in the whole
+// batch (noise), li: in this chain (latents, history).  h is read only when c7 != 0, so an unwritten history never enters
+// step 0; lane-private (same element read and written by one lane).
+__device__ __forceinline__ float sched_update(float xv, float e, const float* c, const StepState* st, int step, size_t gi, int n_total,
+                                             size_t li) {
     float x0 = (xv - c[0] * e) / c[1];
     x0 = fminf(fmaxf(x0, -c[2]), c[2]);
     float r = c[3] * x0 + c[4] * xv + c[5] * e;
@@ -168,6 +176,12 @@ __device__ __forceinline__ float sched_update(float xv, float e, const float* c,
         // (the pointer is read from device memory: say that it is a global pointer, or the load is a flat load with a full wait)
         const float z = st->noise ? ((const __attribute__((address_space(1))) float*)st->noise)[(size_t)step * n_total + gi] : philox_normal(st->seed, (unsigned)step, (unsigned)gi);
         r += c[6] * z;
+    }
+    if (st->x0_hist) {
+        __attribute__((address_space(1))) float* h = (__attribute__((address_space(1))) float*)st->x0_hist;
+        const float c7 = ((const __attribute__((address_space(1))) float*)st->c7)[step];
+        if (c7 != 0.f) r += c7 * h[li];
+        h[li] = x0;
     }
     return r;
 }
@@ -255,7 +269,7 @@ __global__ __launch_bounds__(256) void ending_conv_kernel(const float* __restric
     eps[o] = e;
     if (sa.lat) {
         const int step = sa.st->step;
-        sa.lat[o] = sched_update(sa.lat[o], e, sa.coef + (size_t)step * 7, sa.st, step, (size_t)sa.elem0 + o, sa.n_total);
+        sa.lat[o] = sched_update(sa.lat[o], e, sa.coef + (size_t)step * 7, sa.st, step, (size_t)sa.elem0 + o, sa.n_total, o);
     }
 }
 
@@ -434,10 +448,11 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 }
 
 // The sampling loop applies the scheduler update inside ending_conv_kernel (sched_update); this kernel serves
-// hd_scheduler_step.
+// hd_scheduler_step (hist NULL) and hd_scheduler_step_multistep (hist: read for the c7 term when c7 != 0, then <- x0).
 struct Coef7 { float c[7]; };
 static __global__ void sched_step_direct_kernel(float* __restrict__ x, const float* __restrict__ eps, const Coef7 k,
-                                         const float* __restrict__ noise, unsigned long long seed, int step, long long n) {
+                                         const float* __restrict__ noise, unsigned long long seed, int step, long long n,
+                                         float* __restrict__ hist, float c7) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float xv = x[i], e = eps[i];
@@ -445,6 +460,10 @@ static __global__ void sched_step_direct_kernel(float* __restrict__ x, const flo
     x0 = fminf(fmaxf(x0, -k.c[2]), k.c[2]);
     float r = k.c[3] * x0 + k.c[4] * xv + k.c[5] * e;
     if (k.c[6] != 0.f) r += k.c[6] * (noise ? noise[i] : philox_normal(seed, (unsigned)step, (unsigned)i));
+    if (hist) {
+        if (c7 != 0.f) r += c7 * hist[i];
+        hist[i] = x0;
+    }
     x[i] = r;
 }
 

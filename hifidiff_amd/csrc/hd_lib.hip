@@ -86,13 +86,16 @@ int alloc_workspace_new(hd_ctx* c, int B) {
     const size_t per_face = (size_t)4 * c->L * c->L;
     int rc = 0;
     rc |= dev_alloc(c, &c->lat, (size_t)B * per_face); rc |= dev_alloc(c, &c->eps, (size_t)B * per_face);
+    rc |= dev_alloc(c, &c->x0_hist, (size_t)B * per_face);
     if (rc) return rc;
     c->dbg["lat"] = {c->lat, {(size_t)B * per_face, 0}}; c->dbg["eps"] = {c->eps, {(size_t)B * per_face, 0}};
+    c->dbg["x0_hist"] = {c->x0_hist, {(size_t)B * per_face, 0}};
     c->chains.resize(n);
     for (int i = 0; i < n; ++i) {
         Chain& ch = c->chains[i];
         ch.index = i; ch.B = B / n; ch.face0 = i * (B / n);
         ch.lat = c->lat + (size_t)ch.face0 * per_face; ch.eps = c->eps + (size_t)ch.face0 * per_face;
+        ch.x0_hist = c->x0_hist + (size_t)ch.face0 * per_face;
         rc = alloc_chain(c, ch);
         if (rc) return rc;
     }
@@ -1020,7 +1023,18 @@ int hd_scheduler_step(float* x_inout, const float* eps, const float* coef7, cons
     Coef7 k;
     for (int i = 0; i < 7; ++i) k.c[i] = coef7[i];
     hipLaunchKernelGGL(sched_step_direct_kernel, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       x_inout, eps, k, noise, (unsigned long long)seed, step, (long long)n_elems);
+                       x_inout, eps, k, noise, (unsigned long long)seed, step, (long long)n_elems, (float*)nullptr, 0.f);
+    return hipGetLastError() == hipSuccess ? HD_OK : HD_ERR_HIP;
+}
+
+int hd_scheduler_step_multistep(float* x_inout, const float* eps, const float* coef8, float* x0_hist, const float* noise, uint64_t seed,
+                                int step, int64_t n_elems, void* stream) {
+    if (!x_inout || !eps || !coef8 || n_elems <= 0) return HD_ERR_INVALID;
+    if (!x0_hist && coef8[7] != 0.f) return HD_ERR_INVALID;      // a history term needs the history
+    Coef7 k;
+    for (int i = 0; i < 7; ++i) k.c[i] = coef8[i];
+    hipLaunchKernelGGL(sched_step_direct_kernel, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                       x_inout, eps, k, noise, (unsigned long long)seed, step, (long long)n_elems, x0_hist, coef8[7]);
     return hipGetLastError() == hipSuccess ? HD_OK : HD_ERR_HIP;
 }
 
@@ -1054,16 +1068,15 @@ int hd_eps(hd_ctx* c, const float* x, const float* timesteps, int n_t, float* ep
     return HD_OK;
 }
 
-int hd_sample(hd_ctx* c, float* x_inout, const hd_schedule* sched, const float* noise, uint64_t seed, void* stream) {
-    int rc = check_ready(c, true);
-    if (rc) return rc;
-    rc = check_xcd(c);
-    if (rc) return rc;
-    if (!x_inout || !sched || sched->n_steps <= 0 || !sched->timesteps || !sched->coef) HD_FAIL(c, HD_ERR_INVALID, "hd_sample: bad arguments");
+// hd_sample (ncoef 7) and hd_sample_multistep (ncoef 8: c7 goes to its own [n] table, and every chain's StepState carries
+// its x0 history).  One captured graph serves both: the single-step path keeps its [n][7] table and a StepState whose
+// x0_hist is NULL, so its launches and their memory traffic are those of a single-step-only build.
+static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps, const float* coef, int ncoef, const float* noise,
+                       uint64_t seed, void* stream) {
     HIPCHECK(c, hipSetDevice(c->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int n = sched->n_steps;
-    rc = ensure_film_rows(c, n);
+    const bool ms = ncoef == 8;
+    int rc = ensure_film_rows(c, n);
     if (rc) return rc;
     if (n > c->coef_cap) {
         dev_free(c, c->coef_dev);
@@ -1074,15 +1087,23 @@ int hd_sample(hd_ctx* c, float* x_inout, const hd_schedule* sched, const float* 
         // parked workspaces captured the old coefficient buffer into their ending launch as well (SchedArgs::coef)
         for (auto& kv : c->ws_cache) kv.second.graphs_valid = false;
     }
+    if (ms && n > c->c7_cap) {                            // read through StepState: no graph holds this pointer
+        dev_free(c, c->c7_dev);
+        rc = dev_alloc(c, &c->c7_dev, (size_t)n);
+        if (rc) return rc;
+        c->c7_cap = n;
+    }
     const size_t per_face = (size_t)4 * c->L * c->L;
     const size_t nlat = (size_t)c->B * per_face;
     // schedule and loop state (step = -1: each chain's intro kernel pre-increments) go through a pinned staging buffer of
-    // the context, so the caller's host arrays are free on return and nothing here waits for the stream
+    // the context, so the caller's host arrays are free on return and nothing here waits for the stream.
+    // Layout: coef [n][7] | timesteps [n] | StepState (single-step), or coef | timesteps | c7 [n] | one StepState per chain.
     StepState st{};
     st.step = -1; st.n_steps = n; st.noise = noise; st.seed = seed;
     {
         auto& sg = c->stage[c->stage_idx ^= 1];
-        const size_t st_f = (sizeof(StepState) + 3) / 4, need = (size_t)n * 8 + st_f;
+        const size_t st_f = (sizeof(StepState) + 3) / 4, st0 = (size_t)n * (ms ? 9 : 8);
+        const size_t need = st0 + st_f * (ms ? c->chains.size() : 1);
         if (sg.pending) { HIPCHECK(c, hipEventSynchronize(sg.ev)); sg.pending = false; }     // the copy issued two calls ago
         if (sg.cap < need) {
             if (sg.host) (void)hipHostFree(sg.host);
@@ -1091,13 +1112,27 @@ int hd_sample(hd_ctx* c, float* x_inout, const hd_schedule* sched, const float* 
             sg.cap = need;
         }
         if (!sg.ev) HIPCHECK(c, hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
-        memcpy(sg.host, sched->coef, (size_t)n * 7 * sizeof(float));
-        memcpy(sg.host + (size_t)n * 7, sched->timesteps, (size_t)n * sizeof(float));
-        memcpy(sg.host + (size_t)n * 8, &st, sizeof(st));
+        if (!ms) {
+            memcpy(sg.host, coef, (size_t)n * 7 * sizeof(float));
+            memcpy(sg.host + st0, &st, sizeof(st));
+        } else {
+            for (int i = 0; i < n; ++i) {
+                memcpy(sg.host + (size_t)i * 7, coef + (size_t)i * 8, 7 * sizeof(float));
+                sg.host[(size_t)n * 8 + i] = coef[(size_t)i * 8 + 7];
+            }
+            st.c7 = c->c7_dev;
+            for (size_t k = 0; k < c->chains.size(); ++k) {
+                st.x0_hist = c->chains[k].x0_hist;
+                memcpy(sg.host + st0 + k * st_f, &st, sizeof(st));
+            }
+            HIPCHECK(c, hipMemcpyAsync(c->c7_dev, sg.host + (size_t)n * 8, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+        }
+        memcpy(sg.host + (size_t)n * 7, timesteps, (size_t)n * sizeof(float));
         HIPCHECK(c, hipMemcpyAsync(c->coef_dev, sg.host, (size_t)n * 7 * sizeof(float), hipMemcpyHostToDevice, s));
-        for (auto& ch : c->chains) HIPCHECK(c, hipMemcpyAsync(ch.step_state, sg.host + (size_t)n * 8, sizeof(st), hipMemcpyHostToDevice, s));
+        for (size_t k = 0; k < c->chains.size(); ++k)
+            HIPCHECK(c, hipMemcpyAsync(c->chains[k].step_state, sg.host + st0 + (ms ? k * st_f : 0), sizeof(st), hipMemcpyHostToDevice, s));
         const bool same_sched = c->film_valid && c->film_sched.size() == (size_t)n &&
-                                memcmp(c->film_sched.data(), sched->timesteps, (size_t)n * sizeof(float)) == 0;
+                                memcmp(c->film_sched.data(), timesteps, (size_t)n * sizeof(float)) == 0;
         if (!same_sched) HIPCHECK(c, hipMemcpyAsync(c->t_dev, sg.host + (size_t)n * 7, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
         HIPCHECK(c, hipEventRecord(sg.ev, s));
         sg.pending = true;
@@ -1108,7 +1143,7 @@ int hd_sample(hd_ctx* c, float* x_inout, const hd_schedule* sched, const float* 
             if (rc) return rc;
             if (!c->film_ev) HIPCHECK(c, hipEventCreateWithFlags(&c->film_ev, hipEventDisableTiming));
             HIPCHECK(c, hipEventRecord(c->film_ev, s));
-            c->film_sched.assign(sched->timesteps, sched->timesteps + n);
+            c->film_sched.assign(timesteps, timesteps + n);
             c->film_valid = true;
         } else {
             HIPCHECK(c, hipStreamWaitEvent(s, c->film_ev, 0));       // no-op on the stream that computed it
@@ -1161,6 +1196,27 @@ int hd_sample(hd_ctx* c, float* x_inout, const hd_schedule* sched, const float* 
     if (rc) return rc;
     HIPCHECK(c, hipMemcpyAsync(x_inout, c->lat, nlat * sizeof(float), hipMemcpyDeviceToDevice, s));
     return HD_OK;
+}
+
+int hd_sample(hd_ctx* c, float* x_inout, const hd_schedule* sched, const float* noise, uint64_t seed, void* stream) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    rc = check_xcd(c);
+    if (rc) return rc;
+    if (!x_inout || !sched || sched->n_steps <= 0 || !sched->timesteps || !sched->coef) HD_FAIL(c, HD_ERR_INVALID, "hd_sample: bad arguments");
+    return sample_impl(c, x_inout, sched->n_steps, sched->timesteps, sched->coef, 7, noise, seed, stream);
+}
+
+int hd_sample_multistep(hd_ctx* c, float* x_inout, const hd_schedule_ms* sched, const float* noise, uint64_t seed, void* stream) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    rc = check_xcd(c);
+    if (rc) return rc;
+    if (!x_inout || !sched || sched->n_steps <= 0 || !sched->timesteps || !sched->coef)
+        HD_FAIL(c, HD_ERR_INVALID, "hd_sample_multistep: bad arguments");
+    // the first step has no previous x0: the history of the call starts there (never inherited from an earlier call)
+    if (sched->coef[7] != 0.f) HD_FAIL(c, HD_ERR_INVALID, "hd_sample_multistep: row 0 must have c7 == 0 (no history before the first step)");
+    return sample_impl(c, x_inout, sched->n_steps, sched->timesteps, sched->coef, 8, noise, seed, stream);
 }
 
 static std::vector<Op>* which_program(hd_ctx* c, int which) {

@@ -41,7 +41,9 @@ def ddim_sample_eager_unconditional(model, latents, scheduler, num_inference_ste
 def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, prepare=True, check=True):
     """Whole loop on the GPU: returns the final latents (a new tensor).
 
-    noise: optional [n_steps, B, 4, L, L] tensor of z (DDPM); None -> device Philox(seed).
+    The scheduler's coefficient table picks the entry point: 7 columns (DDIM / DDPM) -> hd_sample, 8 columns
+    (DPMSolverMultistepScheduler) -> hd_sample_multistep.
+    noise: optional [n_steps, B, 4, L, L] tensor of z (DDPM, SDE-DPM-Solver++); None -> device Philox(seed).
     For the unconditional `Denoiser` pass cr_face = cr_latent = None.
     check=True (the default): ONE stream synchronisation after the whole loop (not per step), then RuntimeError if a persistent
     stage launch gave up during it -- where the reference's loop would have raised (test_refiner.py:89-91), so that the last batch
@@ -62,7 +64,8 @@ def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, pr
     x = latents.to(device=e.device, dtype=torch.float32).contiguous().clone()
     ts, coef = scheduler.coefficient_table()
     ts, coef = ts.contiguous(), coef.contiguous()
-    sch = _lib.Schedule()
+    multistep = coef.shape[1] == 8                         # DPMSolverMultistepScheduler: one history term (hd_schedule_ms)
+    sch = _lib.ScheduleMS() if multistep else _lib.Schedule()
     sch.n_steps = ts.numel()
     sch.timesteps = ctypes.cast(ts.data_ptr(), ctypes.POINTER(ctypes.c_float))
     sch.coef = ctypes.cast(coef.data_ptr(), ctypes.POINTER(ctypes.c_float))
@@ -73,8 +76,8 @@ def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, pr
             raise RuntimeError("noise must be [n_steps, B, 4, L, L]")
         nptr = noise.data_ptr()
     with torch.cuda.device(e.device):
-        _lib.check(_lib.lib().hd_sample(e.ctx, x.data_ptr(), ctypes.byref(sch), nptr, int(seed),
-                                        torch.cuda.current_stream(e.device).cuda_stream), e.ctx)
+        run = _lib.lib().hd_sample_multistep if multistep else _lib.lib().hd_sample
+        _lib.check(run(e.ctx, x.data_ptr(), ctypes.byref(sch), nptr, int(seed), torch.cuda.current_stream(e.device).cuda_stream), e.ctx)
     if check:
         e.check()
     return x

@@ -52,6 +52,18 @@ typedef struct hd_schedule {
     const float* coef;        /* [n_steps][7]                                                     */
 } hd_schedule;
 
+/* Multistep schedule: the coefficient form above plus one history term, h = the previous step's x0 of the same element.
+ * Replaces diffusers' DPMSolverMultistepScheduler (DPM-Solver++ 2M / SDE-DPM-Solver++ 2M, Lu et al. 2022, arXiv 2211.01095)
+ * swapped in for DDIMScheduler in the same loop:
+ *     x0     = clamp((x - c[0]*eps) / c[1], -c[2], +c[2])
+ *     x_prev = c[3]*x0 + c[4]*x + c[5]*eps + c[6]*z + c[7]*h          then  h <- x0
+ * h is read only where c[7] != 0; row 0 must have c[7] == 0 (the history of a call starts at its first step). */
+typedef struct hd_schedule_ms {
+    int32_t n_steps;
+    const float* timesteps;   /* [n_steps]                                                        */
+    const float* coef;        /* [n_steps][8]                                                     */
+} hd_schedule_ms;
+
 /* FacialRefiner(latent_res) (models/refiner.py:11-16): builds the network description for latent
  * side `latent_res` (16 for 16->128 px, 32 for 32->256 px) on HIP device `device`. */
 int hd_create(hd_ctx** out, int latent_res, int device);
@@ -127,12 +139,21 @@ int hd_eps(hd_ctx* ctx, const float* x, const float* timesteps, int n_t, float* 
  *          NULL to draw z on the device from Philox4x32-10(seed; step, element). */
 int hd_sample(hd_ctx* ctx, float* x_inout, const hd_schedule* sched, const float* noise,
               uint64_t seed, void* stream);
+/* The same loop with a multistep schedule (hd_schedule_ms): same graph, noise layout, Philox keying and hd_check semantics
+ * as hd_sample.  The x0 history lives in the context's workspace ("x0_hist", [B,4,L,L]) and is per call.
+ * HD_ERR_INVALID if row 0 has c[7] != 0. */
+int hd_sample_multistep(hd_ctx* ctx, float* x_inout, const hd_schedule_ms* sched, const float* noise,
+                        uint64_t seed, void* stream);
 
 /* One scheduler update on its own: `scheduler.step(eps, t, x).prev_sample` (test_refiner.py:91) in
  * the coefficient form of hd_schedule (coef7 on the host); x updated in place.  noise/seed/step as in
  * hd_sample.  Needs no context. */
 int hd_scheduler_step(float* x_inout, const float* eps, const float* coef7, const float* noise,
                       uint64_t seed, int step, int64_t n_elems, void* stream);
+/* One multistep update (coef8 on the host, hd_schedule_ms form): x0_hist [n_elems] device fp32 is read for the c[7] term and
+ * then overwritten with this step's x0.  x0_hist may be NULL only when c[7] == 0 (HD_ERR_INVALID otherwise). */
+int hd_scheduler_step_multistep(float* x_inout, const float* eps, const float* coef8, float* x0_hist, const float* noise,
+                                uint64_t seed, int step, int64_t n_elems, void* stream);
 
 /* Introspection for tests and profiling (not on the hot path; reads synchronise the device).
  * `which` selects the launch program: 0 = one denoiser evaluation (hd_eps / one hd_sample step),
