@@ -661,6 +661,10 @@ template <int C, int OWN = 32>
 inline hipError_t launch_face_stage(const FStageP& p, hipStream_t s) {
     typedef FaceCfg<C, OWN> K;
     if (p.B < 1 || p.B > 64 || p.nblocks < 1 || p.nblocks > XS_MAXBLK) return hipErrorInvalidValue;
+    // an entry this instantiation does not compile (the if-constexpr entries above) would leave its producer's output unwritten: refuse the launch, the caller
+    // then runs the producer's launch and the per-block launches
+    if ((p.intro_lat || p.up_A) && !(C == 128 && OWN == 32)) return hipErrorInvalidValue;
+    if (p.down_A && !(C == 256 && OWN == 16)) return hipErrorInvalidValue;
     static std::atomic<unsigned long long> granted{0};
         { const hipError_t e = grant_dynamic_lds(reinterpret_cast<const void*>(&naf_face_stage_kernel<C, OWN>), K::SMEM, granted); if (e != hipSuccess) return e; }
     hipLaunchKernelGGL((naf_face_stage_kernel<C, OWN>), dim3(64 * K::CL), dim3(K::THREADS), K::SMEM, s, p);

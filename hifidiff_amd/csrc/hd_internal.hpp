@@ -103,6 +103,8 @@ struct Chain {
     hipEvent_t done = nullptr;
     hipGraphExec_t graph_exec = nullptr;     // program + scheduler update of this chain, replayed per step
     hipGraphExec_t graph_multi = nullptr;    // kGraphSteps consecutive steps in one graph (the step index lives in device memory)
+    // what build_denoiser_program folded into this chain's program (hd_get_option reports these, not the switches)
+    bool fold_intro = false, fold_down0 = false, fold_up = false, fuse_end = false;
 };
 
 constexpr int kGraphSteps = 10;              // diffusion steps per captured graph in hd_sample (plus a one-step graph for the remainder)
@@ -237,7 +239,7 @@ struct hd_ctx {
     bool face_ok = false;                     // decided per context in setup_xcd (HD_NO_FACE / HD_NO_XCD at the time the context is finalized)
     bool face_on = true;                      // run-time switch (hd_set_option "face")
     int face_block_limit = 0;
-    bool end_fold = getenv("HD_NO_END_FOLD") == nullptr;   // the last HCA conv + the ending conv as one launch (hd_end.hpp); end_fused: cleared when its launch is refused
+    bool end_fold = true;                     // the last HCA conv + the ending conv as one launch (hd_end.hpp); end_fused: cleared when its launch is refused
     bool end_fused = true;
     bool up_fold = true;                      // the last up conv as the entry of the level-0 decoder stage (HD_NO_UP_FOLD=1: its own launch)
     bool down_fold = true;                    // the down conv of level 0 as the entry of the level-1 encoder stage (HD_NO_DOWN_FOLD=1: its own launch)

@@ -255,7 +255,9 @@ int build_denoiser_program(hd_ctx* c) {
         np = lv.C / 32; cnt = 32;
     };
     // the down conv of level 0 as the entry of the level-1 stage (same conditions as that stage; HD_NO_DOWN_FOLD=1 keeps the launch)
-    const bool fold_down0 = fold_intro && c->down_fold && c->ch->lv[1].C == 256 && c->ch->lv[1].H == 8 && c->den_down[0].K == 512 && c->den_down[0].N == 256;
+    // (only the 16-row instantiation of that stage has the entry: HD_FACE_L1_ROWS=32 keeps the launch)
+    const bool fold_down0 = fold_intro && c->down_fold && c->face_l1_rows == 16 && c->ch->lv[1].C == 256 && c->ch->lv[1].H == 8 && c->den_down[0].K == 512 && c->den_down[0].N == 256;
+    chp->fold_intro = fold_intro; chp->fold_down0 = fold_down0;
     std::vector<Op> down0;
     for (int l = 0; l < 4; ++l) {
         if (l >= 2) add_stage(enc[l], c->ch->lv[l], nullptr);
@@ -274,6 +276,7 @@ int build_denoiser_program(hd_ctx* c) {
     if (cond) add_hca(c, prog, "hcas.0", c->hca[0], c->ch->lv[4].Xg, c->ch->lv[4].Y, c->ch->lv[4].Yb, c->ch->lv[4].M, c->ch->lv[4].H);
     // (with the other folds: the program of the persistent stages; the one-launch-per-GEMM programs keep every launch and its tap)
     const bool fuse_end = cond && fold_intro && c->end_fold && L == 16 && c->ch->lv[0].C == 128 && c->ch->lv[0].H == 16 && !c->hca[4].centre_only;
+    chp->fuse_end = fuse_end;
     std::vector<Op> hca4;
     for (int i = 0; i < 4; ++i) {
         const int l = 3 - i;
@@ -283,6 +286,7 @@ int build_denoiser_program(hd_ctx* c) {
         // the last up conv as the entry of the level-0 decoder stage (same conditions as that stage; HD_NO_UP_FOLD=1 keeps the launch)
         const bool fold_up = i == 3 && fold_intro && c->up_fold && lo.C == 128 && lo.H == 16 && c->den_up[3].K == 256 && c->den_up[3].N == 512;
         std::vector<Op> up3;
+        if (i == 3) chp->fold_up = fold_up;
         add_up(c, fold_up ? up3 : prog, "ups." + std::to_string(i), c->den_up[i], cond ? hi.Yb : hi.Xb, true, hi.M, hi.H, hi.C, lo.X, lo.X, 2, lo.Xb, lo.sx);
         np = lo.C / 32; cnt = 32;
         GateOut g; g.gate_c = c->ch->gate_c[i + 1]; g.gate_s = c->ch->gate_s[i + 1];
@@ -512,6 +516,7 @@ int compute_film(hd_ctx* c, const float* t_dev, int n, hipStream_t s) {
 // program without them.
 int setup_xcd(hd_ctx* c) {
     c->xcd_ok = false; c->face_ok = false;
+    c->end_fold = getenv("HD_NO_END_FOLD") == nullptr;
     if (c->S != 1 || getenv("HD_NO_XCD")) return HD_OK;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, c->device) != hipSuccess || prop.multiProcessorCount != XS_GROUPS * XS_GROUP_WG) return HD_OK;
@@ -1311,10 +1316,15 @@ int hd_get_option(hd_ctx* c, const char* key) {
     if (k == "xcd2") return (c->xcd_ok && c->xcd_on && c->xcd2_on) ? c->xcd2_mask : 0;
     if (k == "xcd_stages") return (int)c->xstages.size();
     if (k == "face_stages") return (int)c->fstages.size();
-    if (k == "intro_fold") return (c->xcd_ok && c->face_ok && c->intro_fold) ? 1 : 0;
-    if (k == "end_fold") return (c->end_fold && c->end_fused) ? 1 : 0;
-    if (k == "up_fold") return (c->xcd_ok && c->face_ok && c->intro_fold && c->up_fold) ? 1 : 0;
-    if (k == "down_fold") return (c->xcd_ok && c->face_ok && c->intro_fold && c->down_fold) ? 1 : 0;
+    if (k == "face_l1_rows") return c->face_l1_rows;
+    // the folds of the program built for the batch in use (0 before the first call): the decisions build_denoiser_program made, and
+    // whether the launch that carries them still runs -- the face-stage entries need the face stages on and a single chain
+    const Chain* ch = c->chains.empty() ? nullptr : &c->chains[0];
+    const bool face_runs = c->xcd_ok && c->face_on && c->chains.size() == 1;
+    if (k == "intro_fold") return (ch && ch->fold_intro && face_runs) ? 1 : 0;
+    if (k == "down_fold") return (ch && ch->fold_down0 && face_runs) ? 1 : 0;
+    if (k == "up_fold") return (ch && ch->fold_up && face_runs) ? 1 : 0;
+    if (k == "end_fold") return (ch && ch->fuse_end && c->end_fused) ? 1 : 0;
     return HD_ERR_INVALID;
 }
 
