@@ -7,7 +7,7 @@
                 (or --scheduler dpmpp2m: DPM-Solver++ 2M, the usual diffusers swap for fewer evaluations, e.g. --steps 20)
     images    = vae.decode(latent / 0.18215).sample          # hifidiff_amd.vae         (test_refiner.py:93)
 
-    python examples/pipeline.py [--batch 8] [--scheduler ddim|dpmpp2m] [--steps 50]
+    python examples/pipeline.py [--batch 8] [--scheduler ddim|dpmpp2m] [--steps 50] [--strength 0.6]
 """
 import argparse
 import os
@@ -29,6 +29,8 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--scheduler", choices=("ddim", "dpmpp2m"), default="ddim")
     ap.add_argument("--steps", type=int, default=None, help="denoiser evaluations per face (default: 50 for ddim, 20 for dpmpp2m)")
+    ap.add_argument("--strength", type=float, default=None,
+                    help="img2img: start from cr_latent noised to this strength (diffusers' convention; default: off, pure-noise start)")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     dev = torch.device("cuda", 0)
@@ -60,7 +62,11 @@ def main():
     cr_latent = vae.encode_scaled(cr_face, 128, seed=7)                # bicubic (identity at 128) + encode + sample + x 0.18215
     torch.cuda.synchronize(); t2 = time.time()
     sch.set_timesteps(steps)
-    out = sampling.sample(model, latent, cr_face, cr_latent, sch)      # conditioning once + graph-replayed loop
+    if a.strength is None:
+        out = sampling.sample(model, latent, cr_face, cr_latent, sch)  # conditioning once + graph-replayed loop
+    else:                                                              # img2img: noise cr_latent to timesteps[start], run the remaining rows
+        latent, start = sampling.img2img_start(sch, cr_latent, a.strength, noise=latent)
+        out = sampling.sample(model, latent, cr_face, cr_latent, sch, start_steps=start)
     torch.cuda.synchronize(); t3 = time.time()
     images = vae.decode(out / 0.18215).sample                          # the reference's call form; decode_scaled(out) is the fused one
     torch.cuda.synchronize(); t4 = time.time()

@@ -17,7 +17,7 @@ import torch  # noqa: F401  (load order matters, see above)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhifidiff_hip.so")
 # translation units (compiled in parallel, one hipcc each) and the headers they include
-UNITS = [os.path.join(_HERE, "csrc", f) for f in ("hd_lib.hip", "hd_aux.hip", "hd_stages.hip", "hd_strip.hip", "hd_dispatch_ln.hip", "hd_dispatch_lnface.hip", "hd_dispatch_bf16.hip", "hd_dispatch_misc.hip")]
+UNITS = [os.path.join(_HERE, "csrc", f) for f in ("hd_lib.hip", "hd_aux.hip", "hd_stages.hip", "hd_stages_rows.hip", "hd_strip.hip", "hd_dispatch_ln.hip", "hd_dispatch_lnface.hip", "hd_dispatch_bf16.hip", "hd_dispatch_misc.hip")]
 SOURCES = UNITS + [os.path.join(_HERE, "csrc", f) for f in ("hd_gemm.hpp", "hd_dispatch.hpp", "hd_kernels.hpp", "hd_chain.hpp", "hd_conv.hpp", "hd_cr.hpp", "hd_vae.hpp", "hd_internal.hpp", "hd_stage_api.hpp", "hd_xcd.hpp", "hd_xcd2.hpp", "hd_face.hpp", "hd_strip.hpp", "hd_wide.hpp", "hd_end.hpp")]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "hifidiff_hip.h")
 
@@ -38,7 +38,7 @@ def unit_deps(unit):
 
 EXPORTS = [
     "hd_create", "hd_create_unconditional", "hd_prepare_unconditional", "hd_cr_create", "hd_cr_forward", "hd_vae_create", "hd_vae_encode", "hd_vae_decode", "hd_destroy", "hd_last_error", "hd_load_weights", "hd_finalize_weights", "hd_prepare",
-    "hd_prepare_from_priors", "hd_fpg", "hd_idc", "hd_eps", "hd_sample", "hd_sample_multistep", "hd_scheduler_step",
+    "hd_prepare_from_priors", "hd_fpg", "hd_idc", "hd_eps", "hd_sample", "hd_sample_multistep", "hd_sample_rows", "hd_sample_rows_multistep", "hd_scheduler_step",
     "hd_scheduler_step_multistep", "hd_num_ops", "hd_num_chains",
     "hd_debug_limit_ops", "hd_debug_op_name", "hd_debug_read_op", "hd_debug_read", "hd_debug_write", "hd_set_option", "hd_get_option", "hd_check",
     "hd_set_profiling", "hd_get_profile",
@@ -120,6 +120,8 @@ def lib():
     L.hd_sample.argtypes = [vp, vp, ctypes.POINTER(Schedule), vp, u64, vp]
     L.hd_scheduler_step.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_float), vp, u64, i32, i64, vp]
     L.hd_sample_multistep.argtypes = [vp, vp, ctypes.POINTER(ScheduleMS), vp, u64, vp]
+    L.hd_sample_rows.argtypes = [vp, vp, ctypes.POINTER(Schedule), vp, i32, vp, u64, vp]
+    L.hd_sample_rows_multistep.argtypes = [vp, vp, ctypes.POINTER(ScheduleMS), vp, i32, i32, vp, u64, vp]
     L.hd_scheduler_step_multistep.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_float), vp, vp, u64, i32, i64, vp]
     L.hd_num_ops.argtypes = [vp, i32]
     L.hd_num_chains.argtypes = [vp]

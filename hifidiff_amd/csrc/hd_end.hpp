@@ -39,6 +39,8 @@ struct EndCfg {
     static constexpr int SMEM = RED > XIN ? RED : XIN;
 };
 
+// PF: the per-face form of hd_sample_rows* (ending_conv_body's PF): sa.film_cur is [B][film_total], every face has its own schedule row
+template <bool PF = false>
 static __global__ __launch_bounds__(EndCfg::THREADS) void hca_ending_conv_kernel(const EndP p) {
     typedef EndCfg K;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -49,7 +51,16 @@ static __global__ __launch_bounds__(EndCfg::THREADS) void hca_ending_conv_kernel
     const int y0 = qd * K::OWNR;                                     // first own image row
 
     // ---- the next step's FiLM row to its fixed address (ending_conv_kernel's trailing workgroups): every workgroup moves its share ----
-    if (p.sa.lat) {
+    if (PF && p.sa.lat) {
+        // the four workgroups of a face move its row r_f + step + 1 (while it exists: a held face keeps its last row)
+        const int row = st_row(p.sa.st, face) + p.sa.st->step + 1;
+        if (row < p.sa.st->n_steps) {
+            const float4* src = reinterpret_cast<const float4*>(p.sa.film_table + (size_t)row * p.sa.film_total);
+            float4* dst = reinterpret_cast<float4*>(p.sa.film_cur + (size_t)face * p.sa.film_total);
+            for (int i = qd * K::THREADS + tid; i < p.sa.film_total / 4; i += 4 * K::THREADS) dst[i] = src[i];
+        }
+    }
+    if (!PF && p.sa.lat) {
         const int step = p.sa.st->step;
         if (step + 1 < p.sa.st->n_steps) {
             const float4* src = reinterpret_cast<const float4*>(p.sa.film_table + (size_t)(step + 1) * p.sa.film_total);
@@ -211,14 +222,23 @@ static __global__ __launch_bounds__(EndCfg::THREADS) void hca_ending_conv_kernel
     p.eps[o] = e;
     if (p.sa.lat) {
         const int step = p.sa.st->step;
-        p.sa.lat[o] = sched_update(p.sa.lat[o], e, p.sa.coef + (size_t)step * 7, p.sa.st, step, (size_t)p.sa.elem0 + o, p.sa.n_total, o);
+        if constexpr (PF) {
+            const int r = st_row(p.sa.st, face), k = r + step;       // workgroup-uniform: one face
+            if (k < p.sa.st->n_steps)
+                p.sa.lat[o] = sched_update<true>(p.sa.lat[o], e, p.sa.coef + (size_t)k * 7, p.sa.st, k, (size_t)p.sa.elem0 + o, p.sa.n_total, o,
+                                                 k == r && p.sa.st->hist_first);
+        } else {
+            p.sa.lat[o] = sched_update(p.sa.lat[o], e, p.sa.coef + (size_t)step * 7, p.sa.st, step, (size_t)p.sa.elem0 + o, p.sa.n_total, o);
+        }
     }
 }
 
-inline hipError_t launch_hca_ending(const EndP& p, hipStream_t s) {
-    static std::atomic<unsigned long long> granted{0};
-    { const hipError_t e = grant_dynamic_lds(reinterpret_cast<const void*>(&hca_ending_conv_kernel), EndCfg::SMEM, granted); if (e != hipSuccess) return e; }
-    hipLaunchKernelGGL(hca_ending_conv_kernel, dim3(p.B * 4), dim3(EndCfg::THREADS), EndCfg::SMEM, s, p);
+inline hipError_t launch_hca_ending(const EndP& p, hipStream_t s, bool per_face = false) {
+    static std::atomic<unsigned long long> granted{0}, granted_rows{0};
+    const void* fn = per_face ? reinterpret_cast<const void*>(&hca_ending_conv_kernel<true>) : reinterpret_cast<const void*>(&hca_ending_conv_kernel<false>);
+    { const hipError_t e = grant_dynamic_lds(fn, EndCfg::SMEM, per_face ? granted_rows : granted); if (e != hipSuccess) return e; }
+    if (per_face) hipLaunchKernelGGL(hca_ending_conv_kernel<true>, dim3(p.B * 4), dim3(EndCfg::THREADS), EndCfg::SMEM, s, p);
+    else hipLaunchKernelGGL(hca_ending_conv_kernel<false>, dim3(p.B * 4), dim3(EndCfg::THREADS), EndCfg::SMEM, s, p);
     return hipGetLastError();
 }
 

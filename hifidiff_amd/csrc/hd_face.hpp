@@ -24,6 +24,19 @@
 // members of a cluster get block ids that are equal mod 8 (one XCD under round-robin dispatch: speed only).  Every spin is
 // bounded; all workgroups of a face must be resident (512 workgroups at two per CU at level 0, 128 at level 1).
 #pragma once
+// Compiled twice: hd_stages.hip with one FiLM row for all faces (naf_face_stage_kernel), hd_stages_rows.hip with HD_FACE_ROWS = 1 -- the
+// per-face rows of hd_sample_rows* (naf_face_rows_stage_kernel: a workgroup owns rows of one face and reads that face's FiLM rows at
+// film + face * film_face_stride).  One source, two translation units: the shared-row kernel is the same code whether or not the other exists.
+#ifndef HD_FACE_ROWS
+#define HD_FACE_ROWS 0
+#endif
+#if HD_FACE_ROWS
+#define HD_FACE_KERNEL naf_face_rows_stage_kernel
+#define HD_FACE_LAUNCH launch_face_rows_stage
+#else
+#define HD_FACE_KERNEL naf_face_stage_kernel
+#define HD_FACE_LAUNCH launch_face_stage
+#endif
 #include "hd_chain.hpp"
 #include "hd_xcd.hpp"
 
@@ -75,7 +88,7 @@ __device__ __forceinline__ void face_load_b(const uint4* W, int tile, int lane, 
 }
 
 template <int C, int OWN = 32>
-__global__ __launch_bounds__((FaceCfg<C, OWN>::THREADS), 2) void naf_face_stage_kernel(const FStageP p) {      // two waves per SIMD: two 4-wave workgroups per CU at C = 128
+__global__ __launch_bounds__((FaceCfg<C, OWN>::THREADS), 2) void HD_FACE_KERNEL(const FStageP p) {      // two waves per SIMD: two 4-wave workgroups per CU at C = 128
     typedef FaceCfg<C, OWN> K;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ XBlockW s_blk[XS_MAXBLK];
@@ -374,7 +387,12 @@ __global__ __launch_bounds__((FaceCfg<C, OWN>::THREADS), 2) void naf_face_stage_
         float4 gbv = make_float4(0.f, 0.f, 0.f, 0.f);                // [bias_att | gain_att | bias_ffn | gain_ffn] at film_off: 4C floats
         const int gi = tid - 64;
         static_assert(K::THREADS - 64 >= C, "one float4 of the FiLM rows per thread of waves 1..");
+#if HD_FACE_ROWS
+        // per-face rows (hd_sample_rows*): this workgroup's face reads its own rows
+        if (gi >= 0 && gi < C) gbv = *reinterpret_cast<const float4*>(p.film + (size_t)face * p.film_face_stride + B.film_off + 4 * gi);
+#else
         if (gi >= 0 && gi < C) gbv = *reinterpret_cast<const float4*>(p.film + B.film_off + 4 * gi);
+#endif
         face_load_b<C>(B.w1, tile, lane, bw);
         if constexpr (C == 128) face_load_b<C>(B.w1, tile + K::NT, lane, bw2);    // C = 256: one gate half at a time (registers)
         // per-channel constants of the depthwise stage: requested with the weights at C = 128; at C = 256 the two weight sets
@@ -658,7 +676,7 @@ __global__ __launch_bounds__((FaceCfg<C, OWN>::THREADS), 2) void naf_face_stage_
 }
 
 template <int C, int OWN = 32>
-inline hipError_t launch_face_stage(const FStageP& p, hipStream_t s) {
+inline hipError_t HD_FACE_LAUNCH(const FStageP& p, hipStream_t s) {
     typedef FaceCfg<C, OWN> K;
     if (p.B < 1 || p.B > 64 || p.nblocks < 1 || p.nblocks > XS_MAXBLK) return hipErrorInvalidValue;
     // an entry this instantiation does not compile (the if-constexpr entries above) would leave its producer's output unwritten: refuse the launch, the caller
@@ -666,8 +684,8 @@ inline hipError_t launch_face_stage(const FStageP& p, hipStream_t s) {
     if ((p.intro_lat || p.up_A) && !(C == 128 && OWN == 32)) return hipErrorInvalidValue;
     if (p.down_A && !(C == 256 && OWN == 16)) return hipErrorInvalidValue;
     static std::atomic<unsigned long long> granted{0};
-        { const hipError_t e = grant_dynamic_lds(reinterpret_cast<const void*>(&naf_face_stage_kernel<C, OWN>), K::SMEM, granted); if (e != hipSuccess) return e; }
-    hipLaunchKernelGGL((naf_face_stage_kernel<C, OWN>), dim3(64 * K::CL), dim3(K::THREADS), K::SMEM, s, p);
+        { const hipError_t e = grant_dynamic_lds(reinterpret_cast<const void*>(&HD_FACE_KERNEL<C, OWN>), K::SMEM, granted); if (e != hipSuccess) return e; }
+    hipLaunchKernelGGL((HD_FACE_KERNEL<C, OWN>), dim3(64 * K::CL), dim3(K::THREADS), K::SMEM, s, p);
     return hipGetLastError();
 }
 

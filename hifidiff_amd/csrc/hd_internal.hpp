@@ -103,6 +103,11 @@ struct Chain {
     hipEvent_t done = nullptr;
     hipGraphExec_t graph_exec = nullptr;     // program + scheduler update of this chain, replayed per step
     hipGraphExec_t graph_multi = nullptr;    // kGraphSteps consecutive steps in one graph (the step index lives in device memory)
+    // the per-face-row form of the same two graphs (hd_sample_rows*; captured on first use): the LayerNorm loaders read hd_ctx::film_pf
+    // with a face stride, the ending launch stages every face's next row.  Valid while rows_gen / rows_film match the context.
+    hipGraphExec_t graph_rows_exec = nullptr, graph_rows_multi = nullptr;
+    unsigned rows_gen = 0;
+    const float* rows_film = nullptr;
     // what build_denoiser_program folded into this chain's program (hd_get_option reports these, not the switches)
     bool fold_intro = false, fold_down0 = false, fold_up = false, fuse_end = false;
 };
@@ -189,6 +194,23 @@ struct hd_ctx {
     int coef_cap = 0;
     float* c7_dev = nullptr;                  // [n] history coefficients of a multistep schedule (StepState::c7, not captured)
     int c7_cap = 0;
+    // per-face schedule positions (hd_sample_rows*): film_pf [B][film_total] holds every face's FiLM row of the current iteration (the
+    // LayerNorm loaders read it with film_face_stride = film_total while film_pf_mode is set, i.e. while the per-face graphs are captured);
+    // rows_dev [B] the faces' start rows.  rows_gen: bumped wherever the captured graphs go stale (Chain::rows_gen).
+    float* film_pf = nullptr;
+    size_t film_pf_cap = 0;
+    int* rows_dev = nullptr;
+    int rows_cap = 0;
+    bool film_pf_mode = false;
+    unsigned rows_gen = 1;
+    // the x0 history left by the last multistep call (hd_sample_rows_multistep resume = 1 continues it): valid for batch hist_B until
+    // hd_prepare* or a single-step sampling call
+    bool hist_valid = false;
+    int hist_B = 0;
+    // persistent-stage launches recorded by the last one-step capture of each form (hd_get_option "sample_stage_launches",
+    // "sample_face_stage_launches", "rows_stage_launches"); stage_count / face_stage_count count while a capture runs
+    int stage_count = 0, face_stage_count = 0;
+    int sample_stages = -1, sample_face_stages = -1, rows_stages = -1;
     int advance = 0;
     hipEvent_t fork_ev = nullptr;
     // hd_sample never blocks on the caller's stream: the schedule is staged through two pinned buffers owned by the
@@ -265,6 +287,11 @@ struct hd_ctx {
     std::map<std::string, std::pair<void*, std::pair<size_t, int>>> dbg;   // name -> (ptr, (elems, is_bf16))
 };
 
+// The FiLM rows a denoiser LayerNorm of chain chp reads: per-face rows (hd_sample_rows*), the staged row of the sampling loop, or the table
+inline const float* film_src(const hd_ctx* c, const Chain* chp) {
+    return c->film_pf_mode ? c->film_pf : c->film_from_cur ? chp->film_cur : c->film_table;
+}
+
 #define HD_FAIL(ctx, code, ...)                                   \
     do {                                                          \
         char _b[512];                                             \
@@ -302,6 +329,8 @@ void destroy_saved(SavedWs& w) {
     for (auto& ch : w.chains) {
         if (ch.graph_exec) (void)hipGraphExecDestroy(ch.graph_exec);
         if (ch.graph_multi) (void)hipGraphExecDestroy(ch.graph_multi);
+        if (ch.graph_rows_exec) (void)hipGraphExecDestroy(ch.graph_rows_exec);
+        if (ch.graph_rows_multi) (void)hipGraphExecDestroy(ch.graph_rows_multi);
         if (ch.stream) (void)hipStreamDestroy(ch.stream);
         if (ch.done) (void)hipEventDestroy(ch.done);
     }
@@ -646,7 +675,7 @@ void add_gemm(hd_ctx* c, std::vector<Op>& prog, const std::string& name, GemmP p
     op.run = [c, chp, gp, lk, ek, t128, film](hipStream_t s) mutable -> hipError_t {
                         if (film && gp->film == nullptr) {        // denoiser FiLM rows live in the (re-allocatable) table
                             GemmP q = *gp;
-                            q.film = c->film_from_cur ? chp->film_cur : c->film_table;
+                            q.film = film_src(c, chp);
                             q.film_face_stride = c->film_face_stride;
                             q.film_step_stride = 0;
                             q.step_ptr = nullptr;
@@ -698,7 +727,7 @@ void add_naf_block(hd_ctx* c, std::vector<Op>& prog, const BlockW& bw, const Lev
         op.name = bw.name + ".conv2_gate_pool"; op.out = lv.G; op.out_elems = (size_t)M * C; op.out_bf16 = 1;
         op.run = [c, chp, q](hipStream_t s) mutable -> hipError_t {
             StripP r = q;
-            if (r.film == nullptr) { r.film = c->film_from_cur ? chp->film_cur : c->film_table; r.film_face_stride = c->film_face_stride; }
+            if (r.film == nullptr) { r.film = film_src(c, chp); r.film_face_stride = c->film_face_stride; }
             return run_strip_dwgate(r, s);
         };
         prog.push_back(op);
@@ -752,7 +781,7 @@ void add_naf_block(hd_ctx* c, std::vector<Op>& prog, const BlockW& bw, const Lev
         op.run = [c, chp, q, big, two](hipStream_t s) mutable -> hipError_t {
             ChainP r = q;
             if (r.film == nullptr) {                      // denoiser: FiLM rows live in the (re-allocatable) table
-                r.film = c->film_from_cur ? chp->film_cur : c->film_table; r.film_face_stride = c->film_face_stride; r.film_step_stride = 0;
+                r.film = film_src(c, chp); r.film_face_stride = c->film_face_stride; r.film_step_stride = 0;
                 r.step_ptr = nullptr;
             }
             return big ? launch_chain<256, 1>(r, s) : two ? launch_chain<128, 2>(r, s) : launch_chain<128, 1>(r, s);

@@ -18,6 +18,11 @@ struct StepState {
     // history coefficient c7.  NULL: single-step schedule (hd_sample) -- the update reads and writes nothing more.
     float* x0_hist;
     const float* c7;
+    // per-face schedule positions (hd_sample_rows*): this chain's [B_chain] start rows r_f; face f is evaluated at row r_f + step
+    // and held (nothing written) from row n_steps on.  hist_first: a face's first row is first-order (no history before it: h := x0).
+    // NULL for hd_sample / hd_sample_multistep, whose launches never read these fields.
+    const int* start_rows;
+    int hist_first;
 };
 
 // ----------------------------------------------------------------------------------- weight packing
@@ -167,11 +172,20 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 // and, with a history (st->x0_hist != NULL, hd_schedule_ms):  x <- ... + c7*h;  h <- x0.  gi: element index in the whole
 // batch (noise), li: in this chain (latents, history).  h is read only when c7 != 0, so an unwritten history never enters
 // step 0; lane-private (same element read and written by one lane).
+// PF (per-face rows, hd_sample_rows*): `step` is the face's row k, and `first` (k == r_f with StepState::hist_first) makes that row
+// first-order (h := x0, see below).  PF = false is the code of hd_sample / hd_sample_multistep.
+// face f's start row (the pointer is read from device memory: a global pointer, as in sched_update)
+__device__ __forceinline__ int st_row(const StepState* st, int f) { return ((const __attribute__((address_space(1))) int*)st->start_rows)[f]; }
+template <bool PF = false>
 __device__ __forceinline__ float sched_update(float xv, float e, const float* c, const StepState* st, int step, size_t gi, int n_total,
-                                             size_t li) {
+                                             size_t li, bool first = false) {
     float x0 = (xv - c[0] * e) / c[1];
     x0 = fminf(fmaxf(x0, -c[2]), c[2]);
-    float r = c[3] * x0 + c[4] * xv + c[5] * e;
+    float c3 = c[3];
+    // a face's first row of a multistep call has no history: the row is taken first-order, h := x0 -- the x0 coefficient becomes c3 + c7
+    // (c3 = g (1 + k'), c7 = -g k' in a second-order row: their sum is the first-order g)
+    if (PF && first && st->x0_hist) c3 += ((const __attribute__((address_space(1))) float*)st->c7)[step];
+    float r = c3 * x0 + c[4] * xv + c[5] * e;
     if (c[6] != 0.f) {
         // (the pointer is read from device memory: say that it is a global pointer, or the load is a flat load with a full wait)
         const float z = st->noise ? ((const __attribute__((address_space(1))) float*)st->noise)[(size_t)step * n_total + gi] : philox_normal(st->seed, (unsigned)step, (unsigned)gi);
@@ -179,7 +193,8 @@ __device__ __forceinline__ float sched_update(float xv, float e, const float* c,
     }
     if (st->x0_hist) {
         __attribute__((address_space(1))) float* h = (__attribute__((address_space(1))) float*)st->x0_hist;
-        const float c7 = ((const __attribute__((address_space(1))) float*)st->c7)[step];
+        float c7 = ((const __attribute__((address_space(1))) float*)st->c7)[step];
+        if (PF && first) c7 = 0.f;
         if (c7 != 0.f) r += c7 * h[li];
         h[li] = x0;
     }
@@ -191,14 +206,33 @@ static __global__ void ending_weight_layout_kernel(const float* __restrict__ w, 
     const int co = i / (128 * 9), r = i - co * 128 * 9, ci = r / 9, tap = r - ci * 9;
     wT[(tap * 4 + co) * 128 + ci] = w[i];
 }
-template <int PXS>
+// PF (hd_sample_rows*): film_cur is the chain's [B][film_total] staging buffer and every face has its own row (StepState::start_rows);
+// the trailing workgroups stage ceil(film_total / 1024) float4 pieces of 256 threads x 4 per face (film_stage_pieces): grid = conv workgroups
+// + B * film_stage_pieces(film_total).
+__host__ __device__ constexpr int film_stage_pieces(int film_total) { return (film_total / 4 + 1023) / 1024; }
+template <int PXS, bool PF = false>
 __global__ __launch_bounds__(256) void ending_conv_kernel(const float* __restrict__ X, const float* __restrict__ wT,
                                                            const float* __restrict__ b, float* __restrict__ eps,
                                                            int B, int L, const SchedArgs sa) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nseg = B * L * (L / PXS);                                  // runs of PXS pixels (L is a multiple of 16)
     const int nb_conv = (nseg + 3) >> 2;
-    if ((int)blockIdx.x >= nb_conv) {
+    if (PF && (int)blockIdx.x >= nb_conv) {
+        // per face: row r_f + step + 1 of the table while it exists (a held face keeps its last row: its eps is discarded)
+        const int t = (int)blockIdx.x - nb_conv, np = film_stage_pieces(sa.film_total), f = t / np, piece = t - f * np;
+        if (f >= B) return;
+        const int row = st_row(sa.st, f) + sa.st->step + 1;
+        if (row >= sa.st->n_steps) return;
+        const float4* src = reinterpret_cast<const float4*>(sa.film_table + (size_t)row * sa.film_total);
+        float4* dst = reinterpret_cast<float4*>(sa.film_cur + (size_t)f * sa.film_total);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = piece * 1024 + j * 256 + (int)threadIdx.x;
+            if (i < sa.film_total / 4) dst[i] = src[i];
+        }
+        return;
+    }
+    if (!PF && (int)blockIdx.x >= nb_conv) {
         // trailing workgroups: stage the NEXT step's FiLM row at a fixed address, so that no LayerNorm loader of
         // the next replay has to chase the step index through memory before it can fetch its gain/bias
         const int step = sa.st->step;
@@ -269,8 +303,25 @@ __global__ __launch_bounds__(256) void ending_conv_kernel(const float* __restric
     eps[o] = e;
     if (sa.lat) {
         const int step = sa.st->step;
-        sa.lat[o] = sched_update(sa.lat[o], e, sa.coef + (size_t)step * 7, sa.st, step, (size_t)sa.elem0 + o, sa.n_total, o);
+        if constexpr (PF) {
+            const int r = st_row(sa.st, bb), k = r + step;          // the wave's run lies in one face: k is wave-uniform
+            if (k < sa.st->n_steps)
+                sa.lat[o] = sched_update<true>(sa.lat[o], e, sa.coef + (size_t)k * 7, sa.st, k, (size_t)sa.elem0 + o, sa.n_total, o,
+                                               k == r && sa.st->hist_first);
+        } else {
+            sa.lat[o] = sched_update(sa.lat[o], e, sa.coef + (size_t)step * 7, sa.st, step, (size_t)sa.elem0 + o, sa.n_total, o);
+        }
     }
+}
+
+// first FiLM rows of the per-face form: film_pf[f] = film_table[min(r_f, n - 1)] (a face that starts held reads a valid row)
+static __global__ void film_rows_gather_kernel(float* __restrict__ film_pf, const float* __restrict__ film_table, const int* __restrict__ rows,
+                                               int n, int film_total) {
+    const int f = blockIdx.y;
+    const int row = min(rows[f], n - 1);
+    const float4* src = reinterpret_cast<const float4*>(film_table + (size_t)row * film_total);
+    float4* dst = reinterpret_cast<float4*>(film_pf + (size_t)f * film_total);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < film_total / 4; i += gridDim.x * blockDim.x) dst[i] = src[i];
 }
 
 // ----------------------------------------------------------------------- depthwise 3x3 + gate + pool

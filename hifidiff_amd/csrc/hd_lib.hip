@@ -175,21 +175,23 @@ int build_denoiser_program(hd_ctx* c) {
         op.run = [c, chp, sp, sp2, have2, sub, l3, first](hipStream_t s) -> hipError_t {
             if (have2 && c->xcd_ok && c->xcd_on && c->xcd2_on && c->chains.size() == 1 && c->film_face_stride == 0) {
                 X2StageP r = sp2;
-                r.film = c->film_from_cur ? chp->film_cur : c->film_table;
+                r.film = film_src(c, chp);
                 r.phase_limit = (c->stage_limit_first < 0 || c->stage_limit_first == first) ? c->xcd_phase_limit : 0;
                 r.force_global = c->xcd_force_global; r.test_abort = c->stage_test_abort;
                 const hipError_t e = run_xcd2_stage(l3 ? 1024 : 512, r, s);
-                if (e == hipSuccess) return e;
+                if (e == hipSuccess) { ++c->stage_count; return e; }
                 (void)hipGetLastError();                      // refused launch (LDS / CU budget of this device or tenant): nothing ran -> the K-split form, then the per-GEMM launches
                 c->xcd2_on = false;
             }
-            if (c->xcd_ok && c->xcd_on && c->chains.size() == 1 && c->film_face_stride == 0) {
+            // (per-face rows of hd_sample_rows*: the K-split form's per-face instantiation; the autonomous-wave form above has none)
+            if (c->xcd_ok && c->xcd_on && c->chains.size() == 1 && (c->film_face_stride == 0 || c->film_pf_mode)) {
                 XStageP r = sp;
-                r.film = c->film_from_cur ? chp->film_cur : c->film_table;
+                r.film = film_src(c, chp);
+                r.film_face_stride = c->film_pf_mode ? c->film_total : 0;
                 r.phase_limit = (c->stage_limit_first < 0 || c->stage_limit_first == first) ? c->xcd_phase_limit : 0;
                 r.force_global = c->xcd_force_global; r.test_abort = c->stage_test_abort;
-                const hipError_t e = run_xcd_stage(l3 ? 1024 : 512, r, s);
-                if (e == hipSuccess) return e;
+                const hipError_t e = c->film_pf_mode ? run_xcd_rows_stage(l3 ? 1024 : 512, r, s) : run_xcd_stage(l3 ? 1024 : 512, r, s);
+                if (e == hipSuccess) { ++c->stage_count; return e; }
                 (void)hipGetLastError();                      // as the face stages below: a refused launch is recoverable
                 c->xcd_on = false;
             }
@@ -235,15 +237,18 @@ int build_denoiser_program(hd_ctx* c) {
         Op op;
         op.name = c->den_blocks[first + nblk - 1].name + ".conv5"; op.out = lv.X; op.out_elems = (size_t)lv.M * lv.C; op.out_bf16 = 0;
         op.run = [c, chp, fp, sub, c128, first, intro_first](hipStream_t s) -> hipError_t {
-            // (per-face timesteps and split batches run the per-GEMM form: one FiLM row and every workgroup resident are what the stage needs)
-            if (c->xcd_ok && c->face_on && c->chains.size() == 1 && c->film_face_stride == 0) {
+            // (hd_eps's per-face timesteps and split batches run the per-GEMM form: every workgroup resident is what the stage needs; the
+            // per-face rows of hd_sample_rows* have an instantiation of their own)
+            if (c->xcd_ok && c->face_on && c->chains.size() == 1 && (c->film_face_stride == 0 || c->film_pf_mode)) {
                 FStageP r = fp;
-                r.film = c->film_from_cur ? chp->film_cur : c->film_table;
+                r.film = film_src(c, chp);
+                r.film_face_stride = c->film_pf_mode ? c->film_total : 0;
                 r.block_limit = (c->stage_limit_first < 0 || c->stage_limit_first == first) ? c->face_block_limit : 0;
                 r.test_abort = c->stage_test_abort;
                 r.intro_advance = c->advance;
-                const hipError_t e = run_face_stage(c128 ? 128 : 256, c128 ? 32 : c->face_l1_rows, r, s);
-                if (e == hipSuccess) return e;
+                const hipError_t e = c->film_pf_mode ? run_face_rows_stage(c128 ? 128 : 256, c128 ? 32 : c->face_l1_rows, r, s)
+                                                     : run_face_stage(c128 ? 128 : 256, c128 ? 32 : c->face_l1_rows, r, s);
+                if (e == hipSuccess) { ++c->stage_count; ++c->face_stage_count; return e; }
                 (void)hipGetLastError();                      // (the dynamic-LDS grant was refused: nothing was launched) -> the per-block launches
                 c->face_on = false;
             }
@@ -323,8 +328,9 @@ int build_denoiser_program(hd_ctx* c) {
                                     q.sa.lat = chp->lat; q.sa.coef = c->coef_dev; q.sa.st = chp->step_state;
                                     q.sa.elem0 = (int)(chp->face0 * per_face); q.sa.n_total = (int)(c->B * per_face);
                                     q.sa.film_table = c->film_table; q.sa.film_cur = chp->film_cur; q.sa.film_total = c->film_total;
+                                    if (c->film_pf_mode) q.sa.film_cur = c->film_pf + (size_t)chp->face0 * c->film_total;   // this chain's faces
                                 }
-                                const hipError_t e = launch_hca_ending(q, s);
+                                const hipError_t e = launch_hca_ending(q, s, c->film_from_cur && c->film_pf_mode);
                                 if (e == hipSuccess) return e;
                                 (void)hipGetLastError();              // the dynamic-LDS grant was refused: nothing was launched -> the two launches
                                 c->end_fused = false;
@@ -337,6 +343,13 @@ int build_denoiser_program(hd_ctx* c) {
                                 sa.lat = chp->lat; sa.coef = c->coef_dev; sa.st = chp->step_state;
                                 sa.elem0 = (int)(chp->face0 * per_face); sa.n_total = (int)(c->B * per_face);
                                 sa.film_table = c->film_table; sa.film_cur = chp->film_cur; sa.film_total = c->film_total;
+                                if (c->film_pf_mode) {                // per-face rows: every face of this chain stages its own next row
+                                    sa.film_cur = c->film_pf + (size_t)chp->face0 * c->film_total;
+                                    nb += (unsigned)(B * film_stage_pieces(c->film_total));
+                                    if (long_runs) hipLaunchKernelGGL((ending_conv_kernel<16, true>), dim3(nb), dim3(256), 0, s, X, w, b, eps, B, L, sa);
+                                    else hipLaunchKernelGGL((ending_conv_kernel<kEndingPx, true>), dim3(nb), dim3(256), 0, s, X, w, b, eps, B, L, sa);
+                                    return hipGetLastError();
+                                }
                                 nb += (unsigned)((c->film_total / 4 + 255) / 256);
                             }
                             if (long_runs) hipLaunchKernelGGL(ending_conv_kernel<16>, dim3(nb), dim3(256), 0, s, X, w, b, eps, B, L, sa);
@@ -603,6 +616,7 @@ static int check_xcd(hd_ctx* c) {
         if (c->abort_dev) (void)hipMemset(c->abort_dev, 0, 64 * sizeof(unsigned));
         c->xcd_on = false; c->graphs_valid = false;
         for (auto& kv : c->ws_cache) kv.second.graphs_valid = false;
+        ++c->rows_gen;
         for (auto& kv : c->xstages) {
             (void)hipMemset(kv.second.sync, 0, (size_t)3 * 256 * sizeof(unsigned));
             if (kv.second.sync2) (void)hipMemset(kv.second.sync2, 0, (size_t)2048 * sizeof(unsigned));
@@ -670,6 +684,8 @@ void hd_destroy(hd_ctx* c) {
     for (auto& ch : c->chains) {
         if (ch.graph_exec) (void)hipGraphExecDestroy(ch.graph_exec);
         if (ch.graph_multi) (void)hipGraphExecDestroy(ch.graph_multi);
+        if (ch.graph_rows_exec) (void)hipGraphExecDestroy(ch.graph_rows_exec);
+        if (ch.graph_rows_multi) (void)hipGraphExecDestroy(ch.graph_rows_multi);
         if (ch.stream) (void)hipStreamDestroy(ch.stream);
         if (ch.done) (void)hipEventDestroy(ch.done);
     }
@@ -920,6 +936,7 @@ int hd_prepare_unconditional(hd_ctx* c, int batch, void* stream) {
     int rc = prepare_common(c, batch);
     if (rc) return rc;
     c->prepared = true;
+    c->hist_valid = false;                               // a new batch: no multistep history to resume
     return HD_OK;
 }
 
@@ -945,6 +962,7 @@ int hd_prepare(hd_ctx* c, int batch, const float* cr_latent, const float* cr_fac
     c->ch = &c->chains[0];
     if (rc) return rc;
     c->prepared = true;
+    c->hist_valid = false;                               // a new batch: no multistep history to resume
     return HD_OK;
 }
 
@@ -974,6 +992,7 @@ int hd_prepare_from_priors(hd_ctx* c, int batch, const float* const priors[5], c
     c->ch = &c->chains[0];
     if (rc) return rc;
     c->prepared = true;
+    c->hist_valid = false;                               // a new batch: no multistep history to resume
     return HD_OK;
 }
 
@@ -1076,11 +1095,14 @@ int hd_eps(hd_ctx* c, const float* x, const float* timesteps, int n_t, float* ep
 // hd_sample (ncoef 7) and hd_sample_multistep (ncoef 8: c7 goes to its own [n] table, and every chain's StepState carries
 // its x0 history).  One captured graph serves both: the single-step path keeps its [n][7] table and a StepState whose
 // x0_hist is NULL, so its launches and their memory traffic are those of a single-step-only build.
+// hd_sample_rows* (rows != NULL: host [B] start rows, already checked): n_iters iterations of the per-face graphs (Chain::graph_rows_*),
+// every chain's StepState carries its start rows; hist_first = !resume.  rows == NULL: n_iters == n, the graphs of hd_sample.
 static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps, const float* coef, int ncoef, const float* noise,
-                       uint64_t seed, void* stream) {
+                       uint64_t seed, void* stream, const int32_t* rows = nullptr, int n_iters = 0, int resume = 0) {
     HIPCHECK(c, hipSetDevice(c->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool ms = ncoef == 8;
+    const bool ms = ncoef == 8, pf = rows != nullptr;
+    if (!pf) n_iters = n;
     int rc = ensure_film_rows(c, n);
     if (rc) return rc;
     if (n > c->coef_cap) {
@@ -1091,6 +1113,20 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
         c->graphs_valid = false;
         // parked workspaces captured the old coefficient buffer into their ending launch as well (SchedArgs::coef)
         for (auto& kv : c->ws_cache) kv.second.graphs_valid = false;
+        ++c->rows_gen;
+    }
+    if (pf && (size_t)c->B * c->film_total > c->film_pf_cap) {   // the per-face graphs hold this pointer
+        dev_free(c, c->film_pf);
+        rc = dev_alloc(c, &c->film_pf, (size_t)c->B * c->film_total);
+        if (rc) return rc;
+        c->film_pf_cap = (size_t)c->B * c->film_total;
+        ++c->rows_gen;
+    }
+    if (pf && c->B > c->rows_cap) {                       // read through StepState: no graph holds this pointer
+        dev_free(c, c->rows_dev);
+        rc = dev_alloc(c, &c->rows_dev, (size_t)c->B);
+        if (rc) return rc;
+        c->rows_cap = c->B;
     }
     if (ms && n > c->c7_cap) {                            // read through StepState: no graph holds this pointer
         dev_free(c, c->c7_dev);
@@ -1102,13 +1138,15 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
     const size_t nlat = (size_t)c->B * per_face;
     // schedule and loop state (step = -1: each chain's intro kernel pre-increments) go through a pinned staging buffer of
     // the context, so the caller's host arrays are free on return and nothing here waits for the stream.
-    // Layout: coef [n][7] | timesteps [n] | StepState (single-step), or coef | timesteps | c7 [n] | one StepState per chain.
+    // Layout: coef [n][7] | timesteps [n] | StepState (single-step), or coef | timesteps | c7 [n] | one StepState per chain
+    // (multistep or per-face rows) | start rows [B] (per-face rows).
     StepState st{};
     st.step = -1; st.n_steps = n; st.noise = noise; st.seed = seed;
     {
         auto& sg = c->stage[c->stage_idx ^= 1];
         const size_t st_f = (sizeof(StepState) + 3) / 4, st0 = (size_t)n * (ms ? 9 : 8);
-        const size_t need = st0 + st_f * (ms ? c->chains.size() : 1);
+        const size_t nst = (ms || pf) ? c->chains.size() : 1, rows0 = st0 + st_f * nst;
+        const size_t need = rows0 + (pf ? (size_t)c->B : 0);
         if (sg.pending) { HIPCHECK(c, hipEventSynchronize(sg.ev)); sg.pending = false; }     // the copy issued two calls ago
         if (sg.cap < need) {
             if (sg.host) (void)hipHostFree(sg.host);
@@ -1119,23 +1157,28 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
         if (!sg.ev) HIPCHECK(c, hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
         if (!ms) {
             memcpy(sg.host, coef, (size_t)n * 7 * sizeof(float));
-            memcpy(sg.host + st0, &st, sizeof(st));
         } else {
             for (int i = 0; i < n; ++i) {
                 memcpy(sg.host + (size_t)i * 7, coef + (size_t)i * 8, 7 * sizeof(float));
                 sg.host[(size_t)n * 8 + i] = coef[(size_t)i * 8 + 7];
             }
             st.c7 = c->c7_dev;
-            for (size_t k = 0; k < c->chains.size(); ++k) {
-                st.x0_hist = c->chains[k].x0_hist;
-                memcpy(sg.host + st0 + k * st_f, &st, sizeof(st));
-            }
             HIPCHECK(c, hipMemcpyAsync(c->c7_dev, sg.host + (size_t)n * 8, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+        }
+        if (pf) st.hist_first = resume ? 0 : 1;
+        for (size_t k = 0; k < nst; ++k) {
+            if (ms) st.x0_hist = c->chains[k].x0_hist;
+            if (pf) st.start_rows = c->rows_dev + c->chains[k].face0;
+            memcpy(sg.host + st0 + k * st_f, &st, sizeof(st));
+        }
+        if (pf) {
+            memcpy(sg.host + rows0, rows, (size_t)c->B * sizeof(int32_t));
+            HIPCHECK(c, hipMemcpyAsync(c->rows_dev, sg.host + rows0, (size_t)c->B * sizeof(int32_t), hipMemcpyHostToDevice, s));
         }
         memcpy(sg.host + (size_t)n * 7, timesteps, (size_t)n * sizeof(float));
         HIPCHECK(c, hipMemcpyAsync(c->coef_dev, sg.host, (size_t)n * 7 * sizeof(float), hipMemcpyHostToDevice, s));
         for (size_t k = 0; k < c->chains.size(); ++k)
-            HIPCHECK(c, hipMemcpyAsync(c->chains[k].step_state, sg.host + st0 + (ms ? k * st_f : 0), sizeof(st), hipMemcpyHostToDevice, s));
+            HIPCHECK(c, hipMemcpyAsync(c->chains[k].step_state, sg.host + st0 + (nst > 1 ? k * st_f : 0), sizeof(st), hipMemcpyHostToDevice, s));
         const bool same_sched = c->film_valid && c->film_sched.size() == (size_t)n &&
                                 memcmp(c->film_sched.data(), timesteps, (size_t)n * sizeof(float)) == 0;
         if (!same_sched) HIPCHECK(c, hipMemcpyAsync(c->t_dev, sg.host + (size_t)n * 7, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
@@ -1158,14 +1201,29 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
     c->film_face_stride = 0;
     c->film_from_cur = true;
     c->advance = 1;
-    for (auto& ch : c->chains)                          // step 0's row; the ending launch of step i stages row i+1
-        HIPCHECK(c, hipMemcpyAsync(ch.film_cur, c->film_table, (size_t)c->film_total * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (!c->graphs_valid || c->graph_film != c->film_table || c->graph_B != c->B) {
+    if (pf) {                                           // every face's first row; the ending launch of iteration i stages rows r_f + i + 1
+        hipLaunchKernelGGL(film_rows_gather_kernel, dim3(8, c->B), dim3(256), 0, s, c->film_pf, c->film_table, c->rows_dev, n, c->film_total);
+        HIPCHECK(c, hipGetLastError());
+    } else {
+        for (auto& ch : c->chains)                      // step 0's row; the ending launch of step i stages row i+1
+            HIPCHECK(c, hipMemcpyAsync(ch.film_cur, c->film_table, (size_t)c->film_total * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    bool stale = !c->graphs_valid || c->graph_film != c->film_table || c->graph_B != c->B;
+    if (pf) {
+        stale = false;
+        for (auto& ch : c->chains) stale |= !ch.graph_rows_exec || ch.rows_gen != c->rows_gen || ch.rows_film != c->film_table;
+    }
+    if (stale) {
         // One graph per chain: its launch program + its scheduler update.  Faces never interact, so the
         // chains are independent over the whole loop and each graph is replayed on the chain's own stream.
+        // (per-face rows: the LayerNorm loaders read film_pf with a face stride while the program is captured)
+        if (pf) { c->film_pf_mode = true; c->film_face_stride = c->film_total; }
+        c->stage_count = c->face_stage_count = 0;
         for (auto& ch : c->chains) {
-            if (ch.graph_exec) { (void)hipGraphExecDestroy(ch.graph_exec); ch.graph_exec = nullptr; }
-            if (ch.graph_multi) { (void)hipGraphExecDestroy(ch.graph_multi); ch.graph_multi = nullptr; }
+            hipGraphExec_t& g1 = pf ? ch.graph_rows_exec : ch.graph_exec;
+            hipGraphExec_t& gm = pf ? ch.graph_rows_multi : ch.graph_multi;
+            if (g1) { (void)hipGraphExecDestroy(g1); g1 = nullptr; }
+            if (gm) { (void)hipGraphExecDestroy(gm); gm = nullptr; }
             for (int multi = 0; multi < 2; ++multi) {       // one step, and kGraphSteps steps back to back (fewer graph launches)
                 hipGraph_t graph = nullptr;
                 hipError_t e = hipStreamBeginCapture(ch.stream, hipStreamCaptureModeThreadLocal);
@@ -1175,28 +1233,35 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
                     hipError_t e2 = hipStreamEndCapture(ch.stream, &graph);
                     if (e == hipSuccess) e = e2;
                 }
-                if (e == hipSuccess) e = hipGraphInstantiate(multi ? &ch.graph_multi : &ch.graph_exec, graph, nullptr, nullptr, 0);
+                if (e == hipSuccess) e = hipGraphInstantiate(multi ? &gm : &g1, graph, nullptr, nullptr, 0);
                 if (graph) (void)hipGraphDestroy(graph);
-                if (e != hipSuccess) HD_FAIL(c, HD_ERR_HIP, "graph capture/instantiate failed: %s", hipGetErrorString(e));
+                if (e != hipSuccess) { c->film_pf_mode = false; c->film_face_stride = 0; HD_FAIL(c, HD_ERR_HIP, "graph capture/instantiate failed: %s", hipGetErrorString(e)); }
+                if (multi == 0 && &ch == &c->chains[0]) {      // the one-step program of chain 0: what hd_get_option reports
+                    (pf ? c->rows_stages : c->sample_stages) = c->stage_count;
+                    if (!pf) c->sample_face_stages = c->face_stage_count;
+                }
             }
+            if (pf) { ch.rows_gen = c->rows_gen; ch.rows_film = c->film_table; }
         }
-        c->graphs_valid = true; c->graph_film = c->film_table; c->graph_B = c->B;
+        c->film_pf_mode = false; c->film_face_stride = 0;
+        if (!pf) { c->graphs_valid = true; c->graph_film = c->film_table; c->graph_B = c->B; }
     }
     if (c->profiling) HIPCHECK(c, hipEventRecord(c->ev0, s));
     HIPCHECK(c, hipEventRecord(c->fork_ev, s));
     for (auto& ch : c->chains) HIPCHECK(c, hipStreamWaitEvent(ch.stream, c->fork_ev, 0));
     {
         int i = 0;
-        for (; i + graph_steps() <= n; i += graph_steps())
-            for (auto& ch : c->chains) HIPCHECK(c, hipGraphLaunch(ch.graph_multi, ch.stream));
-        for (; i < n; ++i)
-            for (auto& ch : c->chains) HIPCHECK(c, hipGraphLaunch(ch.graph_exec, ch.stream));
+        for (; i + graph_steps() <= n_iters; i += graph_steps())
+            for (auto& ch : c->chains) HIPCHECK(c, hipGraphLaunch(pf ? ch.graph_rows_multi : ch.graph_multi, ch.stream));
+        for (; i < n_iters; ++i)
+            for (auto& ch : c->chains) HIPCHECK(c, hipGraphLaunch(pf ? ch.graph_rows_exec : ch.graph_exec, ch.stream));
     }
     for (auto& ch : c->chains) {
         HIPCHECK(c, hipEventRecord(ch.done, ch.stream));
         HIPCHECK(c, hipStreamWaitEvent(s, ch.done, 0));
     }
-    if (c->profiling) { HIPCHECK(c, hipEventRecord(c->ev1, s)); c->last_steps = n; }
+    if (c->profiling) { HIPCHECK(c, hipEventRecord(c->ev1, s)); c->last_steps = n_iters; }
+    c->hist_valid = ms; c->hist_B = c->B;                // what a later hd_sample_rows_multistep(resume = 1) may continue
     rc = poison_on_abort(c, c->lat, nlat, s);
     if (rc) return rc;
     HIPCHECK(c, hipMemcpyAsync(x_inout, c->lat, nlat * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1222,6 +1287,46 @@ int hd_sample_multistep(hd_ctx* c, float* x_inout, const hd_schedule_ms* sched, 
     // the first step has no previous x0: the history of the call starts there (never inherited from an earlier call)
     if (sched->coef[7] != 0.f) HD_FAIL(c, HD_ERR_INVALID, "hd_sample_multistep: row 0 must have c7 == 0 (no history before the first step)");
     return sample_impl(c, x_inout, sched->n_steps, sched->timesteps, sched->coef, 8, noise, seed, stream);
+}
+
+// start rows in [0, n], n_iters in [1, n - min r_f]
+static int check_rows(hd_ctx* c, const char* fn, int n, const int32_t* rows, int n_iters) {
+    int rmin = n;
+    for (int f = 0; f < c->B; ++f) {
+        if (rows[f] < 0 || rows[f] > n) HD_FAIL(c, HD_ERR_INVALID, "%s: start_rows[%d] = %d outside [0, %d]", fn, f, rows[f], n);
+        if (rows[f] < rmin) rmin = rows[f];
+    }
+    if (n_iters < 1 || n_iters > n - rmin) HD_FAIL(c, HD_ERR_INVALID, "%s: n_iters = %d outside [1, %d]", fn, n_iters, n - rmin);
+    return HD_OK;
+}
+
+int hd_sample_rows(hd_ctx* c, float* x_inout, const hd_schedule* sched, const int32_t* start_rows, int n_iters, const float* noise,
+                   uint64_t seed, void* stream) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    rc = check_xcd(c);
+    if (rc) return rc;
+    if (!x_inout || !sched || sched->n_steps <= 0 || !sched->timesteps || !sched->coef || !start_rows)
+        HD_FAIL(c, HD_ERR_INVALID, "hd_sample_rows: bad arguments");
+    rc = check_rows(c, "hd_sample_rows", sched->n_steps, start_rows, n_iters);
+    if (rc) return rc;
+    return sample_impl(c, x_inout, sched->n_steps, sched->timesteps, sched->coef, 7, noise, seed, stream, start_rows, n_iters, 0);
+}
+
+int hd_sample_rows_multistep(hd_ctx* c, float* x_inout, const hd_schedule_ms* sched, const int32_t* start_rows, int n_iters, int resume,
+                             const float* noise, uint64_t seed, void* stream) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    rc = check_xcd(c);
+    if (rc) return rc;
+    if (!x_inout || !sched || sched->n_steps <= 0 || !sched->timesteps || !sched->coef || !start_rows || (resume != 0 && resume != 1))
+        HD_FAIL(c, HD_ERR_INVALID, "hd_sample_rows_multistep: bad arguments");
+    rc = check_rows(c, "hd_sample_rows_multistep", sched->n_steps, start_rows, n_iters);
+    if (rc) return rc;
+    if (resume && !(c->hist_valid && c->hist_B == c->B))
+        HD_FAIL(c, HD_ERR_INVALID, "hd_sample_rows_multistep: resume = 1 but no multistep history of this batch (no earlier multistep call, "
+                                   "hd_prepare since, another batch size or a single-step call in between)");
+    return sample_impl(c, x_inout, sched->n_steps, sched->timesteps, sched->coef, 8, noise, seed, stream, start_rows, n_iters, resume);
 }
 
 static std::vector<Op>* which_program(hd_ctx* c, int which) {
@@ -1307,6 +1412,7 @@ int hd_set_option(hd_ctx* c, const char* key, int value) {
     else HD_FAIL(c, HD_ERR_INVALID, "unknown option %s", key);
     c->graphs_valid = false;                               // captured graphs hold the old choice
     for (auto& kv : c->ws_cache) kv.second.graphs_valid = false;
+    ++c->rows_gen;
     return HD_OK;
 }
 int hd_get_option(hd_ctx* c, const char* key) {
@@ -1317,6 +1423,11 @@ int hd_get_option(hd_ctx* c, const char* key) {
     if (k == "xcd_stages") return (int)c->xstages.size();
     if (k == "face_stages") return (int)c->fstages.size();
     if (k == "face_l1_rows") return c->face_l1_rows;
+    // persistent-stage launches (face-cluster and XCD-local) recorded by the last one-step capture of hd_sample* / hd_sample_rows* (-1: none
+    // yet): a stage op that falls back to its per-block launches is not counted
+    if (k == "sample_stage_launches") return c->sample_stages;
+    if (k == "sample_face_stage_launches") return c->sample_face_stages;
+    if (k == "rows_stage_launches") return c->rows_stages;
     // the folds of the program built for the batch in use (0 before the first call): the decisions build_denoiser_program made, and
     // whether the launch that carries them still runs -- the face-stage entries need the face stages on and a single chain
     const Chain* ch = c->chains.empty() ? nullptr : &c->chains[0];

@@ -37,6 +37,7 @@ struct XStageP {
     unsigned long long* stamps;           // [phase][workgroup][8]: 0 start, 1 barrier passed, 2 K loop done, 3 epilogue stores issued, 4 drained, 5 published
     int dbg_no_a, dbg_no_w;               // timing-only what-ifs (results are garbage): activation loads through zero-record descriptors / no weight loads
 #endif
+    int film_face_stride;                 // per-face FiLM rows (hd_sample_rows*, xcd_rows_stage_kernel): face f's rows at film + f * film_face_stride
 };
 
 struct FStageP {
@@ -69,6 +70,8 @@ struct FStageP {
     unsigned long long* stamps;            // [block][workgroup][8]
     int dbg_no_w;                          // timing-only what-if (results are garbage): no weight loads
 #endif
+    // per-face FiLM rows (hd_sample_rows*): face f's rows at film + f * film_face_stride; 0 = one row for all faces (the shared-row kernel)
+    int film_face_stride;
 };
 struct X2StageP {
     int B, nblocks;
@@ -108,5 +111,8 @@ hipError_t run_xcd_stage(int C, const XStageP& p, hipStream_t s);
 hipError_t run_xcd2_stage(int C, const X2StageP& p, hipStream_t s);
 hipError_t run_strip_dwgate(const StripP& p, hipStream_t s);                        // hipErrorInvalidValue unless side = 32, C = 128
 hipError_t run_face_stage(int C, int own_rows, const FStageP& p, hipStream_t s);   // own_rows: pixel rows per workgroup, 32 (C = 128, 256) or 16 (C = 256)
+// the same with per-face FiLM rows (hd_sample_rows*): face f's rows at p.film + f * p.film_face_stride (hd_stages_rows.hip)
+hipError_t run_face_rows_stage(int C, int own_rows, const FStageP& p, hipStream_t s);
+hipError_t run_xcd_rows_stage(int C, const XStageP& p, hipStream_t s);             // the K-split XCD-local stages with per-face FiLM rows
 
 }  // namespace hd

@@ -35,6 +35,19 @@
 // may occupy the GPU's CUs for longer than the spin bound.
 #pragma once
 #include <type_traits>
+// Compiled twice (as hd_face.hpp): hd_stages.hip with one FiLM row for all faces (xcd_stage_kernel), hd_stages_rows.hip with HD_XCD_ROWS = 1 --
+// the per-face rows of hd_sample_rows* (xcd_rows_stage_kernel: the gain | bias image in LDS holds one [2C] row per face of the workgroup's
+// tile, [FCU][2C], read per row as the A tile is normalised; 64 KB at level 3, 16 KB at level 2).
+#ifndef HD_XCD_ROWS
+#define HD_XCD_ROWS 0
+#endif
+#if HD_XCD_ROWS
+#define HD_XCD_KERNEL xcd_rows_stage_kernel
+#define HD_XCD_LAUNCH launch_xcd_rows_stage
+#else
+#define HD_XCD_KERNEL xcd_stage_kernel
+#define HD_XCD_LAUNCH launch_xcd_stage
+#endif
 
 #include "hd_gemm.hpp"
 #include "hd_stage_api.hpp"
@@ -68,7 +81,7 @@ struct XcdCfg {
     static_assert(TPR * 4 >= NT, "partials per thread");
 };
 
-template <int C, int HW>
+template <int C, int HW, int GBF = 1>
 struct XLds {
     typedef XcdCfg<C, HW> K;
     char stage[K::WK * K::RCU * 32 * 2 * 4];              // wave-private A staging (8 x 4608 B), then the K-split partial tiles
@@ -77,7 +90,7 @@ struct XLds {
     float rs[(K::RCU / K::S) * 32];                       // depthwise row sums
     float pl[XS_FACES * 32];                              // pooled tile / sca tile
     float2 stats[K::RCU];                                 // (mean, rstd) per row
-    float gb[2 * C];                                      // FiLM gain | bias
+    float gb[GBF * 2 * C];                                // FiLM gain | bias (per-face rows: [face of the tile][gain | bias])
     float dwc[22 * 32];                                   // per-column constants of the fused depthwise epilogue
     XBlockW blk[XS_MAXBLK];
     unsigned base, local, abort, pad_;
@@ -113,9 +126,9 @@ __device__ __forceinline__ void xs_lds_barrier() { asm volatile("s_waitcnt lgkmc
 #endif
 
 template <int C, int HW>
-__global__ __launch_bounds__(XS_THREADS) void xcd_stage_kernel(const XStageP p) {
+__global__ __launch_bounds__(XS_THREADS) void HD_XCD_KERNEL(const XStageP p) {
     typedef XcdCfg<C, HW> K;
-    __shared__ __attribute__((aligned(16))) XLds<C, HW> L;
+    __shared__ __attribute__((aligned(16))) XLds<C, HW, HD_XCD_ROWS ? XcdCfg<C, HW>::FCU : 1> L;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int group = blockIdx.x & 7, rank = blockIdx.x >> 3;        // blocks b and b + 8 share an XCD under round-robin dispatch (speed only)
     const int face_g0 = group * XS_FACES;
@@ -234,13 +247,25 @@ __global__ __launch_bounds__(XS_THREADS) void xcd_stage_kernel(const XStageP p) 
         for (int d = 0; d < K::CPW; ++d) {
             const int k = (c0 + d) * 64 + 8 * kq;
             f32x2_t g[4], b[4];
+#if !HD_XCD_ROWS
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 g[i] = *reinterpret_cast<const f32x2_t*>(&L.gb[k + 2 * i]);
                 b[i] = *reinterpret_cast<const f32x2_t*>(&L.gb[C + k + 2 * i]);
             }
+#endif
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
+#if HD_XCD_ROWS
+                {                                                    // this row's face inside the tile
+                    const float* gbf = &L.gb[((wm * 32 + (lane >> 3) + 8 * u) / HW) * 2 * C];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        g[i] = *reinterpret_cast<const f32x2_t*>(&gbf[k + 2 * i]);
+                        b[i] = *reinterpret_cast<const f32x2_t*>(&gbf[C + k + 2 * i]);
+                    }
+                }
+#endif
                 const unsigned w[4] = {aq[d][u].x, aq[d][u].y, aq[d][u].z, aq[d][u].w};
                 unsigned o[4];
 #pragma unroll
@@ -272,6 +297,9 @@ __global__ __launch_bounds__(XS_THREADS) void xcd_stage_kernel(const XStageP p) 
     // The (small) loads go out BEFORE the A rows, the merge runs while those are still arriving (loads return in order).
     float2 ln_ps[4];
     float4 ln_g = make_float4(0.f, 0.f, 0.f, 0.f), ln_b = ln_g;
+#if HD_XCD_ROWS
+    int ln_film_off = 0;
+#endif
     auto ln_issue = [&](const __amdgpu_buffer_rsrc_t& rs, int film_bias_off) __attribute__((always_inline)) {
         constexpr int TPR = K::TPR;
         const int rl = tid / TPR, part = tid % TPR, row = row0 + rl;
@@ -288,20 +316,36 @@ __global__ __launch_bounds__(XS_THREADS) void xcd_stage_kernel(const XStageP p) 
         // FiLM gain / bias of this LayerNorm: [bias | gain] at film_bias_off (written by an earlier launch: plain loads)
         static_assert(C <= XS_THREADS * 4, "one float4 of gain and bias per thread");
         const int k = tid * 4;
+#if HD_XCD_ROWS
+        ln_film_off = film_bias_off;                                      // per-face rows: read in ln_finish, one row per face of the tile
+        (void)k;
+#else
         if (k < C) {
             ln_b = *reinterpret_cast<const float4*>(p.film + film_bias_off + k);
             ln_g = *reinterpret_cast<const float4*>(p.film + film_bias_off + C + k);
         }
+#endif
     };
     auto ln_finish = [&]() __attribute__((always_inline)) {
         constexpr int TPR = K::TPR;
         const int rl = tid / TPR, part = tid % TPR;
         const bool rv = row0 + rl < M;
         const int k = tid * 4;
+#if HD_XCD_ROWS
+        (void)ln_g; (void)ln_b; (void)k;
+        for (int q = tid; q < K::FCU * (C / 4); q += XS_THREADS) {        // [face][gain | bias]: faces past the batch read face 0's row
+            const int f = q / (C / 4), kk = (q - f * (C / 4)) * 4;
+            const int face = (face0 + f) < p.B ? face0 + f : 0;
+            const float* src = p.film + (size_t)face * p.film_face_stride + ln_film_off;
+            *reinterpret_cast<float4*>(&L.gb[f * 2 * C + kk]) = *reinterpret_cast<const float4*>(src + C + kk);
+            *reinterpret_cast<float4*>(&L.gb[f * 2 * C + C + kk]) = *reinterpret_cast<const float4*>(src + kk);
+        }
+#else
         if (k < C) {
             *reinterpret_cast<float4*>(&L.gb[k]) = ln_g;
             *reinterpret_cast<float4*>(&L.gb[C + k]) = ln_b;
         }
+#endif
         auto row_sum = [](float v) __attribute__((always_inline)) {
             if (TPR > 1) v += dpp_mov<0xB1>(v);
             if (TPR > 2) v += dpp_mov<0x4E>(v);
@@ -748,9 +792,9 @@ __global__ __launch_bounds__(XS_THREADS) void xcd_stage_kernel(const XStageP p) 
 }
 
 template <int C, int HW>
-inline hipError_t launch_xcd_stage(const XStageP& p, hipStream_t s) {
+inline hipError_t HD_XCD_LAUNCH(const XStageP& p, hipStream_t s) {
     if (p.B < 1 || p.B > XS_GROUPS * XS_FACES || p.nblocks < 1 || p.nblocks > XS_MAXBLK) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((xcd_stage_kernel<C, HW>), dim3(XS_GROUPS * XS_GROUP_WG), dim3(XS_THREADS), 0, s, p);
+    hipLaunchKernelGGL((HD_XCD_KERNEL<C, HW>), dim3(XS_GROUPS * XS_GROUP_WG), dim3(XS_THREADS), 0, s, p);
     return hipGetLastError();
 }
 

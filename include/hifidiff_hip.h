@@ -145,6 +145,22 @@ int hd_sample(hd_ctx* ctx, float* x_inout, const hd_schedule* sched, const float
 int hd_sample_multistep(hd_ctx* ctx, float* x_inout, const hd_schedule_ms* sched, const float* noise,
                         uint64_t seed, void* stream);
 
+/* Per-face schedule positions: the same loop where every face f starts at its own row r_f = start_rows[f] (host [B], 0 <= r_f <= n_steps)
+ * of one shared table.  Replaces diffusers' img2img convention -- `get_timesteps(num_inference_steps, strength)` + `scheduler.add_noise(
+ * init_latents, noise, timesteps[t_start])`, then the loop of test_refiner.py:85-91 over the remaining rows -- with one strength per face,
+ * and a loop split over several calls (preview / cancel / time-slicing).  The call runs n_iters iterations, 1 <= n_iters <= n_steps - min r_f:
+ * at iteration i face f is evaluated at row k = r_f + i (timesteps[k], FiLM row k, coefficient row k, z = noise[k] or Philox(seed; k, element),
+ * so all r_f = 0 and n_iters = n_steps is hd_sample bit for bit); from k = n_steps on the face is held (its latents are not written).
+ * The step graphs of this form are captured on first use, next to hd_sample's.  HD_ERR_INVALID for a row or n_iters out of range. */
+int hd_sample_rows(hd_ctx* ctx, float* x_inout, const hd_schedule* sched, const int32_t* start_rows, int n_iters, const float* noise,
+                   uint64_t seed, void* stream);
+/* The same with a multistep schedule (hd_sample_multistep; a held face's history is not written either).  resume = 0: each face's history
+ * starts at its own first row, which is taken first-order as diffusers' img2img does: h := x0 there, so x0 is multiplied by c[3] + c[7].  resume = 1: the history the previous multistep call on this context left for
+ * this batch is continued, so a loop split over calls (start rows advanced by the caller) reproduces the one-call loop bit for bit;
+ * HD_ERR_INVALID when there is none (no earlier multistep call, hd_prepare* since, another batch size, or hd_sample / hd_sample_rows in between). */
+int hd_sample_rows_multistep(hd_ctx* ctx, float* x_inout, const hd_schedule_ms* sched, const int32_t* start_rows, int n_iters, int resume,
+                             const float* noise, uint64_t seed, void* stream);
+
 /* One scheduler update on its own: `scheduler.step(eps, t, x).prev_sample` (test_refiner.py:91) in
  * the coefficient form of hd_schedule (coef7 on the host); x updated in place.  noise/seed/step as in
  * hd_sample.  Needs no context. */
@@ -174,7 +190,9 @@ int hd_debug_write(hd_ctx* ctx, const char* name, const float* host_in, int64_t 
  * launch per GEMM; "face" 1/0 the same for levels 0 / 1 (hd_face.hpp); "xcd_phase_limit" n / "face_block_limit" n = stop
  * the persistent stages after n phases / blocks (0: all), "stage_limit_first" i = only the stage whose first block has index
  * i (-1: every stage) -- tests read a stage's residual stream block by block; "xcd_force_global" 1 = its
- * placement-independent hand-off form.  hd_get_option: "xcd" (effective), "xcd_stages" (stages built so far). */
+ * placement-independent hand-off form.  hd_get_option: "xcd" (effective), "xcd_stages" (stages built so far);
+ * "sample_stage_launches" / "sample_face_stage_launches" / "rows_stage_launches": persistent-stage launches (all / face-cluster only) that
+ * the last one-step capture of hd_sample* / hd_sample_rows* recorded (-1 before the first capture; a stage that fell back is not counted). */
 int hd_set_option(hd_ctx* ctx, const char* key, int value);
 int hd_get_option(hd_ctx* ctx, const char* key);
 /* Error status of the asynchronous calls.  hd_eps / hd_sample only enqueue work; a persistent stage launch that has to give
