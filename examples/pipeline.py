@@ -8,6 +8,7 @@
     images    = vae.decode(latent / 0.18215).sample          # hifidiff_amd.vae         (test_refiner.py:93)
 
     python examples/pipeline.py [--batch 8] [--scheduler ddim|dpmpp2m] [--steps 50] [--strength 0.6]
+    python examples/pipeline.py --stream 200 [--refill-every 5] [--batch 64]    # continuous batching of 200 requests, mixed strengths
 """
 import argparse
 import os
@@ -31,6 +32,10 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="denoiser evaluations per face (default: 50 for ddim, 20 for dpmpp2m)")
     ap.add_argument("--strength", type=float, default=None,
                     help="img2img: start from cr_latent noised to this strength (diffusers' convention; default: off, pure-noise start)")
+    ap.add_argument("--stream", type=int, default=None, metavar="N",
+                    help="continuous batching: N synthetic requests with strengths in [0.2, 1.0] through sampling.ContinuousSampler "
+                         "(--batch slots), then VAE decode")
+    ap.add_argument("--refill-every", type=int, default=5, metavar="K", help="--stream: iterations per call between refills")
     a = ap.parse_args()
     torch.set_grad_enabled(False)
     dev = torch.device("cuda", 0)
@@ -51,6 +56,9 @@ def main():
         sch = schedulers.DPMSolverMultistepScheduler(num_train_timesteps=1000, beta_schedule="scaled_linear",
                                                      prediction_type="epsilon", solver_order=2, algorithm_type="dpmsolver++")
     steps = a.steps or (50 if a.scheduler == "ddim" else 20)
+
+    if a.stream is not None:
+        return stream(a, cr, vae, model, sch, steps, dev)
 
     B = a.batch
     ln_face = torch.from_numpy(np.stack([synth.rand(f"ln_face/{f}", (3, 128, 128)) for f in range(B)])).to(dev)
@@ -73,6 +81,35 @@ def main():
     print(f"batch {B}: coarse restoration {1e3 * (t1 - t0):.1f} ms, VAE encode {1e3 * (t2 - t1):.1f} ms, {steps}-step {a.scheduler} "
           f"{1e3 * (t3 - t2):.1f} ms, VAE decode {1e3 * (t4 - t3):.1f} ms; latent range [{float(out.min()):.2f}, {float(out.max()):.2f}], "
           f"images {tuple(images.shape)} finite {bool(torch.isfinite(images).all())}")
+
+
+def stream(a, cr, vae, model, sch, steps, dev):
+    """N requests, each with its own seed and strength, through the serving loop: a finished face leaves its slot and the next request
+    takes it (FacialRefiner.prepare_slots), so no slot waits for the slowest face of a batch."""
+    N = a.stream
+    g = torch.Generator().manual_seed(3)
+    strength = (0.2 + 0.8 * torch.rand(N, generator=g)).tolist()
+    torch.cuda.synchronize(); t0 = time.time()
+    reqs = []
+    for b in range(0, N, 64):                                          # coarse restoration + VAE encode of the requests, 64 at a time
+        n = min(64, N - b)
+        ln_face = torch.from_numpy(np.stack([synth.rand(f"ln_face/{f}", (3, 128, 128)) for f in range(b, b + n)])).to(dev)
+        cr_face = cr(ln_face)
+        cr_latent = vae.encode_scaled(cr_face, 128, seed=7 + b)
+        reqs += [(cr_face[i], cr_latent[i]) for i in range(n)]
+    sch.set_timesteps(steps)
+    cs = sampling.ContinuousSampler(model, sch, batch=a.batch, refill_every=a.refill_every)
+    torch.cuda.synchronize(); t1 = time.time()
+    ids = [cs.submit(f, l, seed=1000 + i, strength=strength[i]) for i, (f, l) in enumerate(reqs)]
+    out = cs.drain()
+    torch.cuda.synchronize(); t2 = time.time()
+    lat = torch.stack([out[i] for i in ids])
+    images = vae.decode(lat / 0.18215).sample
+    torch.cuda.synchronize(); t3 = time.time()
+    print(f"stream of {N} requests (strength 0.2..1.0), {a.batch} slots, refill every {a.refill_every}: coarse restoration + VAE encode "
+          f"{1e3 * (t1 - t0):.1f} ms, {steps}-step {a.scheduler} {1e3 * (t2 - t1):.1f} ms ({N / (t2 - t1):.1f} faces/s, {cs.calls} calls, "
+          f"{cs.refilled} slots refilled), VAE decode {1e3 * (t3 - t2):.1f} ms; images {tuple(images.shape)} finite "
+          f"{bool(torch.isfinite(images).all())}")
 
 
 if __name__ == "__main__":

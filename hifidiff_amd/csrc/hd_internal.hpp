@@ -128,6 +128,7 @@ struct SavedWs {
     uint64_t stamp = 0;
     std::vector<Chain> chains;
     float *lat = nullptr, *eps = nullptr, *x0_hist = nullptr;
+    Chain slot_stage; bool slot_stage_ok = false; int* slots_dev = nullptr;
     std::vector<void*> allocs;
     std::map<std::string, std::pair<void*, std::pair<size_t, int>>> dbg;
     bool graphs_valid = false;
@@ -184,6 +185,11 @@ struct hd_ctx {
     float *lat = nullptr, *eps = nullptr;    // [B,4,L,L] of the whole batch; chains own contiguous face ranges
     float* x0_hist = nullptr;                // [B,4,L,L]: previous step's x0 of a multistep schedule (hd_sample_multistep)
     bool prepared = false;
+    // hd_prepare_slots: a private chain of capacity B (allocated on first use, owned and parked with this workspace) on which the
+    // conditioning prologue runs at batch n, and the [B] device list of the slots it is scattered to
+    Chain slot_stage;
+    bool slot_stage_ok = false;
+    int* slots_dev = nullptr;
 
     // FiLM / schedule
     float *t_dev = nullptr, *temb_a = nullptr, *temb_b = nullptr, *temb_c = nullptr, *film_table = nullptr;
@@ -207,6 +213,14 @@ struct hd_ctx {
     // hd_prepare* or a single-step sampling call
     bool hist_valid = false;
     int hist_B = 0;
+    // the same per face (hd_sample_faces_multistep resume[f] = 1 needs hist_face[f]): [hist_B] flags, cleared where hist_valid is, per slot
+    // by hd_prepare_slots; set for every face that ran a row of a multistep rows / faces call
+    std::vector<char> hist_face;
+    // per-face Philox keys and first-order flags of hd_sample_faces* ([B] each, read through StepState: no graph holds these pointers)
+    unsigned long long* seeds_dev = nullptr;
+    int* first_dev = nullptr;
+    int faces_cap = 0;
+    int graph_captures = 0;                   // step-graph instantiations of this context (hd_get_option "graph_captures")
     // persistent-stage launches recorded by the last one-step capture of each form (hd_get_option "sample_stage_launches",
     // "sample_face_stage_launches", "rows_stage_launches"); stage_count / face_stage_count count while a capture runs
     int stage_count = 0, face_stage_count = 0;
@@ -325,7 +339,13 @@ void dev_free(hd_ctx* c, void* p) {
 }
 
 constexpr size_t kWsCached = 3;
+void destroy_chain_queue(Chain& ch) {
+    if (ch.stream) (void)hipStreamDestroy(ch.stream);
+    if (ch.done) (void)hipEventDestroy(ch.done);
+    ch.stream = nullptr; ch.done = nullptr;
+}
 void destroy_saved(SavedWs& w) {
+    if (w.slot_stage_ok) destroy_chain_queue(w.slot_stage);
     for (auto& ch : w.chains) {
         if (ch.graph_exec) (void)hipGraphExecDestroy(ch.graph_exec);
         if (ch.graph_multi) (void)hipGraphExecDestroy(ch.graph_multi);
@@ -343,6 +363,8 @@ void park_workspace(hd_ctx* c) {
     SavedWs w;
     w.B = c->B; w.stamp = ++c->ws_clock;
     w.chains = std::move(c->chains); w.lat = c->lat; w.eps = c->eps; w.x0_hist = c->x0_hist;
+    w.slot_stage = c->slot_stage; w.slot_stage_ok = c->slot_stage_ok; w.slots_dev = c->slots_dev;
+    c->slot_stage = Chain(); c->slot_stage_ok = false; c->slots_dev = nullptr;
     w.allocs = std::move(c->ws_allocs);
     w.dbg = c->dbg;
     w.graphs_valid = c->graphs_valid; w.graph_film = c->graph_film; w.graph_B = c->graph_B;
@@ -377,6 +399,7 @@ bool unpark_workspace(hd_ctx* c, int B) {
     if (it == c->ws_cache.end()) return false;
     SavedWs& w = it->second;
     c->chains = std::move(w.chains); c->lat = w.lat; c->eps = w.eps; c->x0_hist = w.x0_hist;
+    c->slot_stage = w.slot_stage; c->slot_stage_ok = w.slot_stage_ok; c->slots_dev = w.slots_dev;
     c->ws_allocs = std::move(w.allocs);
     for (auto& kv : w.dbg) if (kv.first != "film" && kv.first != "temb") c->dbg[kv.first] = kv.second;
     c->graphs_valid = w.graphs_valid; c->graph_film = w.graph_film; c->graph_B = w.graph_B;

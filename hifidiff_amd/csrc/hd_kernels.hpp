@@ -23,6 +23,10 @@ struct StepState {
     // NULL for hd_sample / hd_sample_multistep, whose launches never read these fields.
     const int* start_rows;
     int hist_first;
+    // per-face keys and resumption (hd_sample_faces*; NULL for every other entry): this chain's [B_chain] Philox keys -- face f's z at
+    // row k, element e of the face is Philox(face_seeds[f]; k, e) -- and [B_chain] first-order flags that replace hist_first per face.
+    const unsigned long long* face_seeds;
+    const int* face_first;
 };
 
 // ----------------------------------------------------------------------------------- weight packing
@@ -176,9 +180,14 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 // first-order (h := x0, see below).  PF = false is the code of hd_sample / hd_sample_multistep.
 // face f's start row (the pointer is read from device memory: a global pointer, as in sched_update)
 __device__ __forceinline__ int st_row(const StepState* st, int f) { return ((const __attribute__((address_space(1))) int*)st->start_rows)[f]; }
+// is face f's row k its first-order row: k == r_f and (per face, hd_sample_faces_multistep) face_first[f] or (hd_sample_rows*) hist_first
+__device__ __forceinline__ bool st_first(const StepState* st, int f, int k, int r) {
+    return k == r && (st->face_first ? ((const __attribute__((address_space(1))) int*)st->face_first)[f] != 0 : st->hist_first != 0);
+}
+// PF: f is the chain-local face and ef the element's index inside the face (the per-face Philox key's counter, hd_sample_faces*)
 template <bool PF = false>
 __device__ __forceinline__ float sched_update(float xv, float e, const float* c, const StepState* st, int step, size_t gi, int n_total,
-                                             size_t li, bool first = false) {
+                                             size_t li, bool first = false, int f = 0, unsigned ef = 0) {
     float x0 = (xv - c[0] * e) / c[1];
     x0 = fminf(fmaxf(x0, -c[2]), c[2]);
     float c3 = c[3];
@@ -188,7 +197,10 @@ __device__ __forceinline__ float sched_update(float xv, float e, const float* c,
     float r = c3 * x0 + c[4] * xv + c[5] * e;
     if (c[6] != 0.f) {
         // (the pointer is read from device memory: say that it is a global pointer, or the load is a flat load with a full wait)
-        const float z = st->noise ? ((const __attribute__((address_space(1))) float*)st->noise)[(size_t)step * n_total + gi] : philox_normal(st->seed, (unsigned)step, (unsigned)gi);
+        float z;
+        if (st->noise) z = ((const __attribute__((address_space(1))) float*)st->noise)[(size_t)step * n_total + gi];
+        else if (PF && st->face_seeds) z = philox_normal(((const __attribute__((address_space(1))) unsigned long long*)st->face_seeds)[f], (unsigned)step, ef);
+        else z = philox_normal(st->seed, (unsigned)step, (unsigned)gi);
         r += c[6] * z;
     }
     if (st->x0_hist) {
@@ -307,7 +319,7 @@ __global__ __launch_bounds__(256) void ending_conv_kernel(const float* __restric
             const int r = st_row(sa.st, bb), k = r + step;          // the wave's run lies in one face: k is wave-uniform
             if (k < sa.st->n_steps)
                 sa.lat[o] = sched_update<true>(sa.lat[o], e, sa.coef + (size_t)k * 7, sa.st, k, (size_t)sa.elem0 + o, sa.n_total, o,
-                                               k == r && sa.st->hist_first);
+                                               st_first(sa.st, bb, k, r), bb, (unsigned)(o - (size_t)bb * 4 * L * L));
         } else {
             sa.lat[o] = sched_update(sa.lat[o], e, sa.coef + (size_t)step * 7, sa.st, step, (size_t)sa.elem0 + o, sa.n_total, o);
         }
@@ -322,6 +334,25 @@ static __global__ void film_rows_gather_kernel(float* __restrict__ film_pf, cons
     const float4* src = reinterpret_cast<const float4*>(film_table + (size_t)row * film_total);
     float4* dst = reinterpret_cast<float4*>(film_pf + (size_t)f * film_total);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < film_total / 4; i += gridDim.x * blockDim.x) dst[i] = src[i];
+}
+
+// hd_prepare_slots: copy face j (< n) of the n-face conditioning (the staging chain's buffers: 5 priors NHWC, 5 w_c, 5 w_s, the idc term and
+// id_emb, face-contiguous with sz[b] floats per face) to slot slots[j] of the batch: chain slots[j] / faces_per_chain, face slots[j] % faces_per_chain
+// of that chain.  grid (x, n, kSlotBufs); the slots are checked on the host (distinct, in [0, B)).
+constexpr int kSlotBufs = 17, kSlotChains = 8;
+struct SlotScatterP {
+    const float* src[kSlotBufs];
+    float* dst[kSlotChains][kSlotBufs];
+    int sz[kSlotBufs];
+    const int* slots;
+    int faces_per_chain;
+};
+static __global__ __launch_bounds__(256) void slot_scatter_kernel(const SlotScatterP p) {
+    const int j = blockIdx.y, b = blockIdx.z, sz = p.sz[b];
+    const int slot = p.slots[j], ch = slot / p.faces_per_chain, f = slot - ch * p.faces_per_chain;
+    const float* __restrict__ src = p.src[b] + (size_t)j * sz;
+    float* __restrict__ dst = p.dst[ch][b] + (size_t)f * sz;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < sz; i += gridDim.x * blockDim.x) dst[i] = src[i];
 }
 
 // ----------------------------------------------------------------------- depthwise 3x3 + gate + pool

@@ -689,6 +689,7 @@ void hd_destroy(hd_ctx* c) {
         if (ch.stream) (void)hipStreamDestroy(ch.stream);
         if (ch.done) (void)hipEventDestroy(ch.done);
     }
+    if (c->slot_stage_ok) destroy_chain_queue(c->slot_stage);
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
     if (c->film_ev) (void)hipEventDestroy(c->film_ev);
     for (auto& sg : c->stage) { if (sg.ev) (void)hipEventDestroy(sg.ev); if (sg.host) (void)hipHostFree(sg.host); }
@@ -937,6 +938,7 @@ int hd_prepare_unconditional(hd_ctx* c, int batch, void* stream) {
     if (rc) return rc;
     c->prepared = true;
     c->hist_valid = false;                               // a new batch: no multistep history to resume
+    c->hist_face.clear();
     return HD_OK;
 }
 
@@ -963,6 +965,7 @@ int hd_prepare(hd_ctx* c, int batch, const float* cr_latent, const float* cr_fac
     if (rc) return rc;
     c->prepared = true;
     c->hist_valid = false;                               // a new batch: no multistep history to resume
+    c->hist_face.clear();
     return HD_OK;
 }
 
@@ -993,6 +996,7 @@ int hd_prepare_from_priors(hd_ctx* c, int batch, const float* const priors[5], c
     if (rc) return rc;
     c->prepared = true;
     c->hist_valid = false;                               // a new batch: no multistep history to resume
+    c->hist_face.clear();
     return HD_OK;
 }
 
@@ -1097,8 +1101,11 @@ int hd_eps(hd_ctx* c, const float* x, const float* timesteps, int n_t, float* ep
 // x0_hist is NULL, so its launches and their memory traffic are those of a single-step-only build.
 // hd_sample_rows* (rows != NULL: host [B] start rows, already checked): n_iters iterations of the per-face graphs (Chain::graph_rows_*),
 // every chain's StepState carries its start rows; hist_first = !resume.  rows == NULL: n_iters == n, the graphs of hd_sample.
+// hd_sample_faces* (faces = true): the same per-face graphs, and StepState also carries the faces' Philox keys (face_seeds, host [B] or NULL)
+// and first-order flags (first, host [B] or NULL: hist_first).
 static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps, const float* coef, int ncoef, const float* noise,
-                       uint64_t seed, void* stream, const int32_t* rows = nullptr, int n_iters = 0, int resume = 0) {
+                       uint64_t seed, void* stream, const int32_t* rows = nullptr, int n_iters = 0, int resume = 0,
+                       const uint64_t* face_seeds = nullptr, const int32_t* first = nullptr) {
     HIPCHECK(c, hipSetDevice(c->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool ms = ncoef == 8, pf = rows != nullptr;
@@ -1122,6 +1129,14 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
         c->film_pf_cap = (size_t)c->B * c->film_total;
         ++c->rows_gen;
     }
+    if ((face_seeds || first) && c->B > c->faces_cap) {   // read through StepState: no graph holds these pointers
+        dev_free(c, c->seeds_dev); dev_free(c, c->first_dev);
+        c->seeds_dev = nullptr; c->first_dev = nullptr; c->faces_cap = 0;
+        rc = dev_alloc(c, &c->seeds_dev, (size_t)c->B);
+        if (!rc) rc = dev_alloc(c, &c->first_dev, (size_t)c->B);
+        if (rc) return rc;
+        c->faces_cap = c->B;
+    }
     if (pf && c->B > c->rows_cap) {                       // read through StepState: no graph holds this pointer
         dev_free(c, c->rows_dev);
         rc = dev_alloc(c, &c->rows_dev, (size_t)c->B);
@@ -1139,14 +1154,16 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
     // schedule and loop state (step = -1: each chain's intro kernel pre-increments) go through a pinned staging buffer of
     // the context, so the caller's host arrays are free on return and nothing here waits for the stream.
     // Layout: coef [n][7] | timesteps [n] | StepState (single-step), or coef | timesteps | c7 [n] | one StepState per chain
-    // (multistep or per-face rows) | start rows [B] (per-face rows).
+    // (multistep or per-face rows) | start rows [B] (per-face rows) | Philox keys [B] (2 words each) | first-order flags [B] (per-face keys /
+    // flags).
     StepState st{};
     st.step = -1; st.n_steps = n; st.noise = noise; st.seed = seed;
     {
         auto& sg = c->stage[c->stage_idx ^= 1];
         const size_t st_f = (sizeof(StepState) + 3) / 4, st0 = (size_t)n * (ms ? 9 : 8);
         const size_t nst = (ms || pf) ? c->chains.size() : 1, rows0 = st0 + st_f * nst;
-        const size_t need = rows0 + (pf ? (size_t)c->B : 0);
+        const size_t seeds0 = rows0 + (pf ? (size_t)c->B : 0), first0 = seeds0 + (face_seeds ? 2 * (size_t)c->B : 0);
+        const size_t need = first0 + (first ? (size_t)c->B : 0);
         if (sg.pending) { HIPCHECK(c, hipEventSynchronize(sg.ev)); sg.pending = false; }     // the copy issued two calls ago
         if (sg.cap < need) {
             if (sg.host) (void)hipHostFree(sg.host);
@@ -1169,11 +1186,21 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
         for (size_t k = 0; k < nst; ++k) {
             if (ms) st.x0_hist = c->chains[k].x0_hist;
             if (pf) st.start_rows = c->rows_dev + c->chains[k].face0;
+            if (face_seeds) st.face_seeds = c->seeds_dev + c->chains[k].face0;
+            if (first) st.face_first = c->first_dev + c->chains[k].face0;
             memcpy(sg.host + st0 + k * st_f, &st, sizeof(st));
         }
         if (pf) {
             memcpy(sg.host + rows0, rows, (size_t)c->B * sizeof(int32_t));
             HIPCHECK(c, hipMemcpyAsync(c->rows_dev, sg.host + rows0, (size_t)c->B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        }
+        if (face_seeds) {
+            memcpy(sg.host + seeds0, face_seeds, (size_t)c->B * sizeof(uint64_t));
+            HIPCHECK(c, hipMemcpyAsync(c->seeds_dev, sg.host + seeds0, (size_t)c->B * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+        }
+        if (first) {
+            memcpy(sg.host + first0, first, (size_t)c->B * sizeof(int32_t));
+            HIPCHECK(c, hipMemcpyAsync(c->first_dev, sg.host + first0, (size_t)c->B * sizeof(int32_t), hipMemcpyHostToDevice, s));
         }
         memcpy(sg.host + (size_t)n * 7, timesteps, (size_t)n * sizeof(float));
         HIPCHECK(c, hipMemcpyAsync(c->coef_dev, sg.host, (size_t)n * 7 * sizeof(float), hipMemcpyHostToDevice, s));
@@ -1234,6 +1261,7 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
                     if (e == hipSuccess) e = e2;
                 }
                 if (e == hipSuccess) e = hipGraphInstantiate(multi ? &gm : &g1, graph, nullptr, nullptr, 0);
+                if (e == hipSuccess) ++c->graph_captures;
                 if (graph) (void)hipGraphDestroy(graph);
                 if (e != hipSuccess) { c->film_pf_mode = false; c->film_face_stride = 0; HD_FAIL(c, HD_ERR_HIP, "graph capture/instantiate failed: %s", hipGetErrorString(e)); }
                 if (multi == 0 && &ch == &c->chains[0]) {      // the one-step program of chain 0: what hd_get_option reports
@@ -1261,7 +1289,16 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
         HIPCHECK(c, hipStreamWaitEvent(s, ch.done, 0));
     }
     if (c->profiling) { HIPCHECK(c, hipEventRecord(c->ev1, s)); c->last_steps = n_iters; }
-    c->hist_valid = ms; c->hist_B = c->B;                // what a later hd_sample_rows_multistep(resume = 1) may continue
+    // what a later hd_sample_rows_multistep(resume = 1) may continue, and per face what hd_sample_faces_multistep(resume[f] = 1) may:
+    // a whole-batch call leaves every face's history (multistep) or none; a multistep rows / faces call that of every face that ran a row
+    if (c->hist_B != c->B || c->hist_face.size() != (size_t)c->B) c->hist_face.assign((size_t)c->B, 0);
+    if (ms && pf) {
+        for (int f = 0; f < c->B; ++f) if (rows[f] < n) c->hist_face[f] = 1;
+    } else {
+        c->hist_face.assign((size_t)c->B, ms ? 1 : 0);
+    }
+    c->hist_valid = ms; c->hist_B = c->B;
+    if (ms && first) for (char h : c->hist_face) c->hist_valid = c->hist_valid && h;   // hd_sample_faces_multistep: only when every face has one
     rc = poison_on_abort(c, c->lat, nlat, s);
     if (rc) return rc;
     HIPCHECK(c, hipMemcpyAsync(x_inout, c->lat, nlat * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1327,6 +1364,133 @@ int hd_sample_rows_multistep(hd_ctx* c, float* x_inout, const hd_schedule_ms* sc
         HD_FAIL(c, HD_ERR_INVALID, "hd_sample_rows_multistep: resume = 1 but no multistep history of this batch (no earlier multistep call, "
                                    "hd_prepare since, another batch size or a single-step call in between)");
     return sample_impl(c, x_inout, sched->n_steps, sched->timesteps, sched->coef, 8, noise, seed, stream, start_rows, n_iters, resume);
+}
+
+int hd_sample_faces(hd_ctx* c, float* x_inout, const hd_schedule* sched, const int32_t* start_rows, int n_iters, const uint64_t* face_seeds,
+                    const float* noise, uint64_t seed, void* stream) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    rc = check_xcd(c);
+    if (rc) return rc;
+    if (!x_inout || !sched || sched->n_steps <= 0 || !sched->timesteps || !sched->coef || !start_rows)
+        HD_FAIL(c, HD_ERR_INVALID, "hd_sample_faces: bad arguments");
+    rc = check_rows(c, "hd_sample_faces", sched->n_steps, start_rows, n_iters);
+    if (rc) return rc;
+    return sample_impl(c, x_inout, sched->n_steps, sched->timesteps, sched->coef, 7, noise, seed, stream, start_rows, n_iters, 0, face_seeds);
+}
+
+int hd_sample_faces_multistep(hd_ctx* c, float* x_inout, const hd_schedule_ms* sched, const int32_t* start_rows, int n_iters,
+                              const int32_t* resume, const uint64_t* face_seeds, const float* noise, uint64_t seed, void* stream) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    rc = check_xcd(c);
+    if (rc) return rc;
+    if (!x_inout || !sched || sched->n_steps <= 0 || !sched->timesteps || !sched->coef || !start_rows || !resume)
+        HD_FAIL(c, HD_ERR_INVALID, "hd_sample_faces_multistep: bad arguments");
+    rc = check_rows(c, "hd_sample_faces_multistep", sched->n_steps, start_rows, n_iters);
+    if (rc) return rc;
+    const bool have = c->hist_B == c->B && c->hist_face.size() == (size_t)c->B;
+    std::vector<int32_t> first((size_t)c->B);
+    for (int f = 0; f < c->B; ++f) {
+        if (resume[f] != 0 && resume[f] != 1) HD_FAIL(c, HD_ERR_INVALID, "hd_sample_faces_multistep: resume[%d] = %d is not 0 or 1", f, resume[f]);
+        if (resume[f] && !(have && c->hist_face[f]))
+            HD_FAIL(c, HD_ERR_INVALID, "hd_sample_faces_multistep: resume[%d] = 1 but face %d has no multistep history (no multistep row since "
+                                       "hd_prepare*, hd_prepare_slots refilled it, or a single-step call in between)", f, f);
+        first[f] = resume[f] ? 0 : 1;
+    }
+    return sample_impl(c, x_inout, sched->n_steps, sched->timesteps, sched->coef, 8, noise, seed, stream, start_rows, n_iters, 0, face_seeds,
+                       first.data());
+}
+
+// Replace the conditioning of n slots.  The prologue (FPG, ResNet-50 or the given embedding, HCA gates, idc_conv) runs at batch n on the
+// workspace's private staging chain -- the same launches hd_prepare issues for a batch of n, so the n faces' conditioning is bit for bit
+// that of hd_prepare(n) -- and slot_scatter_kernel copies it into the slots.  Nothing of the batch's chains is rebuilt, parked or
+// recaptured; only the refilled slots' buffers are written.
+int hd_prepare_slots(hd_ctx* c, int n, const int32_t* slots, const float* cr_latent, const float* cr_face, const float* id_emb, void* stream) {
+    if (!c) return HD_ERR_INVALID;
+    if (c->cr || c->vae || !c->conditional)
+        HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: this context holds the unconditional Denoiser, CoarseRestoration or the VAE (no conditioning)");
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    if (n < 1 || n > c->B) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: n = %d outside [1, %d]", n, c->B);
+    if (!slots || !cr_latent || (!cr_face == !id_emb))
+        HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: need slots, cr_latent and exactly one of cr_face / id_emb");
+    {
+        std::vector<char> seen((size_t)c->B, 0);
+        for (int j = 0; j < n; ++j) {
+            if (slots[j] < 0 || slots[j] >= c->B) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: slots[%d] = %d outside [0, %d)", j, slots[j], c->B);
+            if (seen[slots[j]]) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: slot %d given twice", slots[j]);
+            seen[slots[j]] = 1;
+        }
+    }
+    if (c->chains.size() > (size_t)kSlotChains) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: more than %d chains", kSlotChains);
+    HIPCHECK(c, hipSetDevice(c->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    Chain& sc = c->slot_stage;
+    if (!c->slot_stage_ok) {                               // first refill of this workspace: its buffers join the workspace's allocations
+        sc = Chain();
+        sc.index = -1; sc.B = c->B; sc.face0 = 0;          // index -1: no introspection names (those stay on chain 0)
+        c->ws_scope = true;
+        rc = alloc_chain(c, sc);
+        if (!rc) rc = dev_alloc(c, &c->slots_dev, (size_t)c->B);
+        c->ws_scope = false;
+        if (rc) { destroy_chain_queue(sc); return rc; }
+        c->slot_stage_ok = true;
+    }
+    // the staging chain at batch n: the level geometry of a batch of n faces (its buffers hold B)
+    sc.B = n;
+    for (int l = 0; l < 5; ++l) sc.lv[l].M = n * sc.lv[l].H * sc.lv[l].H;
+    Chain* prev = c->ch;
+    c->ch = &sc;
+    std::vector<Op> prog;
+    add_fpg(c, prog, cr_latent);
+    if (cr_face) add_resnet(c, prog, cr_face);
+    for (int i = 0; i < 5; ++i) add_gates(c, prog, i);
+    add_idc_term(c, prog);
+    c->ch = prev;
+    if (!cr_face) HIPCHECK(c, hipMemcpyAsync(sc.id_emb, id_emb, (size_t)n * 2048 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    rc = run_ops(c, prog, s);
+    if (rc) return rc;
+    // slots: through the pinned staging buffer (the caller's array is free on return; nothing waits for the stream)
+    {
+        auto& sg = c->stage[c->stage_idx ^= 1];
+        if (sg.pending) { HIPCHECK(c, hipEventSynchronize(sg.ev)); sg.pending = false; }
+        if (sg.cap < (size_t)n) {
+            if (sg.host) (void)hipHostFree(sg.host);
+            sg.host = nullptr; sg.cap = 0;
+            HIPCHECK(c, hipHostMalloc(reinterpret_cast<void**>(&sg.host), (size_t)n * sizeof(float), hipHostMallocDefault));
+            sg.cap = n;
+        }
+        if (!sg.ev) HIPCHECK(c, hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
+        memcpy(sg.host, slots, (size_t)n * sizeof(int32_t));
+        HIPCHECK(c, hipMemcpyAsync(c->slots_dev, sg.host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIPCHECK(c, hipEventRecord(sg.ev, s));
+        sg.pending = true;
+    }
+    SlotScatterP p{};
+    int b = 0;
+    for (int i = 0; i < 5; ++i) {
+        const Level& lv = sc.lv[4 - i];
+        const int sz[3] = {lv.H * lv.H * lv.C, lv.C, lv.H * lv.H};      // prior i (NHWC), w_c, w_s per face
+        float* const srcs[3] = {sc.prior[i], sc.gate_c[i], sc.gate_s[i]};
+        for (int q = 0; q < 3; ++q, ++b) {
+            p.src[b] = srcs[q]; p.sz[b] = sz[q];
+            for (size_t k = 0; k < c->chains.size(); ++k) p.dst[k][b] = q == 0 ? c->chains[k].prior[i] : q == 1 ? c->chains[k].gate_c[i] : c->chains[k].gate_s[i];
+        }
+    }
+    p.src[b] = sc.idc_term; p.sz[b] = 2048 * c->S * c->S;
+    for (size_t k = 0; k < c->chains.size(); ++k) p.dst[k][b] = c->chains[k].idc_term;
+    ++b;
+    p.src[b] = sc.id_emb; p.sz[b] = 2048;
+    for (size_t k = 0; k < c->chains.size(); ++k) p.dst[k][b] = c->chains[k].id_emb;
+    p.slots = c->slots_dev; p.faces_per_chain = c->chains[0].B;
+    hipLaunchKernelGGL(slot_scatter_kernel, dim3(32, n, kSlotBufs), dim3(256), 0, s, p);
+    HIPCHECK(c, hipGetLastError());
+    // the refilled faces have no multistep history; hd_sample_rows_multistep(resume = 1) no longer continues the whole batch
+    if (c->hist_B == c->B && c->hist_face.size() == (size_t)c->B)
+        for (int j = 0; j < n; ++j) c->hist_face[slots[j]] = 0;
+    c->hist_valid = false;
+    return HD_OK;
 }
 
 static std::vector<Op>* which_program(hd_ctx* c, int which) {
@@ -1428,6 +1592,7 @@ int hd_get_option(hd_ctx* c, const char* key) {
     if (k == "sample_stage_launches") return c->sample_stages;
     if (k == "sample_face_stage_launches") return c->sample_face_stages;
     if (k == "rows_stage_launches") return c->rows_stages;
+    if (k == "graph_captures") return c->graph_captures;         // step graphs instantiated by this context (hd_prepare_slots adds none)
     // the folds of the program built for the batch in use (0 before the first call): the decisions build_denoiser_program made, and
     // whether the launch that carries them still runs -- the face-stage entries need the face stages on and a single chain
     const Chain* ch = c->chains.empty() ? nullptr : &c->chains[0];

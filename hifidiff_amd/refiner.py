@@ -59,6 +59,23 @@ def _version(t):
         return None
 
 
+def slots_arg(slots, batch):
+    """slots (int list / int tensor) -> int32 CPU tensor of n distinct slots in [0, batch); ValueError otherwise."""
+    if batch is None:
+        raise RuntimeError("no batch is prepared: call prepare(cr_face, cr_latent) for the whole batch first")
+    t = torch.as_tensor(slots)
+    if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise ValueError("slots must be integers")
+    t = t.flatten().to(device="cpu", dtype=torch.int64)
+    if t.numel() < 1 or t.numel() > batch:
+        raise ValueError(f"between 1 and {batch} slots must be given, got {t.numel()}")
+    if bool(((t < 0) | (t >= batch)).any()):
+        raise ValueError(f"slots must lie in [0, {batch})")
+    if t.unique().numel() != t.numel():
+        raise ValueError("slots must be distinct")
+    return t.to(torch.int32).contiguous()
+
+
 class _Engine:
     """Owns the hd_ctx of one (latent_res, device)."""
 
@@ -173,6 +190,28 @@ class _Engine:
             _lib.check(_lib.lib().hd_prepare(self.ctx, B, crl.data_ptr(), crf.data_ptr() if crf is not None else None,
                                              emb.data_ptr() if emb is not None else None, _stream(self.device)), self.ctx)
         self.batch, self.cond_key, self.prior_key = B, None, None
+
+    def prepare_slots(self, slots, cr_latent, cr_face=None, id_emb=None):
+        """hd_prepare_slots: replace the conditioning of the prepared batch's faces in `slots` (n distinct ints in [0, B))."""
+        self.require_loaded()
+        sl = slots_arg(slots, self.batch)
+        n, L = sl.numel(), self.latent_res
+        if tuple(cr_latent.shape) != (n, 4, L, L):
+            raise RuntimeError("cr_latent must be (%d,4,%d,%d), got %s" % (n, L, L, tuple(cr_latent.shape)))
+        if (cr_face is None) == (id_emb is None):
+            raise RuntimeError("need exactly one of cr_face / id_emb")
+        if cr_face is not None and tuple(cr_face.shape) != (n, 3, 128, 128):
+            raise RuntimeError("cr_face must be (%d,3,128,128), got %s" % (n, tuple(cr_face.shape)))
+        crl = _f32c(cr_latent, self.device)
+        crf = _f32c(cr_face, self.device) if cr_face is not None else None
+        emb = _f32c(id_emb.reshape(n, -1), self.device) if id_emb is not None else None
+        if emb is not None and emb.shape[1] != 2048:
+            raise RuntimeError("identity embedding must have 2048 features")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().hd_prepare_slots(self.ctx, n, ctypes.cast(sl.data_ptr(), ctypes.POINTER(ctypes.c_int32)), crl.data_ptr(),
+                                                   crf.data_ptr() if crf is not None else None, emb.data_ptr() if emb is not None else None,
+                                                   _stream(self.device)), self.ctx)
+        self.cond_key, self.prior_key = None, None         # the batch no longer matches any one pair of tensors
 
     def prepare_unconditional(self, batch):
         self.require_loaded()
@@ -436,6 +475,18 @@ class FacialRefiner(nn.Module):
         e.prepare(cr_latent, cr_face=cr_face)
         # strong references: identity + version, never addresses (a freed tensor's address is handed to the next batch)
         e.cond_key = (cr_face, vf, cr_latent, vl) if (self.cache_conditioning and vf is not None and vl is not None) else None
+
+    def prepare_slots(self, slots, cr_face, cr_latent):
+        """Continuous batching: replace the conditioning of the prepared batch's faces in `slots` (n distinct ints in [0, B)) with that of
+        cr_face [n,3,128,128] / cr_latent [n,4,L,L]; the other faces keep theirs bit for bit and nothing is recaptured.  The refilled faces
+        have no multistep history (sample(..., resume=<[B] bool tensor>) with False there).  Continue with sample(..., prepare=False): the
+        batch no longer matches any one pair of tensors, so the conditioning cache is cleared."""
+        e = self._engine
+        e.ensure(cr_latent.device)
+        e.cond_key = None
+        if not e.conditional:
+            raise RuntimeError("prepare_slots needs the conditional refiner")
+        e.prepare_slots(slots, cr_latent, cr_face=cr_face)
 
     def invalidate_conditioning(self):
         """Forget the cached conditioning (after writing into cr_face / cr_latent through `.data`, numpy or a DLPack alias,

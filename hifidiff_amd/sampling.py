@@ -72,7 +72,7 @@ def img2img_start(scheduler, cr_latent, strength, noise=None, generator=None):
 
 @torch.no_grad()
 def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, prepare=True, check=True,
-           start_steps=None, n_iters=None, resume=False):
+           start_steps=None, n_iters=None, resume=False, face_seeds=None):
     """Whole loop on the GPU: returns the final latents (a new tensor).
 
     The scheduler's coefficient table picks the entry point: 7 columns (DDIM / DDPM) -> hd_sample, 8 columns
@@ -85,11 +85,19 @@ def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, pr
     torch.inference_mode, where tensors carry no version and the cache never hits.  With resume=False a multistep face's first
     row is taken first-order (diffusers' img2img start).
     noise: optional [n_steps, B, 4, L, L] tensor of z (DDPM, SDE-DPM-Solver++); None -> device Philox(seed).
+    face_seeds: None, or one Philox key per face (int list / int64 tensor [B]): face f's z at row k, element e of the face is
+    Philox(face_seeds[f]; k, e), independent of its slot and its neighbours (diffusers' `generator=[...]`).  resume may also be a
+    [B] bool tensor (multistep): True continues that face's history, False takes its first row first-order (a slot refilled by
+    FacialRefiner.prepare_slots).  Either one dispatches to hd_sample_faces / hd_sample_faces_multistep (start_steps default 0).
     For the unconditional `Denoiser` pass cr_face = cr_latent = None.
     check=True (the default): ONE stream synchronisation after the whole loop (not per step), then RuntimeError if a persistent
     stage launch gave up during it -- where the reference's loop would have raised (test_refiner.py:89-91), so that the last batch
     of a val_loop cannot end with rc 0 and NaN images.  check=False only enqueues the work (the returned latents are NaN in the
     failing case either way; `model.check()` reports it later).  bench.py times the loop with its own synchronisation."""
+    if face_seeds is not None:                             # argument errors before any device work
+        face_seeds = face_seeds_arg(face_seeds, latents.shape[0])
+    if isinstance(resume, torch.Tensor):
+        resume = resume_arg(resume, latents.shape[0])
     e = model.engine
     e.ensure(latents.device)
     if latents.shape[0] == 0:                              # empty batch: nothing to sample
@@ -117,6 +125,10 @@ def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, pr
             raise RuntimeError("noise must be [n_steps, B, 4, L, L]")
         nptr = noise.data_ptr()
     stream = torch.cuda.current_stream(e.device).cuda_stream
+    B = x.shape[0]
+    per_face_resume = isinstance(resume, torch.Tensor)
+    if face_seeds is not None or per_face_resume:
+        return _sample_faces(e, x, sch, ts, multistep, nptr, seed, stream, start_steps, n_iters, resume, face_seeds, check)
     if start_steps is None:
         if n_iters is not None or resume:
             raise ValueError("n_iters / resume need start_steps")
@@ -124,7 +136,6 @@ def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, pr
             run = _lib.lib().hd_sample_multistep if multistep else _lib.lib().hd_sample
             _lib.check(run(e.ctx, x.data_ptr(), ctypes.byref(sch), nptr, int(seed), stream), e.ctx)
     else:
-        B = x.shape[0]
         rows = torch.as_tensor(start_steps).to(device="cpu", dtype=torch.int32).flatten()
         if rows.numel() == 1:
             rows = rows.expand(B)
@@ -148,3 +159,254 @@ def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, pr
     if check:
         e.check()
     return x
+
+
+def _rows_arg(start_steps, B):
+    """start rows as an int32 [B] CPU tensor (None: 0 for every face)."""
+    rows = torch.as_tensor(0 if start_steps is None else start_steps).to(device="cpu", dtype=torch.int32).flatten()
+    if rows.numel() == 1:
+        rows = rows.expand(B)
+    rows = rows.contiguous()
+    if rows.numel() != B:
+        raise ValueError(f"start_steps must be an int or a [{B}] tensor")
+    return rows
+
+
+def face_seeds_arg(face_seeds, B):
+    """face_seeds (int list / tuple / int tensor of B values in [-2**63, 2**64); negative int64 keys keep their bit pattern) -> uint64 [B]
+    numpy array for hd_sample_faces*."""
+    import numpy as np
+    if isinstance(face_seeds, torch.Tensor):
+        if face_seeds.dtype.is_floating_point or face_seeds.dtype == torch.bool:
+            raise ValueError("face_seeds must hold integers")
+        vals = [int(v) for v in face_seeds.flatten().cpu().tolist()]
+    else:
+        vals = [int(v) for v in face_seeds]
+    if len(vals) != B:
+        raise ValueError(f"face_seeds must hold {B} seeds (one per face), got {len(vals)}")
+    if any(v < -(1 << 63) or v >= (1 << 64) for v in vals):
+        raise ValueError("face_seeds must lie in [-2**63, 2**64)")
+    return np.array([v & 0xFFFFFFFFFFFFFFFF for v in vals], dtype=np.uint64)   # int64 seeds keep their bit pattern
+
+
+def resume_arg(resume, B):
+    """resume (bool / [B] bool or 0/1 tensor) -> int32 [B] CPU tensor of 0/1 for hd_sample_faces_multistep."""
+    r = torch.as_tensor(resume).flatten().cpu()
+    if r.dtype.is_floating_point:
+        raise ValueError("resume must be a bool or a [B] bool tensor")
+    if r.numel() == 1:
+        r = r.expand(B)
+    if r.numel() != B:
+        raise ValueError(f"resume must be a bool or a [{B}] tensor")
+    if bool(((r != 0) & (r != 1)).any()):
+        raise ValueError("resume holds 0 / 1 (False / True) per face")
+    return r.to(torch.int32).contiguous()
+
+
+def _sample_faces(e, x, sch, ts, multistep, nptr, seed, stream, start_steps, n_iters, resume, face_seeds, check):
+    """hd_sample_faces / hd_sample_faces_multistep: per-face start rows, Philox keys and (multistep) resumption."""
+    B = x.shape[0]
+    rows = _rows_arg(start_steps, B)
+    if (isinstance(resume, torch.Tensor) or resume) and not multistep:
+        raise ValueError("resume applies to multistep schedules only")
+    seeds = face_seeds                                     # already a uint64 array (sample) or None
+    if n_iters is None:
+        n_iters = ts.numel() - int(rows.min())
+        if n_iters == 0:
+            return x
+    rptr = ctypes.cast(rows.data_ptr(), ctypes.POINTER(ctypes.c_int32))
+    sptr = seeds.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if seeds is not None else None
+    with torch.cuda.device(e.device):
+        if multistep:
+            res = resume_arg(resume, B)
+            rc = _lib.lib().hd_sample_faces_multistep(e.ctx, x.data_ptr(), ctypes.byref(sch), rptr, int(n_iters),
+                                                      ctypes.cast(res.data_ptr(), ctypes.POINTER(ctypes.c_int32)), sptr, nptr, int(seed), stream)
+        else:
+            rc = _lib.lib().hd_sample_faces(e.ctx, x.data_ptr(), ctypes.byref(sch), rptr, int(n_iters), sptr, nptr, int(seed), stream)
+        _lib.check(rc, e.ctx)
+    if check:
+        e.check()
+    return x
+
+
+class SlotTable:
+    """Slot bookkeeping of continuous batching (host only, no device): which request holds which slot of a batch of B, the schedule
+    row each slot is at, and whether its multistep history is its own.
+
+    A request placed in a slot starts at its own row (img2img_start's convention) and is "fresh": its first row is taken first-order
+    (resume 0).  After a call of n_iters iterations every occupied slot advances by n_iters rows; a slot that ran at least one row has a
+    history of its own from then on (resume 1), and a slot whose row reached n_steps is complete and free again.  An empty slot is held
+    (start row n_steps) and is never resumed."""
+
+    def __init__(self, batch, n_steps):
+        if batch < 1 or n_steps < 1:
+            raise ValueError("batch and n_steps must be >= 1")
+        self.batch, self.n_steps = int(batch), int(n_steps)
+        self.req = [None] * self.batch          # request id per slot (None: empty)
+        self.row = [self.n_steps] * self.batch  # schedule row of the slot's next iteration
+        self.fresh = [False] * self.batch       # True until the slot's request has run a row (first-order first row)
+
+    def free_slots(self):
+        return [i for i, r in enumerate(self.req) if r is None]
+
+    def occupied(self):
+        return [i for i, r in enumerate(self.req) if r is not None]
+
+    def assign(self, req_id, start_row):
+        """Place a request in the lowest free slot at row start_row (0 <= start_row <= n_steps); returns the slot."""
+        if not 0 <= int(start_row) <= self.n_steps:
+            raise ValueError(f"start row {start_row} outside [0, {self.n_steps}]")
+        free = self.free_slots()
+        if not free:
+            raise RuntimeError("no free slot")
+        i = free[0]
+        self.req[i], self.row[i], self.fresh[i] = req_id, int(start_row), True
+        return i
+
+    def start_rows(self):
+        """Start rows of the next call: the slot's row, n_steps (held) for an empty slot."""
+        return [self.row[i] if self.req[i] is not None else self.n_steps for i in range(self.batch)]
+
+    def resume_flags(self):
+        """Multistep resumption of the next call: 1 for a slot whose request has already run a row, else 0."""
+        return [int(self.req[i] is not None and not self.fresh[i]) for i in range(self.batch)]
+
+    def iters(self, limit):
+        """Iterations of the next call: `limit`, or fewer when no occupied slot has that many rows left (0: nothing runs).  A slot that
+        reaches its last row inside the call is held for the rest of it: refills come every `limit` iterations, not at every finish."""
+        left = [self.n_steps - self.row[i] for i in self.occupied() if self.row[i] < self.n_steps]
+        return min(int(limit), max(left)) if left else 0
+
+    def advance(self, n_iters):
+        """Account for a call of n_iters iterations; returns [(slot, request id)] of the requests it completed (their slots are free)."""
+        done = []
+        for i in self.occupied():
+            if self.row[i] < self.n_steps and n_iters > 0:
+                self.fresh[i] = False
+            self.row[i] = min(self.row[i] + int(n_iters), self.n_steps)
+            if self.row[i] >= self.n_steps:
+                done.append((i, self.req[i]))
+                self.req[i], self.fresh[i] = None, False
+        return done
+
+
+class ContinuousSampler:
+    """Continuous batching: a serving loop that keeps the B slots of one prepared batch busy.  A request that reaches the last row
+    leaves its slot, and the next queued request takes it (FacialRefiner.prepare_slots replaces that slot's conditioning alone, nothing
+    is recaptured); the other faces go on.  Every request's result depends on its own inputs and seed only, not on its slot or
+    neighbours: its initial latents come from a CPU torch.Generator seeded with `seed`, its z (DDPM, SDE-DPM-Solver++) from device
+    Philox keyed by the same seed per face (hd_sample_faces*).
+
+        cs = ContinuousSampler(model, scheduler, batch=64, refill_every=5)    # scheduler.set_timesteps(n) first
+        rid = cs.submit(cr_face, cr_latent, seed=7, strength=0.6)             # [3,128,128], [4,L,L]
+        results = cs.drain()                                                  # {rid: [4,L,L] latents}
+
+    step() runs one call of refill_every iterations (fewer when no slot has that many rows left) after refilling free slots from the
+    queue; a face that reaches its last row inside the call is held (not evaluated further) until the next refill;
+    poll() returns what has finished since the last poll.  The model is the sampler's own while it runs: any other prepare / forward
+    on it replaces the batch.  For the unconditional Denoiser pass cr_face = cr_latent = None (pure-noise start, strength 1)."""
+
+    def __init__(self, model, scheduler, batch=64, refill_every=5):
+        if batch < 1 or refill_every < 1:
+            raise ValueError("batch and refill_every must be >= 1")
+        self.model, self.scheduler = model, scheduler
+        self.batch, self.refill_every = int(batch), int(refill_every)
+        self.conditional = model.engine.conditional
+        self.L = model.engine.latent_res
+        self.n_steps = int(scheduler.timesteps.numel())
+        self.table = SlotTable(self.batch, self.n_steps)
+        self.queue = []                 # (rid, cr_face, cr_latent, seed, strength) in submission order
+        self.finished = {}
+        self.seeds = [0] * self.batch
+        self.x = None                   # [B,4,L,L] device latents of every slot
+        self.prepared = False
+        self.next_id = 0
+        self.calls = 0
+        self.refilled = 0
+
+    def submit(self, cr_face, cr_latent, seed, strength=1.0):
+        L = self.L
+        if self.conditional:
+            if cr_face is None or cr_latent is None:
+                raise ValueError("the refiner needs cr_face and cr_latent")
+            if tuple(cr_latent.shape) != (4, L, L) or tuple(cr_face.shape) != (3, 128, 128):
+                raise ValueError(f"expected cr_face (3,128,128) and cr_latent (4,{L},{L}), got {tuple(cr_face.shape)} and {tuple(cr_latent.shape)}")
+        elif cr_face is not None or cr_latent is not None or float(strength) != 1.0:
+            raise ValueError("the unconditional Denoiser takes no cr_face / cr_latent and starts from noise (strength 1)")
+        if not 0.0 <= float(strength) <= 1.0:
+            raise ValueError("strength must lie in [0, 1]")
+        seed = int(seed)
+        if not 0 <= seed < (1 << 63):
+            raise ValueError("seed must lie in [0, 2**63)")
+        rid = self.next_id
+        self.next_id += 1
+        self.queue.append((rid, cr_face, cr_latent, seed, float(strength)))
+        return rid
+
+    def _start(self, cr_latent, seed, strength):
+        """(initial latents [4,L,L] on the CPU, start row) of one request: img2img_start with a CPU generator seeded by the request."""
+        g = torch.Generator().manual_seed(seed)
+        z = torch.randn((1, 4, self.L, self.L), generator=g)
+        if cr_latent is None:
+            return z[0], 0
+        lat, start = img2img_start(self.scheduler, cr_latent.detach().float().cpu()[None], strength, noise=z)
+        return lat[0], int(start[0])
+
+    def _refill(self, dev):
+        new = []
+        while self.queue and self.table.free_slots():
+            rid, crf, crl, seed, strength = self.queue.pop(0)
+            lat, start = self._start(crl, seed, strength)
+            slot = self.table.assign(rid, start)
+            self.seeds[slot] = seed
+            self.x[slot] = lat.to(dev)
+            new.append((slot, crf, crl))
+        if not new or not self.conditional:
+            return
+        slots = [s for s, _, _ in new]
+        crf = torch.stack([f.to(dev, torch.float32) for _, f, _ in new])
+        crl = torch.stack([l.to(dev, torch.float32) for _, _, l in new])
+        if not self.prepared:           # the first batch: the whole batch is prepared once (empty slots get zeros; they are held)
+            B, L = self.batch, self.L
+            full_f = torch.zeros((B, 3, 128, 128), device=dev)
+            full_l = torch.zeros((B, 4, L, L), device=dev)
+            full_f[slots], full_l[slots] = crf, crl
+            self.model.prepare(full_f, full_l)
+            self.model.engine.cond_key = None          # the batch belongs to the sampler: no cache hit on these tensors later
+            self.prepared = True
+        else:
+            self.model.prepare_slots(slots, crf, crl)
+            self.refilled += len(slots)
+
+    def step(self):
+        """Refill free slots from the queue, then run one call of up to refill_every iterations.  Returns the number of iterations."""
+        e = self.model.engine
+        dev = torch.device("cuda", torch.cuda.current_device()) if e.device is None else e.device
+        if self.x is None:
+            self.x = torch.zeros((self.batch, 4, self.L, self.L), device=dev)
+        self._refill(dev)
+        n = self.table.iters(self.refill_every)
+        if n > 0:
+            multistep = self.scheduler.coefficient_table()[1].shape[1] == 8
+            kw = dict(start_steps=torch.tensor(self.table.start_rows()), n_iters=n, face_seeds=list(self.seeds))
+            if multistep:
+                kw["resume"] = torch.tensor(self.table.resume_flags(), dtype=torch.bool)
+            self.x = sample(self.model, self.x, None, None, self.scheduler, prepare=False, **kw)
+            self.calls += 1
+        for slot, rid in self.table.advance(n):
+            self.finished[rid] = self.x[slot].clone()
+        return n
+
+    def busy(self):
+        return bool(self.queue) or bool(self.table.occupied())
+
+    def poll(self):
+        """Finished requests since the last poll: {request id: final latents [4,L,L] (device)}."""
+        out, self.finished = self.finished, {}
+        return out
+
+    def drain(self):
+        """Run until every submitted request has finished; returns poll()."""
+        while self.busy():
+            self.step()
+        return self.poll()

@@ -161,6 +161,26 @@ int hd_sample_rows(hd_ctx* ctx, float* x_inout, const hd_schedule* sched, const 
 int hd_sample_rows_multistep(hd_ctx* ctx, float* x_inout, const hd_schedule_ms* sched, const int32_t* start_rows, int n_iters, int resume,
                              const float* noise, uint64_t seed, void* stream);
 
+/* Continuous batching (a serving loop that refills the slots of finished faces while the others go on).
+ * hd_prepare_slots: replace the conditioning of n faces of the prepared batch: slots[j] (host [n], distinct, in [0, B)) gets the conditioning
+ * of cr_latent[j] [4,L,L] and cr_face[j] [3,128,128] (or id_emb[j] [2048]; exactly one of the two), bit for bit what hd_prepare computes for
+ * these n faces as a batch of n.  The other slots' conditioning is not touched, captured graphs stay valid (nothing is recaptured), and the
+ * prologue runs for the n faces only.  The refilled slots have no multistep history (and hd_sample_rows_multistep(resume = 1) is refused
+ * until every face has one again).  HD_ERR_NOT_READY without a prepared conditional batch; HD_ERR_INVALID for a duplicate or out-of-range
+ * slot, n outside [1, B], an unconditional / CoarseRestoration / VAE context or a bad pointer combination. */
+int hd_prepare_slots(hd_ctx* ctx, int n, const int32_t* slots, const float* cr_latent, const float* cr_face, const float* id_emb, void* stream);
+/* hd_sample_rows / hd_sample_rows_multistep with per-face noise keys and per-face resumption (same graphs, hd_check and NaN-poisoning rules).
+ * face_seeds: host [B] or NULL.  With it, z of face f at row k, element e of the face (0 <= e < 4L^2) is Philox4x32-10(face_seeds[f]; k, e):
+ *   independent of the slot, the batch size and the neighbours -- a face in slot 0 with key s gets exactly the z of hd_sample_rows(seed = s)
+ *   for face 0.  NULL: hd_sample_rows' batch keying Philox(seed; k, element of the batch).  noise != NULL overrides both, as before.
+ * resume (multistep): host [B] of 0 / 1.  1 continues face f's history; 0 takes its first row first-order (h := x0).  HD_ERR_INVALID if
+ *   resume[f] == 1 for a face without a history: none since hd_prepare*, refilled by hd_prepare_slots, or a single-step call since its last
+ *   multistep row (hd_sample_multistep leaves every face one, a multistep rows / faces call every face that ran a row; a held face keeps its state). */
+int hd_sample_faces(hd_ctx* ctx, float* x_inout, const hd_schedule* sched, const int32_t* start_rows, int n_iters, const uint64_t* face_seeds,
+                    const float* noise, uint64_t seed, void* stream);
+int hd_sample_faces_multistep(hd_ctx* ctx, float* x_inout, const hd_schedule_ms* sched, const int32_t* start_rows, int n_iters,
+                              const int32_t* resume, const uint64_t* face_seeds, const float* noise, uint64_t seed, void* stream);
+
 /* One scheduler update on its own: `scheduler.step(eps, t, x).prev_sample` (test_refiner.py:91) in
  * the coefficient form of hd_schedule (coef7 on the host); x updated in place.  noise/seed/step as in
  * hd_sample.  Needs no context. */
@@ -192,7 +212,8 @@ int hd_debug_write(hd_ctx* ctx, const char* name, const float* host_in, int64_t 
  * i (-1: every stage) -- tests read a stage's residual stream block by block; "xcd_force_global" 1 = its
  * placement-independent hand-off form.  hd_get_option: "xcd" (effective), "xcd_stages" (stages built so far);
  * "sample_stage_launches" / "sample_face_stage_launches" / "rows_stage_launches": persistent-stage launches (all / face-cluster only) that
- * the last one-step capture of hd_sample* / hd_sample_rows* recorded (-1 before the first capture; a stage that fell back is not counted). */
+ * the last one-step capture of hd_sample* / hd_sample_rows* recorded (-1 before the first capture; a stage that fell back is not counted);
+ * "graph_captures": step graphs instantiated by this context so far (hd_prepare_slots adds none). */
 int hd_set_option(hd_ctx* ctx, const char* key, int value);
 int hd_get_option(hd_ctx* ctx, const char* key);
 /* Error status of the asynchronous calls.  hd_eps / hd_sample only enqueue work; a persistent stage launch that has to give

@@ -1,0 +1,199 @@
+"""Continuous batching against static batching: batch 64, latent 16, synthetic weights (writes profiles/r08_stream_bench.txt, or --out).
+
+Scenarios (requests all queued at t = 0; each request has its own seed and img2img strength):
+  (a) 512 requests at strength 1.0, DDIM-50;   (b) 512 requests with strengths uniform in [0.2, 1.0], DDIM-50;   (c) (b) with DPM-Solver++ 2M, 20 steps.
+Forms: static batching -- 64 requests at a time through sample(start_steps=...), the batch runs until its slowest face is done -- and
+sampling.ContinuousSampler at refill_every K = 1, 5, 10.  Each configuration is timed end to end (queue to last result, device
+synchronised), in alternating runs; reported: median and spread of faces/s, and the mean request latency (finish time - 0).
+Also: hd_prepare_slots for n = 1, 8, 32, 64 against hd_prepare at 64, hd_sample_faces ms/step against hd_sample_rows, and where the time
+of a continuous run goes (refills against sampling calls; an instrumented run with a synchronisation around each part)."""
+import argparse
+import ctypes
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def sync():
+    torch.cuda.synchronize()
+
+
+def requests(n, mixed, seed=8):
+    from hifidiff_amd import synth
+    _, crl, crf = synth.sample_inputs(64, 16, seed=seed)
+    g = torch.Generator().manual_seed(seed)
+    strength = (0.2 + 0.8 * torch.rand(n, generator=g)).tolist() if mixed else [1.0] * n
+    # 64 distinct conditioning inputs, reused round robin (their content does not change the cost)
+    return [(crf[i % 64].cuda(), crl[i % 64].cuda(), 1000 + i, strength[i]) for i in range(n)]
+
+
+def run_static(m, sch, reqs):
+    from hifidiff_amd import sampling
+    sync()
+    t0 = time.perf_counter()
+    lat = []
+    probe = sampling.ContinuousSampler(m, sch, batch=64)                  # only for the per-request initial latents (CPU generator)
+    for b in range(0, len(reqs), 64):
+        chunk = reqs[b:b + 64]
+        starts = [probe._start(crl, seed, st) for _, crl, seed, st in chunk]
+        x = torch.stack([s[0] for s in starts]).cuda()
+        rows = torch.tensor([s[1] for s in starts])
+        crf = torch.stack([r[0] for r in chunk])
+        crl = torch.stack([r[1] for r in chunk])
+        sampling.sample(m, x, crf, crl, sch, start_steps=rows, seed=chunk[0][2])      # hd_sample_rows*
+        lat += [time.perf_counter() - t0] * len(chunk)                    # sample() synchronises (check=True)
+    return time.perf_counter() - t0, statistics.mean(lat)
+
+
+def run_continuous(m, sch, reqs, K, instrument=False):
+    from hifidiff_amd import sampling
+    cs = sampling.ContinuousSampler(m, sch, batch=64, refill_every=K)
+    t_refill = [0.0]
+    if instrument:
+        inner = cs._refill
+
+        def timed_refill(dev):
+            sync()
+            t = time.perf_counter()
+            inner(dev)
+            sync()
+            t_refill[0] += time.perf_counter() - t
+        cs._refill = timed_refill
+    sync()
+    t0 = time.perf_counter()
+    for r in reqs:
+        cs.submit(*r)
+    lat = []
+    while cs.busy():
+        cs.step()                                                         # sample() synchronises after each call
+        done = cs.poll()
+        lat += [time.perf_counter() - t0] * len(done)
+    total = time.perf_counter() - t0
+    return total, statistics.mean(lat), t_refill[0], cs.calls
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--requests", type=int, default=512)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08_stream_bench.txt"))
+    a = ap.parse_args()
+    from hifidiff_amd import _lib, schedulers, synth
+    from hifidiff_amd.refiner import FacialRefiner
+    torch.set_grad_enabled(False)
+    m = FacialRefiner(16)
+    m.load_state_dict(synth.refiner_state_dict(16))
+    m.to("cuda:0")
+    L = _lib.lib()
+    out = ["# tools/stream_bench.py: batch 64, latent 16, synthetic weights, one MI355X; requests queued at t = 0; "
+           f"{a.runs} alternating runs per configuration (median [min, max])"]
+
+    def ddim():
+        s = schedulers.DDIMScheduler(clip_sample_range=3.0)
+        s.set_timesteps(50)
+        return s
+
+    def dpm():
+        s = schedulers.DPMSolverMultistepScheduler()
+        s.set_timesteps(20)
+        return s
+
+    scen = [("a", "512 requests, strength 1.0, DDIM-50", ddim, False), ("b", "512 requests, strength U[0.2, 1.0], DDIM-50", ddim, True),
+            ("c", "512 requests, strength U[0.2, 1.0], DPM-Solver++ 2M 20 steps", dpm, True)]
+    forms = ["static"] + [f"continuous K={k}" for k in (1, 5, 10)]
+    for key, title, mk, mixed in scen:
+        reqs = requests(a.requests, mixed)
+        sch = mk()
+        n = len(reqs)
+
+        def one(form):
+            if form == "static":
+                return run_static(m, sch, reqs)
+            return run_continuous(m, sch, reqs, int(form.split("=")[1]))[:2]
+        for f in forms:                                                   # warm: captures, FiLM table, staging chain
+            one(f) if f == "static" else run_continuous(m, sch, reqs[:96], int(f.split("=")[1]))
+        res = {f: [] for f in forms}
+        for _ in range(a.runs):
+            for f in forms:
+                res[f].append(one(f))
+        out.append(f"\n({key}) {title}")
+        out.append("form                 faces/s median [min, max]        mean latency s   vs static")
+        base = statistics.median(n / t for t, _ in res["static"])
+        for f in forms:
+            fps = [n / t for t, _ in res[f]]
+            lat = statistics.median(l for _, l in res[f])
+            out.append(f"{f:<20} {statistics.median(fps):8.1f} [{min(fps):7.1f}, {max(fps):7.1f}]   {lat:10.3f}      "
+                       f"{statistics.median(fps) / base:5.2f}x")
+        for k in (1, 5, 10):
+            total, _, t_ref, calls = run_continuous(m, sch, reqs, k, instrument=True)
+            out.append(f"  instrumented continuous K={k}: {total:.3f} s, of which refills {t_ref:.3f} s ({100 * t_ref / total:.1f} %), "
+                       f"{calls} sampling calls")
+        print("\n".join(out[-(len(forms) + 5):]), flush=True)
+
+    # hd_prepare_slots against hd_prepare
+    _, crl, crf = synth.sample_inputs(64, 16)
+    crl, crf = crl.cuda(), crf.cuda()
+    m.engine.prepare(crl, cr_face=crf)
+
+    def t_ms(fn, reps=10):
+        fn()
+        sync()
+        v = []
+        for _ in range(reps):
+            sync()
+            t = time.perf_counter()
+            fn()
+            sync()
+            v.append((time.perf_counter() - t) * 1e3)
+        return statistics.median(v), min(v), max(v)
+    out.append("\nconditioning (ms, host-timed with synchronisation, median [min, max] of 10)")
+    t = t_ms(lambda: m.engine.prepare(crl, cr_face=crf))
+    out.append(f"hd_prepare        B = 64: {t[0]:7.3f} [{t[1]:.3f}, {t[2]:.3f}]")
+    for nn in (1, 8, 32, 64):
+        sl = list(range(0, 64, 64 // nn))[:nn]
+        t = t_ms(lambda: m.engine.prepare_slots(sl, crl[:nn], cr_face=crf[:nn]))
+        out.append(f"hd_prepare_slots  n = {nn:2d}: {t[0]:7.3f} [{t[1]:.3f}, {t[2]:.3f}]")
+
+    # hd_sample_faces against hd_sample_rows (DDIM-50, start rows spread over the schedule, as tools/rows_bench.py)
+    s = ddim()
+    ts, coef = [u.float().contiguous() for u in s.coefficient_table()]
+    sc = _lib.Schedule()
+    sc.n_steps = 50
+    sc.timesteps = ctypes.cast(ts.data_ptr(), ctypes.POINTER(ctypes.c_float))
+    sc.coef = ctypes.cast(coef.data_ptr(), ctypes.POINTER(ctypes.c_float))
+    rows = torch.tensor([f * 49 // 63 for f in range(64)], dtype=torch.int32)
+    rp = ctypes.cast(rows.data_ptr(), ctypes.POINTER(ctypes.c_int32))
+    seeds = (ctypes.c_uint64 * 64)(*range(64))
+    xd = synth.sample_inputs(64, 16)[0].cuda().contiguous()
+    ctx, stream = m.engine.ctx, torch.cuda.current_stream().cuda_stream
+    fns = {"hd_sample_rows": lambda: L.hd_sample_rows(ctx, xd.data_ptr(), ctypes.byref(sc), rp, 50, None, 0, stream),
+           "hd_sample_faces": lambda: L.hd_sample_faces(ctx, xd.data_ptr(), ctypes.byref(sc), rp, 50, seeds, None, 0, stream)}
+    res = {k: [] for k in fns}
+    for f in fns.values():
+        _lib.check(f(), ctx)
+    for _ in range(5):
+        for k, f in fns.items():
+            sync()
+            t = time.perf_counter()
+            _lib.check(f(), ctx)
+            sync()
+            res[k].append((time.perf_counter() - t) * 1e3 / 50)
+    _lib.check(L.hd_check(ctx), ctx)
+    out.append("\nms per step, DDIM-50, start rows f * 49 // 63, median [min, max] of 5 alternating runs")
+    for k, v in res.items():
+        out.append(f"{k:<16} {statistics.median(v):.3f} [{min(v):.3f}, {max(v):.3f}]")
+    txt = "\n".join(out) + "\n"
+    print(txt)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as fh:
+        fh.write(txt)
+
+
+if __name__ == "__main__":
+    main()
