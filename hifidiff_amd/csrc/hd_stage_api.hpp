@@ -34,7 +34,7 @@ struct XStageP {
     int phase_limit;                      // introspection: stop after this many phases (<= 0: all)
     int force_global;                     // test: use the placement-independent hand-off even when the group shares an XCD
 #ifdef HD_STAMPS
-    unsigned long long* stamps;           // [phase][workgroup][8]: 0 start, 1 barrier passed, 2 K loop done, 3 epilogue stores issued, 4 drained, 5 published
+    unsigned long long* stamps;           // [phase][workgroup][8]: 0 start, 1 barrier passed, 2 K loop done, 6 K-split partials in LDS, 3 epilogue done, 4 stores issued, 5 published
     int dbg_no_a, dbg_no_w;               // timing-only what-ifs (results are garbage): activation loads through zero-record descriptors / no weight loads
 #endif
     int film_face_stride;                 // per-face FiLM rows (hd_sample_rows*, xcd_rows_stage_kernel): face f's rows at film + f * film_face_stride

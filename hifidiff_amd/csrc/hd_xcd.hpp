@@ -52,6 +52,30 @@
 #include "hd_gemm.hpp"
 #include "hd_stage_api.hpp"
 
+// When wave 0 requests its own K slice of a phase's weights (timing only; every form computes the same bits):
+//   0  at the start of the phase, behind the barrier wait
+//   1  right after it has published the previous phase
+//   2  after its K loop of the previous phase, with the other waves' first half (its store drain then waits for them)
+//   3  first half after its K loop, second half after it has published
+#ifndef HD_XS_W0
+#define HD_XS_W0 0
+#endif
+// 1: the epilogue's per-column constants are waited for before the next phase's weights are requested (timing only;
+// the epilogue then runs at its no-weight time: 2.5 vs 4.2 us per level-3 block)
+#ifndef HD_XS_READY
+#define HD_XS_READY 1
+#endif
+// 1: (level 3) wave 0 publishes before the other waves request the second half of the next phase's weights, so the flag
+// store does not queue behind 64 KB of far-source requests in the CU (timing only; tools/xcd_stage_bench.hip, 8 blocks:
+// 198 vs 204-210 us)
+#ifndef HD_XS_PUBFIRST
+#define HD_XS_PUBFIRST 1
+#endif
+// weight fragments loaded non-temporally (timing only)
+#ifndef HD_XS_WNT
+#define HD_XS_WNT 0
+#endif
+
 #pragma clang fp contract(off)                         // as hd_gemm.hpp: every fused multiply-add is written out
 
 namespace hd {
@@ -107,7 +131,11 @@ __device__ __forceinline__ unsigned xs_xcc_id() {
 }
 // pointers read from the LDS copy of the block table are generic to the compiler: say that they point to global memory
 __device__ __forceinline__ uint4 xs_ldg_u4(const uint4* p) {
+#if HD_XS_WNT
+    const xs_u32x4 v = __builtin_nontemporal_load(reinterpret_cast<__attribute__((address_space(1))) const xs_u32x4*>((unsigned long long)p));
+#else
     const xs_u32x4 v = *reinterpret_cast<__attribute__((address_space(1))) const xs_u32x4*>((unsigned long long)p);
+#endif
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ float xs_ldg_f(const float* p) { return *reinterpret_cast<__attribute__((address_space(1))) const float*>((unsigned long long)p); }
@@ -115,6 +143,14 @@ __device__ __forceinline__ float4 xs_ldg_f4(const float* p) {
     typedef float f4v __attribute__((ext_vector_type(4)));
     const f4v v = *reinterpret_cast<__attribute__((address_space(1))) const f4v*>((unsigned long long)p);
     return make_float4(v.x, v.y, v.z, v.w);
+}
+// x is in its register from here on.  A wave's loads complete in order and the compiler waits for one with a count of the
+// loads issued after it, which it cannot know past the conditional weight requests: without this the first use of x in the
+// epilogue waits (vmcnt(0)) for the next phase's weights, requested after it from a far source
+__device__ __forceinline__ void xs_ready(float& x) {
+#if HD_XS_READY
+    asm volatile("" : "+v"(x));
+#endif
 }
 // LDS-only workgroup barrier: __syncthreads() is also a fence and would drain the weight loads in flight
 __device__ __forceinline__ void xs_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -468,7 +504,7 @@ __global__ __launch_bounds__(XS_THREADS) void HD_XCD_KERNEL(const XStageP p) {
             if (ph > 0) { wait_phase(ph - 1); if (dead) return; }
             HD_XSTAMP(1);
             ln_issue(rs_sx, B.film_off);                                // first: the statistics barrier waits for the slowest wave's partials
-            if (ph > 0 && wave == 0) load_w(B.w1, std::true_type());
+            if (HD_XS_W0 == 0 && ph > 0 && wave == 0) load_w(B.w1, std::true_type());
             load_a(rs_Xb);
             // per-channel constants of the fused epilogue (weights: plain loads), parked in LDS until the epilogue: 22 values per
             // column (9 + 9 depthwise taps of the two gate halves, their biases, conv1's biases); two loads per thread
@@ -483,11 +519,13 @@ __global__ __launch_bounds__(XS_THREADS) void HD_XCD_KERNEL(const XStageP p) {
             }
             ln_finish();
             gemm_ln();
-            if (wave != 0 && ph + 1 < P_run) load_w_chunk(B.wsca, std::false_type(), std::integral_constant<int, 0>());
+            if ((wave != 0 || HD_XS_W0 >= 2) && ph + 1 < P_run) load_w_chunk(B.wsca, std::false_type(), std::integral_constant<int, 0>());
+            if (HD_XS_W0 == 2 && wave == 0 && ph + 1 < P_run) load_w_chunk(B.wsca, std::false_type(), std::integral_constant<int, 1>());
             HD_XSTAMP(2);
 #pragma unroll
             for (int i = 0; i < 2; ++i) { const int e = tid + i * XS_THREADS; if (e < 22 * 32) L.dwc[e] = dwc[i]; }
             to_red(std::true_type());
+            HD_XSTAMP(6);
             constexpr int TILE_F = K::RCU * 32 * 2;
             float dw_wa[9], dw_wb[9];
             const int jc = tid & 31;
@@ -537,9 +575,16 @@ __global__ __launch_bounds__(XS_THREADS) void HD_XCD_KERNEL(const XStageP p) {
                 }
                 HD_XSTAMP(4);
             }
+#if HD_XS_PUBFIRST
+            if (wave == 0) publish(ph);
+#endif
             if constexpr (K::kStoresFirst) xs_lds_barrier();          // wave 0's stores are in the queue ahead of the weight requests
             if constexpr (K::kStoresFirst) { if (wave != 0 && ph + 1 < P_run) load_w_chunk(B.wsca, std::false_type(), std::integral_constant<int, 1>()); }
+#if !HD_XS_PUBFIRST
             if (wave == 0) publish(ph);
+#endif
+            if (HD_XS_W0 == 1 && wave == 0 && ph + 1 < P_run) load_w(B.wsca, std::false_type());
+            if (HD_XS_W0 == 3 && wave == 0 && ph + 1 < P_run) load_w_chunk(B.wsca, std::false_type(), std::integral_constant<int, 1>());
             HD_XSTAMP(5);
         }
         // ======================= q1: s = sca(pooled) ; G <- bf16(G * s) =======================
@@ -548,9 +593,9 @@ __global__ __launch_bounds__(XS_THREADS) void HD_XCD_KERNEL(const XStageP p) {
             if (ph >= P_run) break;
             HD_XSTAMP(0);
             wait_phase(ph - 1); if (dead) return;
-            if (wave == 0) load_w(B.wsca, std::false_type());
+            if (HD_XS_W0 == 0 && wave == 0) load_w(B.wsca, std::false_type());
             HD_XSTAMP(1);
-            const float bsca = xs_ldg_f(B.bsca + col);
+            float bsca = xs_ldg_f(B.bsca + col);
             zero_acc();
             if (wm == 0) {
                 // rows = this workgroup's faces (<= 8); the other rows of the MFMA tile are zero
@@ -567,7 +612,9 @@ __global__ __launch_bounds__(XS_THREADS) void HD_XCD_KERNEL(const XStageP p) {
                     chunk_mma(d, std::false_type());
                 }
             }
-            if (wave != 0 && ph + 1 < P_run) load_w_chunk(B.w3, std::false_type(), std::integral_constant<int, 0>());
+            xs_ready(bsca);
+            if ((wave != 0 || HD_XS_W0 >= 2) && ph + 1 < P_run) load_w_chunk(B.w3, std::false_type(), std::integral_constant<int, 0>());
+            if (HD_XS_W0 == 2 && wave == 0 && ph + 1 < P_run) load_w_chunk(B.w3, std::false_type(), std::integral_constant<int, 1>());
             HD_XSTAMP(2);
             // partial tiles of the 8 face rows -> LDS, summed in wave order
             xs_lds_barrier();
@@ -579,6 +626,7 @@ __global__ __launch_bounds__(XS_THREADS) void HD_XCD_KERNEL(const XStageP p) {
                 }
             }
             xs_lds_barrier();
+            HD_XSTAMP(6);
             if (tid < K::FCU * 32) {
                 float v = bsca;
 #pragma unroll
@@ -605,9 +653,16 @@ __global__ __launch_bounds__(XS_THREADS) void HD_XCD_KERNEL(const XStageP p) {
                 if (p.S) for (int e = lane; e < K::FCU * 32; e += 64) if (face0 + (e >> 5) < p.B) p.S[(size_t)(face0 + (e >> 5)) * C + ct * 32 + (e & 31)] = L.pl[e];
                 HD_XSTAMP(4);
             }
+#if HD_XS_PUBFIRST
+            if (wave == 0) publish(ph);
+#endif
             if constexpr (K::kStoresFirst) xs_lds_barrier();          // wave 0's stores are in the queue ahead of the weight requests
             if constexpr (K::kStoresFirst) { if (wave != 0 && ph + 1 < P_run) load_w_chunk(B.w3, std::false_type(), std::integral_constant<int, 1>()); }
+#if !HD_XS_PUBFIRST
             if (wave == 0) publish(ph);
+#endif
+            if (HD_XS_W0 == 1 && wave == 0 && ph + 1 < P_run) load_w(B.w3, std::false_type());
+            if (HD_XS_W0 == 3 && wave == 0 && ph + 1 < P_run) load_w_chunk(B.w3, std::false_type(), std::integral_constant<int, 1>());
             HD_XSTAMP(5);
         }
         // ======================= q2: conv3 ; y = x + beta * (.) ; LayerNorm partials =======================
@@ -616,14 +671,17 @@ __global__ __launch_bounds__(XS_THREADS) void HD_XCD_KERNEL(const XStageP p) {
             if (ph >= P_run) break;
             HD_XSTAMP(0);
             wait_phase(ph - 1); if (dead) return;
-            if (wave == 0) load_w(B.w3, std::false_type());
+            if (HD_XS_W0 == 0 && wave == 0) load_w(B.w3, std::false_type());
             HD_XSTAMP(1);
             load_a(rs_G);
-            const float b3 = xs_ldg_f(B.b3 + col), beta = xs_ldg_f(B.beta + col);
+            float b3 = xs_ldg_f(B.b3 + col), beta = xs_ldg_f(B.beta + col);
             gemm_plain(std::false_type());
-            if (wave != 0 && ph + 1 < P_run) load_w_chunk(B.w4, std::true_type(), std::integral_constant<int, 0>());
+            xs_ready(b3); xs_ready(beta);
+            if ((wave != 0 || HD_XS_W0 >= 2) && ph + 1 < P_run) load_w_chunk(B.w4, std::true_type(), std::integral_constant<int, 0>());
+            if (HD_XS_W0 == 2 && wave == 0 && ph + 1 < P_run) load_w_chunk(B.w4, std::true_type(), std::integral_constant<int, 1>());
             HD_XSTAMP(2);
             to_red(std::false_type());
+            HD_XSTAMP(6);
             constexpr int TILE_F = K::RCU * 32;
             float v[K::NIT];
 #pragma unroll
@@ -656,9 +714,16 @@ __global__ __launch_bounds__(XS_THREADS) void HD_XCD_KERNEL(const XStageP p) {
                 for (int r = lane; r < K::RCU; r += 64) if (row0 + r < M) st64(rs_sy, ((row0 + r) * K::NT + ct) * 8, st_out[r]);
                 HD_XSTAMP(4);
             }
+#if HD_XS_PUBFIRST
+            if (wave == 0) publish(ph);
+#endif
             if constexpr (K::kStoresFirst) xs_lds_barrier();          // wave 0's stores are in the queue ahead of the weight requests
             if constexpr (K::kStoresFirst) { if (wave != 0 && ph + 1 < P_run) load_w_chunk(B.w4, std::true_type(), std::integral_constant<int, 1>()); }
+#if !HD_XS_PUBFIRST
             if (wave == 0) publish(ph);
+#endif
+            if (HD_XS_W0 == 1 && wave == 0 && ph + 1 < P_run) load_w(B.w4, std::true_type());
+            if (HD_XS_W0 == 3 && wave == 0 && ph + 1 < P_run) load_w_chunk(B.w4, std::true_type(), std::integral_constant<int, 1>());
             HD_XSTAMP(5);
         }
         // ======================= q3: LN + FiLM -> conv4 -> SimpleGate =======================
@@ -669,14 +734,17 @@ __global__ __launch_bounds__(XS_THREADS) void HD_XCD_KERNEL(const XStageP p) {
             wait_phase(ph - 1); if (dead) return;
             HD_XSTAMP(1);
             ln_issue(rs_sy, B.film_off + 2 * C);                       // first: the statistics barrier waits for the slowest wave's partials
-            if (wave == 0) load_w(B.w4, std::true_type());
+            if (HD_XS_W0 == 0 && wave == 0) load_w(B.w4, std::true_type());
             load_a(rs_Yb);
-            const float b4a = xs_ldg_f(B.b4 + col), b4b = xs_ldg_f(B.b4 + col + C);
+            float b4a = xs_ldg_f(B.b4 + col), b4b = xs_ldg_f(B.b4 + col + C);
             ln_finish();
             gemm_ln();
-            if (wave != 0 && ph + 1 < P_run) load_w_chunk(B.w5, std::false_type(), std::integral_constant<int, 0>());
+            xs_ready(b4a); xs_ready(b4b);
+            if ((wave != 0 || HD_XS_W0 >= 2) && ph + 1 < P_run) load_w_chunk(B.w5, std::false_type(), std::integral_constant<int, 0>());
+            if (HD_XS_W0 == 2 && wave == 0 && ph + 1 < P_run) load_w_chunk(B.w5, std::false_type(), std::integral_constant<int, 1>());
             HD_XSTAMP(2);
             to_red(std::true_type());
+            HD_XSTAMP(6);
             constexpr int TILE_F = K::RCU * 32 * 2;
 #pragma unroll
             for (int it = 0; it < K::NIT; ++it) {
@@ -696,9 +764,16 @@ __global__ __launch_bounds__(XS_THREADS) void HD_XCD_KERNEL(const XStageP p) {
                 }
                 HD_XSTAMP(4);
             }
+#if HD_XS_PUBFIRST
+            if (wave == 0) publish(ph);
+#endif
             if constexpr (K::kStoresFirst) xs_lds_barrier();          // wave 0's stores are in the queue ahead of the weight requests
             if constexpr (K::kStoresFirst) { if (wave != 0 && ph + 1 < P_run) load_w_chunk(B.w5, std::false_type(), std::integral_constant<int, 1>()); }
+#if !HD_XS_PUBFIRST
             if (wave == 0) publish(ph);
+#endif
+            if (HD_XS_W0 == 1 && wave == 0 && ph + 1 < P_run) load_w(B.w5, std::false_type());
+            if (HD_XS_W0 == 3 && wave == 0 && ph + 1 < P_run) load_w_chunk(B.w5, std::false_type(), std::integral_constant<int, 1>());
             HD_XSTAMP(5);
         }
         // ======================= q4: conv5 ; x' = y + gamma * (.) ; LayerNorm partials =======================
@@ -707,16 +782,19 @@ __global__ __launch_bounds__(XS_THREADS) void HD_XCD_KERNEL(const XStageP p) {
             if (ph >= P_run) break;
             HD_XSTAMP(0);
             wait_phase(ph - 1); if (dead) return;
-            if (wave == 0) load_w(B.w5, std::false_type());
+            if (HD_XS_W0 == 0 && wave == 0) load_w(B.w5, std::false_type());
             HD_XSTAMP(1);
             load_a(rs_G);
-            const float b5 = xs_ldg_f(B.b5 + col), gamma = xs_ldg_f(B.gamma + col);
+            float b5 = xs_ldg_f(B.b5 + col), gamma = xs_ldg_f(B.gamma + col);
             const bool last = (ph == P_run - 1);
             const bool gated = last && ph == P - 1 && p.outg16 != nullptr;
             gemm_plain(std::false_type());
-            if (wave != 0 && !last) load_w_chunk(L.blk[blk + 1].w1, std::true_type(), std::integral_constant<int, 0>());
+            xs_ready(b5); xs_ready(gamma);
+            if ((wave != 0 || HD_XS_W0 >= 2) && !last) load_w_chunk(L.blk[blk + 1].w1, std::true_type(), std::integral_constant<int, 0>());
+            if (HD_XS_W0 == 2 && wave == 0 && !last) load_w_chunk(L.blk[blk + 1].w1, std::true_type(), std::integral_constant<int, 1>());
             HD_XSTAMP(2);
             to_red(std::false_type());
+            HD_XSTAMP(6);
             constexpr int TILE_F = K::RCU * 32;
             float v[K::NIT];
 #pragma unroll
@@ -778,9 +856,16 @@ __global__ __launch_bounds__(XS_THREADS) void HD_XCD_KERNEL(const XStageP p) {
             } else if (wave == 0) {
                 HD_XSTAMP(4);
             }
+#if HD_XS_PUBFIRST
+            if (wave == 0 && !last) publish(ph);
+#endif
             if constexpr (K::kStoresFirst) xs_lds_barrier();          // wave 0's stores are in the queue ahead of the weight requests
             if constexpr (K::kStoresFirst) { if (wave != 0 && !last) load_w_chunk(L.blk[blk + 1].w1, std::true_type(), std::integral_constant<int, 1>()); }
+#if !HD_XS_PUBFIRST
             if (wave == 0 && !last) publish(ph);
+#endif
+            if (HD_XS_W0 == 1 && wave == 0 && !last) load_w(L.blk[blk + 1].w1, std::true_type());
+            if (HD_XS_W0 == 3 && wave == 0 && !last) load_w_chunk(L.blk[blk + 1].w1, std::true_type(), std::integral_constant<int, 1>());
             HD_XSTAMP(5);
         }
     }

@@ -1,8 +1,11 @@
 // xcd_stage_bench.hip — the XCD-local persistent stage kernel (hifidiff_amd/csrc/hd_xcd.hpp) on its own, diagnostic build
 // with in-kernel stamps (tools only): synthetic weights and activations of the level's shapes, batch 64, a few warm
-// launches, then per phase the median over workgroups of: barrier wait, K loop (A loads + LayerNorm + MFMA), epilogue,
-// store drain, publish; and the span of the phase over the whole chip.
+// launches, then per phase, as the median over workgroups and for the slowest workgroup of each group (the last to publish):
+// barrier wait, wave 0's loads + K loop, the other waves' K loops + the K-split partials in LDS, reduction + epilogue, hand-off
+// stores, drain + publish; and the span of the phase over the whole chip.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -DHD_STAMPS -o tools/xcd_stage_bench_bin tools/xcd_stage_bench.hip
+//        what-if builds of the stage (hd_xcd.hpp): -DHD_XS_W0=0..3 (when wave 0 requests its weights), -DHD_XS_WNT=1 (non-temporal weights)
+//        `xcd_stage_bench_bin 20 9`: level 3 only, with the near-source and no-weight what-ifs
 //        (-DXS_EXPERIMENT_PASSES [-DXS_PASS_ROWS=64]: `xcd_stage_bench_bin 20 32` times the archived multi-pass form at latent 32, level 3)
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -86,26 +89,65 @@ void run(int nblocks, int B, int reps, int force_global, int no_a = 0, int no_w 
            best * 1e3, best * 1e3 / nblocks, best * 1e3 / P);
     auto med = [](std::vector<double> v) { std::sort(v.begin(), v.end()); return v[v.size() / 2]; };
     const char* qn[5] = {"q0 conv1+dw", "q1 sca", "q2 conv3", "q3 conv4", "q4 conv5"};
-    double acc[5][6] = {};
+    // segments of a workgroup's phase (thread 0 = wave 0): wait (0-1), wave 0's loads + K loop (1-2), the other waves' K loops +
+    // the K-split partial tiles in LDS (2-6), reduction + epilogue (6-3), hand-off stores issued (3-4), drain + publish (4-5)
+    const int sa[6] = {0, 1, 2, 6, 3, 4}, sb[6] = {1, 2, 6, 3, 4, 5};
+    auto segs = [&](const unsigned long long* s, double* o) { for (int k = 0; k < 6; ++k) o[k] = (double)(s[sb[k]] >= s[sa[k]] ? s[sb[k]] - s[sa[k]] : 0) * 0.01; };
+    double acc[5][7] = {}, slow[5][7] = {};
     int cnt[5] = {};
+    auto line = [&](const char* what, const char* name, const double* v) {
+        printf("  %-22s %-12s wait %5.2f  kloop %5.2f  ksync %5.2f  epilogue %5.2f  stores %5.2f  publish %5.2f | %s %5.2f us\n", what, name, v[0], v[1], v[2], v[3], v[4], v[5],
+               what[0] == 's' ? "lag" : "span", v[6]);
+    };
     for (int ph = 0; ph < P; ++ph) {
-        std::vector<double> seg[5];
+        std::vector<double> seg[6], end5;
+        double sl[7] = {};
         unsigned long long lo = ~0ull, hi = 0;
+        int ng = 0;
         for (int b = 0; b < 256; ++b) {
             const unsigned long long* s = &h[((size_t)ph * 256 + b) * 8];
             if (!s[0]) continue;
-            for (int k = 0; k < 5; ++k) seg[k].push_back((double)(s[k + 1] >= s[k] ? s[k + 1] - s[k] : 0) * 0.01);
+            double o[6]; segs(s, o);
+            for (int k = 0; k < 6; ++k) seg[k].push_back(o[k]);
             lo = std::min(lo, s[0]); hi = std::max(hi, s[5]);
         }
         if (seg[0].empty()) continue;
+        // the slowest workgroup of each group: the last to publish (what every member's next wait waits for); lag = its
+        // publish stamp behind the group's median publish stamp
+        for (int g = 0; g < 8; ++g) {
+            int wb = -1; unsigned long long last = 0;
+            std::vector<unsigned long long> pubs;
+            for (int r = 0; r < 32; ++r) {
+                const int b = r * 8 + g;
+                const unsigned long long* s = &h[((size_t)ph * 256 + b) * 8];
+                if (!s[0]) continue;
+                pubs.push_back(s[5]);
+                if (s[5] > last) { last = s[5]; wb = b; }
+            }
+            if (wb < 0) continue;
+            std::sort(pubs.begin(), pubs.end());
+            double o[6]; segs(&h[((size_t)ph * 256 + wb) * 8], o);
+            for (int k = 0; k < 6; ++k) sl[k] += o[k];
+            sl[6] += (double)(last - pubs[pubs.size() / 2]) * 0.01;
+            ++ng;
+        }
+        for (int k = 0; k < 7; ++k) sl[k] /= ng;
+        double md[7];
+        for (int k = 0; k < 6; ++k) md[k] = med(seg[k]);
+        md[6] = (hi - lo) * 0.01;
         const int q = ph % 5;
-        if (ph >= 5 && ph < P - 5) { for (int k = 0; k < 5; ++k) acc[q][k] += med(seg[k]); acc[q][5] += (hi - lo) * 0.01; cnt[q]++; }
-        if (ph < 10) printf("  phase %2d %-12s wait %5.2f  kloop %5.2f  epilogue %5.2f  drain %5.2f  publish %5.2f | span %5.2f us\n", ph, qn[q], med(seg[0]), med(seg[1]), med(seg[2]),
-                            med(seg[3]), med(seg[4]), (hi - lo) * 0.01);
+        if (ph >= 5 && ph < P - 5) { for (int k = 0; k < 7; ++k) { acc[q][k] += md[k]; slow[q][k] += sl[k]; } cnt[q]++; }
+        if (ph < 10) { char nm[32]; snprintf(nm, sizeof nm, "phase %2d median", ph); line(nm, qn[q], md); }
     }
+    double tm[7] = {}, ts[7] = {};
     for (int q = 0; q < 5; ++q)
-        if (cnt[q]) printf("  mean over inner blocks %-12s wait %5.2f  kloop %5.2f  epilogue %5.2f  drain %5.2f  publish %5.2f | span %5.2f us\n", qn[q], acc[q][0] / cnt[q], acc[q][1] / cnt[q],
-                           acc[q][2] / cnt[q], acc[q][3] / cnt[q], acc[q][4] / cnt[q], acc[q][5] / cnt[q]);
+        if (cnt[q]) {
+            for (int k = 0; k < 7; ++k) { acc[q][k] /= cnt[q]; slow[q][k] /= cnt[q]; tm[k] += acc[q][k]; ts[k] += slow[q][k]; }
+            line("inner blocks, median", qn[q], acc[q]);
+            line("slowest of each group", qn[q], slow[q]);
+        }
+    line("sum of 5 phases, median", "one block", tm);
+    line("slowest of each group", "one block", ts);
 }
 
 int main(int argc, char** argv) {
@@ -120,6 +162,7 @@ int main(int argc, char** argv) {
     }
 #endif
     run<1024, 4>(8, 64, reps, 0);
+    if (argc > 2 && atoi(argv[2]) == 8) { run<512, 16>(4, 64, reps, 0); return 0; }        // the two stage shapes of the step, nothing else
     if (argc > 2 && atoi(argv[2]) == 9) { run<1024, 4>(8, 64, reps, 0, 0, 0, 1); run<1024, 4>(8, 64, reps, 0, 0, 1); return 0; }
     run<512, 16>(4, 64, reps, 0);
     run<1024, 4>(8, 64, reps, 1);
