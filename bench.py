@@ -23,10 +23,13 @@ Prints ONE JSON line (rank 0).  `roofline`: one launch = one captured step graph
 evaluation of the whole batch); algorithmic bytes per launch = the bf16 weights every step must stream
 (0.7227 GB at latent 16), duration = HIP-event time of the replay loop / diffusion steps.
 `roofline.latency_floor_ms` = dependent launches x measured boundary + in-launch hand-offs x measured hand-off + weight bytes / measured chip
-stream rate (each term with its profiles/ file); `frac_of_latency_floor` = that / the measured step.  `secondary`: BASELINE configs[3]
-(latent 32, batch 64, 250-step DDIM), 3 timed passes after the headline's timed region.
+stream rate (each term with its profiles/ file); `frac_of_latency_floor` = that / the measured step.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the dump and the JSON line.
+`--full` adds the measurements that take runs of their own, after the headline's timed region (they never touch `value`):
+`secondary`: BASELINE configs[3] (latent 32, batch 64, 250-step DDIM), 3 timed passes (`--no-secondary` skips it).
 `cpu_baseline`: the CPU oracle (a port of the reference's algorithm, as-written semantics: FPG+IDC
-recomputed every step, fp32) timed on this host on a bounded sample and extrapolated linearly.
+recomputed every step, fp32) timed on this host on a bounded sample and extrapolated linearly (`--no-cpu-baseline` skips it).
 """
 import argparse
 import ctypes
@@ -320,7 +323,7 @@ def dump_outputs(d, arrays):
         np.save(os.path.join(d, name + ".npy"), v.numpy())
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -329,11 +332,25 @@ def main():
     ap.add_argument("--latent", type=int, default=16)
     ap.add_argument("--diffusion-steps", type=int, default=1000)
     ap.add_argument("--kind", default="ddpm", choices=["ddpm", "ddim"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[3] passes that follow the headline's timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the configs[3] passes (`secondary`) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the configs[3] passes that follow the headline's timed region")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the final latents of the last timed step to DIR/latents.npy (float32, rank 0, at most 64 MB)")
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def extra_legs(a, headline, world):
+    """What a run measures besides the headline figure, in order, after its timed region: nothing without --full;
+    `secondary` only after the headline configuration; both at N = 1 only."""
+    if not a.full or world != 1:
+        return []
+    return [leg for leg, on in (("secondary", headline and not a.no_secondary), ("cpu_baseline", not a.no_cpu_baseline)) if on]
+
+
+def main():
+    a = parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -496,9 +513,10 @@ def main():
                        "output_finite": finite},
             "roofline": roof,
         }
-        if headline and world == 1 and not a.no_secondary:    # BASELINE configs[3], after the headline's timed region; never touches `value`
+        legs = extra_legs(a, headline, world)
+        if "secondary" in legs:                               # BASELINE configs[3], after the headline's timed region; never touches `value`
             res["secondary"] = measure_config3(dev, reuse=(P, a.latent))
-        if not a.no_cpu_baseline and world == 1:              # the CPU leg is reported at N=1 only
+        if "cpu_baseline" in legs:
             cb = cpu_baseline(P, a.latent, n_diff)
             res["cpu_baseline"] = {
                 "value": cb["as_written"]["value"], "unit": "faces/s", "cores": cb["cores"], "host_cores": torch.get_num_threads(), "kind": "port",

@@ -274,6 +274,24 @@ def test_bench_dump_outputs_writes_float32_within_the_limit(tmp_path):
     assert rows == sorted(rows)
 
 
+def test_plain_bench_run_measures_only_the_headline():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` does only what the headline figure needs; `--full` adds `secondary` (after the
+    headline configuration only) and `cpu_baseline`, each of which its --no-* option drops again, at N = 1 only."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    plain = ["--gpus", "1", "--steps", "20", "--warmup", "5"]
+    assert b.extra_legs(b.parse_args(plain), True, 1) == []
+    assert b.extra_legs(b.parse_args(plain + ["--dump-outputs", "d"]), True, 1) == []
+    full = b.parse_args(plain + ["--full"])
+    assert b.extra_legs(full, True, 1) == ["secondary", "cpu_baseline"]
+    assert b.extra_legs(full, False, 1) == ["cpu_baseline"]
+    assert b.extra_legs(full, True, 2) == []
+    assert b.extra_legs(b.parse_args(plain + ["--full", "--no-secondary"]), True, 1) == ["cpu_baseline"]
+    assert b.extra_legs(b.parse_args(plain + ["--full", "--no-cpu-baseline"]), True, 1) == ["secondary"]
+
+
 def test_synthetic_weights_can_be_reused_across_latent_sides():
     """bench.py's `secondary` (latent 32) takes every tensor whose spec does not depend on the latent side from the headline's state dict:
     a tensor is a pure function of (name, shape, kind, fan_in, seed), so only idc_conv is generated again and the values are the same."""

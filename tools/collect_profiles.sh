@@ -58,9 +58,9 @@ for out in sys.argv[4:]:
 PY
 # bench.py reads profiles/traffic_latest.json and reports it only while the kernel sources still hash to the recorded value
 
-# 3. the headline bench line (includes the cpu_baseline leg)
+# 3. the headline bench line (with --full: includes the secondary and cpu_baseline legs)
 if [ "$LAT" = "16" ]; then
-  timeout -k 10 600 python bench.py --steps 3 --warmup 1 > "$OUT/bench_1gpu.json.log" 2> "$OUT/bench_1gpu.stderr"
+  timeout -k 10 600 python bench.py --steps 3 --warmup 1 --full > "$OUT/bench_1gpu.json.log" 2> "$OUT/bench_1gpu.stderr"
 else
   N=1000; if [ "$KIND" = "ddim" ]; then N=250; fi
   timeout -k 10 600 python bench.py --steps 3 --warmup 1 --latent $LAT --kind $KIND --diffusion-steps $N --no-cpu-baseline > "$OUT/bench_1gpu.json.log" 2> "$OUT/bench_1gpu.stderr"
