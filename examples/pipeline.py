@@ -9,6 +9,8 @@
 
     python examples/pipeline.py [--batch 8] [--scheduler ddim|dpmpp2m] [--steps 50] [--strength 0.6]
     python examples/pipeline.py --stream 200 [--refill-every 5] [--batch 64]    # continuous batching of 200 requests, mixed strengths
+    python examples/pipeline.py --mask-box 32,40,96,72 --mask-box 48,84,80,108 [--strength 0.8]   # inpainting: resample the boxes (pixels of
+                                                          # the 128 x 128 face), keep the coarse restoration everywhere else
 """
 import argparse
 import os
@@ -36,7 +38,13 @@ def main():
                     help="continuous batching: N synthetic requests with strengths in [0.2, 1.0] through sampling.ContinuousSampler "
                          "(--batch slots), then VAE decode")
     ap.add_argument("--refill-every", type=int, default=5, metavar="K", help="--stream: iterations per call between refills")
+    ap.add_argument("--mask-box", action="append", default=None, metavar="x0,y0,x1,y1",
+                    help="inpainting: resample this pixel box of the 128 x 128 face and keep cr_latent elsewhere (repeatable; composes with "
+                         "--strength, --scheduler and --stream)")
     a = ap.parse_args()
+    a.mask = None
+    if a.mask_box:
+        a.mask = sampling.region_mask([tuple(int(v) for v in b.split(",")) for b in a.mask_box], 16)
     torch.set_grad_enabled(False)
     dev = torch.device("cuda", 0)
 
@@ -70,7 +78,11 @@ def main():
     cr_latent = vae.encode_scaled(cr_face, 128, seed=7)                # bicubic (identity at 128) + encode + sample + x 0.18215
     torch.cuda.synchronize(); t2 = time.time()
     sch.set_timesteps(steps)
-    if a.strength is None:
+    if a.mask is not None:                                             # inpainting: the boxes are resampled, the rest stays cr_latent
+        latent, start, nz = sampling.inpaint_start(sch, cr_latent, 1.0 if a.strength is None else a.strength, noise=latent)
+        out = sampling.sample(model, latent, cr_face, cr_latent, sch, start_steps=start, mask=a.mask[None].expand(B, 16, 16),
+                              known=cr_latent, known_noise=nz)
+    elif a.strength is None:
         out = sampling.sample(model, latent, cr_face, cr_latent, sch)  # conditioning once + graph-replayed loop
     else:                                                              # img2img: noise cr_latent to timesteps[start], run the remaining rows
         latent, start = sampling.img2img_start(sch, cr_latent, a.strength, noise=latent)
@@ -100,7 +112,7 @@ def stream(a, cr, vae, model, sch, steps, dev):
     sch.set_timesteps(steps)
     cs = sampling.ContinuousSampler(model, sch, batch=a.batch, refill_every=a.refill_every)
     torch.cuda.synchronize(); t1 = time.time()
-    ids = [cs.submit(f, l, seed=1000 + i, strength=strength[i]) for i, (f, l) in enumerate(reqs)]
+    ids = [cs.submit(f, l, seed=1000 + i, strength=strength[i], mask=a.mask) for i, (f, l) in enumerate(reqs)]
     out = cs.drain()
     torch.cuda.synchronize(); t2 = time.time()
     lat = torch.stack([out[i] for i in ids])

@@ -220,6 +220,14 @@ struct hd_ctx {
     unsigned long long* seeds_dev = nullptr;
     int* first_dev = nullptr;
     int faces_cap = 0;
+    // masked sampling (hd_mask_faces): the batch's masks [B,L,L], known latents and their noise [B,4,L,L], the per-face flags and the slot
+    // list of a call (sized like rows_dev, read through StepState: no graph holds these pointers).  mask_face: the host's copy of the flags
+    // ([B], empty: none set) -- sample_impl hands the buffers to StepState only while a face is masked.  Masks outlive hd_sample* calls;
+    // every hd_prepare* clears them all, hd_prepare_slots those of the slots it refills.
+    float *mask_dev = nullptr, *mask_known_dev = nullptr, *mask_noise_dev = nullptr;
+    int *mask_on_dev = nullptr, *mask_slots_dev = nullptr;
+    int mask_cap = 0;
+    std::vector<char> mask_face;
     int graph_captures = 0;                   // step-graph instantiations of this context (hd_get_option "graph_captures")
     // persistent-stage launches recorded by the last one-step capture of each form (hd_get_option "sample_stage_launches",
     // "sample_face_stage_launches", "rows_stage_launches"); stage_count / face_stage_count count while a capture runs

@@ -27,6 +27,12 @@ struct StepState {
     // row k, element e of the face is Philox(face_seeds[f]; k, e) -- and [B_chain] first-order flags that replace hist_first per face.
     const unsigned long long* face_seeds;
     const int* face_first;
+    // masked sampling (hd_mask_faces; NULL while no face of the batch has a mask): this chain's [B_chain,L,L] masks m in [0,1] (1: resample,
+    // 0: keep), the [B_chain,4,L,L] known latents and their fixed noise, and [B_chain] flags -- only a face whose flag is set is blended
+    const float* mask;
+    const float* mask_known;
+    const float* mask_noise;
+    const int* mask_on;
 };
 
 // ----------------------------------------------------------------------------------- weight packing
@@ -184,10 +190,14 @@ __device__ __forceinline__ int st_row(const StepState* st, int f) { return ((con
 __device__ __forceinline__ bool st_first(const StepState* st, int f, int k, int r) {
     return k == r && (st->face_first ? ((const __attribute__((address_space(1))) int*)st->face_first)[f] != 0 : st->hist_first != 0);
 }
-// PF: f is the chain-local face and ef the element's index inside the face (the per-face Philox key's counter, hd_sample_faces*)
+// f is the chain-local face and ef the element's index inside the face (PF: the per-face Philox key's counter, hd_sample_faces*)
+// Masked faces (st->mask != NULL and mask_on[f], hd_mask_faces; ll = L*L): the inpainting blend of the updated value r with the known latent
+// re-noised to the next row, x <- m*r + (1 - m)*(b0*known + b1*nz), (b0, b1) = (c1, c0) of row step + 1 -- the row's signal and noise scale
+// -- and (1, 0) on the last row.  In this order m == 1 gives r and m == 0 gives kn exactly, contracted or not.  The history keeps the
+// unblended x0.  f is uniform over the wave (a run lies in one face), so the branch is too.
 template <bool PF = false>
 __device__ __forceinline__ float sched_update(float xv, float e, const float* c, const StepState* st, int step, size_t gi, int n_total,
-                                             size_t li, bool first = false, int f = 0, unsigned ef = 0) {
+                                             size_t li, bool first, int f, unsigned ef, int ll) {
     float x0 = (xv - c[0] * e) / c[1];
     x0 = fminf(fmaxf(x0, -c[2]), c[2]);
     float c3 = c[3];
@@ -209,6 +219,14 @@ __device__ __forceinline__ float sched_update(float xv, float e, const float* c,
         if (PF && first) c7 = 0.f;
         if (c7 != 0.f) r += c7 * h[li];
         h[li] = x0;
+    }
+    if (st->mask && ((const __attribute__((address_space(1))) int*)st->mask_on)[f] != 0) {
+        const bool last = step + 1 >= st->n_steps;
+        const float b0 = last ? 1.f : c[7 + 1], b1 = last ? 0.f : c[7 + 0];
+        const float m = ((const __attribute__((address_space(1))) float*)st->mask)[(size_t)f * ll + (ef & (unsigned)(ll - 1))];
+        const float kn = b0 * ((const __attribute__((address_space(1))) float*)st->mask_known)[li] +
+                         b1 * ((const __attribute__((address_space(1))) float*)st->mask_noise)[li];
+        r = m * r + (1.f - m) * kn;
     }
     return r;
 }
@@ -319,9 +337,10 @@ __global__ __launch_bounds__(256) void ending_conv_kernel(const float* __restric
             const int r = st_row(sa.st, bb), k = r + step;          // the wave's run lies in one face: k is wave-uniform
             if (k < sa.st->n_steps)
                 sa.lat[o] = sched_update<true>(sa.lat[o], e, sa.coef + (size_t)k * 7, sa.st, k, (size_t)sa.elem0 + o, sa.n_total, o,
-                                               st_first(sa.st, bb, k, r), bb, (unsigned)(o - (size_t)bb * 4 * L * L));
+                                               st_first(sa.st, bb, k, r), bb, (unsigned)(o - (size_t)bb * 4 * L * L), L * L);
         } else {
-            sa.lat[o] = sched_update(sa.lat[o], e, sa.coef + (size_t)step * 7, sa.st, step, (size_t)sa.elem0 + o, sa.n_total, o);
+            sa.lat[o] = sched_update(sa.lat[o], e, sa.coef + (size_t)step * 7, sa.st, step, (size_t)sa.elem0 + o, sa.n_total, o, false, bb,
+                                     (unsigned)(o - (size_t)bb * 4 * L * L), L * L);
         }
     }
 }
@@ -334,6 +353,26 @@ static __global__ void film_rows_gather_kernel(float* __restrict__ film_pf, cons
     const float4* src = reinterpret_cast<const float4*>(film_table + (size_t)row * film_total);
     float4* dst = reinterpret_cast<float4*>(film_pf + (size_t)f * film_total);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < film_total / 4; i += gridDim.x * blockDim.x) dst[i] = src[i];
+}
+
+// hd_mask_faces: face j (< n = gridDim.y) of mask [n,L,L] / known / noise [n,4,L,L] goes to slot slots[j] (slots == NULL: j) of the batch's
+// mask buffers and the slot's flag is set; mask == NULL clears the flag and leaves the buffers.  ll = L*L.
+struct MaskScatterP {
+    const float *mask, *known, *noise;
+    float *dmask, *dknown, *dnoise;
+    int* on;
+    const int* slots;
+    int ll;
+};
+static __global__ void mask_scatter_kernel(const MaskScatterP p) {
+    const int j = blockIdx.y, slot = p.slots ? p.slots[j] : j;
+    if (blockIdx.x == 0 && threadIdx.x == 0) p.on[slot] = p.mask ? 1 : 0;
+    if (!p.mask) return;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < 4 * p.ll; i += gridDim.x * blockDim.x) {
+        if (i < p.ll) p.dmask[(size_t)slot * p.ll + i] = p.mask[(size_t)j * p.ll + i];
+        p.dknown[(size_t)slot * 4 * p.ll + i] = p.known[(size_t)j * 4 * p.ll + i];
+        p.dnoise[(size_t)slot * 4 * p.ll + i] = p.noise[(size_t)j * 4 * p.ll + i];
+    }
 }
 
 // hd_prepare_slots: copy face j (< n) of the n-face conditioning (the staging chain's buffers: 5 priors NHWC, 5 w_c, 5 w_s, the idc term and

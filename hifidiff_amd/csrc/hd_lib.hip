@@ -926,15 +926,28 @@ static int prepare_common(hd_ctx* c, int batch) {
     return alloc_workspace(c, batch);
 }
 
+static int masked_faces(const hd_ctx* c) {
+    int n = 0;
+    for (char m : c->mask_face) n += m != 0;
+    return n;
+}
+// every hd_prepare*: the new batch has no masks
+static int clear_masks(hd_ctx* c, hipStream_t s) {
+    if (masked_faces(c) > 0) HIPCHECK(c, hipMemsetAsync(c->mask_on_dev, 0, (size_t)c->mask_cap * sizeof(int), s));
+    c->mask_face.clear();
+    return HD_OK;
+}
+
 #define HD_NEED_CONDITIONAL(c, what) \
     do { if ((c) && !(c)->conditional) HD_FAIL(c, HD_ERR_INVALID, what ": this context holds the unconditional Denoiser or CoarseRestoration (no priors / identity)"); } while (0)
 
 // Unconditional Denoiser: nothing to condition on -- size the workspace for `batch` faces and build the launch program.
 int hd_prepare_unconditional(hd_ctx* c, int batch, void* stream) {
-    (void)stream;
     if (c && c->cr) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_unconditional: this context holds CoarseRestoration");
     if (c && c->conditional) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_unconditional: this context holds the conditional FusedDenoiser");
     int rc = prepare_common(c, batch);
+    if (rc) return rc;
+    rc = clear_masks(c, reinterpret_cast<hipStream_t>(stream));
     if (rc) return rc;
     c->prepared = true;
     c->hist_valid = false;                               // a new batch: no multistep history to resume
@@ -962,6 +975,8 @@ int hd_prepare(hd_ctx* c, int batch, const float* cr_latent, const float* cr_fac
         if (rc) break;
     }
     c->ch = &c->chains[0];
+    if (rc) return rc;
+    rc = clear_masks(c, s);
     if (rc) return rc;
     c->prepared = true;
     c->hist_valid = false;                               // a new batch: no multistep history to resume
@@ -993,6 +1008,8 @@ int hd_prepare_from_priors(hd_ctx* c, int batch, const float* const priors[5], c
         if (rc) break;
     }
     c->ch = &c->chains[0];
+    if (rc) return rc;
+    rc = clear_masks(c, s);
     if (rc) return rc;
     c->prepared = true;
     c->hist_valid = false;                               // a new batch: no multistep history to resume
@@ -1109,6 +1126,7 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
     HIPCHECK(c, hipSetDevice(c->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool ms = ncoef == 8, pf = rows != nullptr;
+    const bool mk = c->mask_face.size() == (size_t)c->B && masked_faces(c) > 0;   // a face carries a mask (hd_mask_faces)
     if (!pf) n_iters = n;
     int rc = ensure_film_rows(c, n);
     if (rc) return rc;
@@ -1154,14 +1172,14 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
     // schedule and loop state (step = -1: each chain's intro kernel pre-increments) go through a pinned staging buffer of
     // the context, so the caller's host arrays are free on return and nothing here waits for the stream.
     // Layout: coef [n][7] | timesteps [n] | StepState (single-step), or coef | timesteps | c7 [n] | one StepState per chain
-    // (multistep or per-face rows) | start rows [B] (per-face rows) | Philox keys [B] (2 words each) | first-order flags [B] (per-face keys /
+    // (multistep, per-face rows or masks) | start rows [B] (per-face rows) | Philox keys [B] (2 words each) | first-order flags [B] (per-face keys /
     // flags).
     StepState st{};
     st.step = -1; st.n_steps = n; st.noise = noise; st.seed = seed;
     {
         auto& sg = c->stage[c->stage_idx ^= 1];
         const size_t st_f = (sizeof(StepState) + 3) / 4, st0 = (size_t)n * (ms ? 9 : 8);
-        const size_t nst = (ms || pf) ? c->chains.size() : 1, rows0 = st0 + st_f * nst;
+        const size_t nst = (ms || pf || mk) ? c->chains.size() : 1, rows0 = st0 + st_f * nst;
         const size_t seeds0 = rows0 + (pf ? (size_t)c->B : 0), first0 = seeds0 + (face_seeds ? 2 * (size_t)c->B : 0);
         const size_t need = first0 + (first ? (size_t)c->B : 0);
         if (sg.pending) { HIPCHECK(c, hipEventSynchronize(sg.ev)); sg.pending = false; }     // the copy issued two calls ago
@@ -1188,6 +1206,11 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
             if (pf) st.start_rows = c->rows_dev + c->chains[k].face0;
             if (face_seeds) st.face_seeds = c->seeds_dev + c->chains[k].face0;
             if (first) st.face_first = c->first_dev + c->chains[k].face0;
+            if (mk) {
+                const size_t f0 = (size_t)c->chains[k].face0, ll = (size_t)c->L * c->L;
+                st.mask = c->mask_dev + f0 * ll; st.mask_known = c->mask_known_dev + f0 * 4 * ll;
+                st.mask_noise = c->mask_noise_dev + f0 * 4 * ll; st.mask_on = c->mask_on_dev + f0;
+            }
             memcpy(sg.host + st0 + k * st_f, &st, sizeof(st));
         }
         if (pf) {
@@ -1486,10 +1509,87 @@ int hd_prepare_slots(hd_ctx* c, int n, const int32_t* slots, const float* cr_lat
     p.slots = c->slots_dev; p.faces_per_chain = c->chains[0].B;
     hipLaunchKernelGGL(slot_scatter_kernel, dim3(32, n, kSlotBufs), dim3(256), 0, s, p);
     HIPCHECK(c, hipGetLastError());
+    // the refilled faces carry no mask (their flags are cleared in stream order; the slot list is on the device already)
+    if (c->mask_face.size() == (size_t)c->B) {
+        bool any = false;
+        for (int j = 0; j < n; ++j) { any |= c->mask_face[slots[j]] != 0; c->mask_face[slots[j]] = 0; }
+        if (any) {
+            MaskScatterP mp{};
+            mp.on = c->mask_on_dev; mp.slots = c->slots_dev; mp.ll = c->L * c->L;
+            hipLaunchKernelGGL(mask_scatter_kernel, dim3(1, n), dim3(64), 0, s, mp);
+            HIPCHECK(c, hipGetLastError());
+        }
+    }
     // the refilled faces have no multistep history; hd_sample_rows_multistep(resume = 1) no longer continues the whole batch
     if (c->hist_B == c->B && c->hist_face.size() == (size_t)c->B)
         for (int j = 0; j < n; ++j) c->hist_face[slots[j]] = 0;
     c->hist_valid = false;
+    return HD_OK;
+}
+
+// Give n faces of the prepared batch a mask, the known latent and its noise (or take their masks away: all three NULL).  The tensors are
+// copied in stream order into buffers of the context that the step kernels reach through StepState: no launch program is rebuilt and no
+// graph recaptured, and while no face is masked the loop's launches read nothing of this.
+int hd_mask_faces(hd_ctx* c, int n, const int32_t* slots, const float* mask, const float* known, const float* known_noise, void* stream) {
+    if (!c) return HD_ERR_INVALID;
+    if (c->cr || c->vae) HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: this context holds CoarseRestoration or the VAE (no sampling loop)");
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    if (n < 1 || n > c->B) HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: n = %d outside [1, %d]", n, c->B);
+    if (!slots && n != c->B) HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: slots == NULL needs n == batch (%d), got %d", c->B, n);
+    if ((!mask != !known) || (!mask != !known_noise))
+        HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: give mask, known and known_noise together, or none of them (clear)");
+    if (slots) {
+        std::vector<char> seen((size_t)c->B, 0);
+        for (int j = 0; j < n; ++j) {
+            if (slots[j] < 0 || slots[j] >= c->B) HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: slots[%d] = %d outside [0, %d)", j, slots[j], c->B);
+            if (seen[slots[j]]) HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: slot %d given twice", slots[j]);
+            seen[slots[j]] = 1;
+        }
+    }
+    if (c->mask_face.size() != (size_t)c->B) c->mask_face.assign((size_t)c->B, 0);
+    if (!mask && masked_faces(c) == 0) return HD_OK;       // nothing to clear
+    HIPCHECK(c, hipSetDevice(c->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const size_t ll = (size_t)c->L * c->L;
+    if (c->B > c->mask_cap) {                              // a larger batch than ever masked: hd_prepare* has cleared every mask since
+        dev_free(c, c->mask_dev); dev_free(c, c->mask_known_dev); dev_free(c, c->mask_noise_dev);
+        dev_free(c, c->mask_on_dev); dev_free(c, c->mask_slots_dev);
+        c->mask_dev = c->mask_known_dev = c->mask_noise_dev = nullptr; c->mask_on_dev = c->mask_slots_dev = nullptr; c->mask_cap = 0;
+        rc = dev_alloc(c, &c->mask_dev, (size_t)c->B * ll);
+        if (!rc) rc = dev_alloc(c, &c->mask_known_dev, (size_t)c->B * 4 * ll);
+        if (!rc) rc = dev_alloc(c, &c->mask_noise_dev, (size_t)c->B * 4 * ll);
+        if (!rc) rc = dev_alloc(c, &c->mask_on_dev, (size_t)c->B);
+        if (!rc) rc = dev_alloc(c, &c->mask_slots_dev, (size_t)c->B);
+        if (rc) return rc;
+        c->mask_cap = c->B;
+        HIPCHECK(c, hipMemsetAsync(c->mask_dev, 0, (size_t)c->B * ll * sizeof(float), s));
+        HIPCHECK(c, hipMemsetAsync(c->mask_known_dev, 0, (size_t)c->B * 4 * ll * sizeof(float), s));
+        HIPCHECK(c, hipMemsetAsync(c->mask_noise_dev, 0, (size_t)c->B * 4 * ll * sizeof(float), s));
+        HIPCHECK(c, hipMemsetAsync(c->mask_on_dev, 0, (size_t)c->B * sizeof(int), s));
+    }
+    if (slots) {                                           // through the pinned staging buffer, as hd_prepare_slots does
+        auto& sg = c->stage[c->stage_idx ^= 1];
+        if (sg.pending) { HIPCHECK(c, hipEventSynchronize(sg.ev)); sg.pending = false; }
+        if (sg.cap < (size_t)n) {
+            if (sg.host) (void)hipHostFree(sg.host);
+            sg.host = nullptr; sg.cap = 0;
+            HIPCHECK(c, hipHostMalloc(reinterpret_cast<void**>(&sg.host), (size_t)n * sizeof(float), hipHostMallocDefault));
+            sg.cap = n;
+        }
+        if (!sg.ev) HIPCHECK(c, hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
+        memcpy(sg.host, slots, (size_t)n * sizeof(int32_t));
+        HIPCHECK(c, hipMemcpyAsync(c->mask_slots_dev, sg.host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIPCHECK(c, hipEventRecord(sg.ev, s));
+        sg.pending = true;
+    }
+    MaskScatterP p{};
+    p.mask = mask; p.known = known; p.noise = known_noise;
+    p.dmask = c->mask_dev; p.dknown = c->mask_known_dev; p.dnoise = c->mask_noise_dev;
+    p.on = c->mask_on_dev; p.slots = slots ? c->mask_slots_dev : nullptr; p.ll = (int)ll;
+    hipLaunchKernelGGL(mask_scatter_kernel, dim3(mask ? 4 : 1, n), dim3(256), 0, s, p);
+    HIPCHECK(c, hipGetLastError());
+    for (int j = 0; j < n; ++j) c->mask_face[slots ? slots[j] : j] = mask ? 1 : 0;
     return HD_OK;
 }
 
@@ -1535,6 +1635,15 @@ int64_t hd_debug_read_op(hd_ctx* c, int which, int i, float* host_out, int64_t m
 
 int64_t hd_debug_read(hd_ctx* c, const char* name, float* host_out, int64_t max_elems) {
     if (!c || !name) return HD_ERR_INVALID;
+    {                                                      // the mask buffers belong to the context, not to a workspace: sized by the batch in use
+        const std::string k = name;
+        const bool m = k == "mask", mkn = k == "mask_known", mnz = k == "mask_noise";
+        if (m || mkn || mnz) {
+            if (!c->mask_dev || c->B < 1 || c->B > c->mask_cap) HD_FAIL(c, HD_ERR_INVALID, "debug buffer %s: no mask has been set for this batch", name);
+            const size_t ll = (size_t)c->L * c->L;
+            return read_to_host(c, m ? c->mask_dev : mkn ? c->mask_known_dev : c->mask_noise_dev, (size_t)c->B * (m ? ll : 4 * ll), 0, host_out, max_elems);
+        }
+    }
     auto it = c->dbg.find(name);
     if (it == c->dbg.end()) HD_FAIL(c, HD_ERR_INVALID, "unknown debug buffer %s", name);
     return read_to_host(c, it->second.first, it->second.second.first, it->second.second.second, host_out, max_elems);
@@ -1592,6 +1701,7 @@ int hd_get_option(hd_ctx* c, const char* key) {
     if (k == "sample_stage_launches") return c->sample_stages;
     if (k == "sample_face_stage_launches") return c->sample_face_stages;
     if (k == "rows_stage_launches") return c->rows_stages;
+    if (k == "masked_faces") return c->mask_face.size() == (size_t)c->B ? masked_faces(c) : 0;   // faces that carry a mask (hd_mask_faces)
     if (k == "graph_captures") return c->graph_captures;         // step graphs instantiated by this context (hd_prepare_slots adds none)
     // the folds of the program built for the batch in use (0 before the first call): the decisions build_denoiser_program made, and
     // whether the launch that carries them still runs -- the face-stage entries need the face stages on and a single chain

@@ -76,6 +76,27 @@ def slots_arg(slots, batch):
     return t.to(torch.int32).contiguous()
 
 
+def mask_args(mask, known, noise, n, L):
+    """Argument checks of set_mask, before any device work: mask [n,L,L] or [n,1,L,L], finite and in [0, 1]; known and noise [n,4,L,L].
+    Returns the three as fp32 tensors ([n,L,L], [n,4,L,L], [n,4,L,L]) on the devices they came from; ValueError otherwise."""
+    if mask is None or known is None or noise is None:
+        raise ValueError("a mask needs all of mask, known and noise (clear_mask() removes a mask)")
+    mask, known, noise = torch.as_tensor(mask), torch.as_tensor(known), torch.as_tensor(noise)
+    if mask.dim() == 4 and mask.shape[1] == 1:
+        mask = mask[:, 0]
+    if tuple(mask.shape) != (n, L, L):
+        raise ValueError("mask must be (%d,%d,%d) or (%d,1,%d,%d), got %s" % (n, L, L, n, L, L, tuple(mask.shape)))
+    for name, t in (("known", known), ("noise", noise)):
+        if tuple(t.shape) != (n, 4, L, L):
+            raise ValueError("%s must be (%d,4,%d,%d), got %s" % (name, n, L, L, tuple(t.shape)))
+    mask = mask.to(torch.float32)
+    if not bool(torch.isfinite(mask).all()):
+        raise ValueError("mask must be finite")
+    if bool(((mask < 0) | (mask > 1)).any()):
+        raise ValueError("mask must lie in [0, 1] (1: resample, 0: keep)")
+    return mask, known.to(torch.float32), noise.to(torch.float32)
+
+
 class _Engine:
     """Owns the hd_ctx of one (latent_res, device)."""
 
@@ -212,6 +233,32 @@ class _Engine:
                                                    crf.data_ptr() if crf is not None else None, emb.data_ptr() if emb is not None else None,
                                                    _stream(self.device)), self.ctx)
         self.cond_key, self.prior_key = None, None         # the batch no longer matches any one pair of tensors
+
+    def set_mask(self, mask, known, noise, slots=None):
+        """hd_mask_faces: the faces in `slots` (None: the whole prepared batch, in order) are inpainted from now on -- mask 1 resamples,
+        0 keeps `known`, re-noised with `noise` to the row the loop is at.  Stays until clear_mask, a new prepare, or (per slot)
+        prepare_slots."""
+        if self.batch is None:                             # the argument errors come first
+            mask_args(mask, known, noise, torch.as_tensor(mask).shape[0] if mask is not None else 0, self.latent_res)
+            raise RuntimeError("no batch is prepared: prepare the batch before giving it a mask")
+        sl = None if slots is None else slots_arg(slots, self.batch)
+        n = self.batch if sl is None else sl.numel()
+        m, k, z = mask_args(mask, known, noise, n, self.latent_res)
+        self.require_loaded()
+        m, k, z = _f32c(m, self.device), _f32c(k, self.device), _f32c(z, self.device)
+        sp = None if sl is None else ctypes.cast(sl.data_ptr(), ctypes.POINTER(ctypes.c_int32))
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().hd_mask_faces(self.ctx, n, sp, m.data_ptr(), k.data_ptr(), z.data_ptr(), _stream(self.device)), self.ctx)
+
+    def clear_mask(self, slots=None):
+        """Take the masks of the faces in `slots` (None: of every face) away; a no-op without a prepared batch."""
+        if self.batch is None or self.ctx is None:
+            return
+        sl = None if slots is None else slots_arg(slots, self.batch)
+        n = self.batch if sl is None else sl.numel()
+        sp = None if sl is None else ctypes.cast(sl.data_ptr(), ctypes.POINTER(ctypes.c_int32))
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().hd_mask_faces(self.ctx, n, sp, None, None, None, _stream(self.device)), self.ctx)
 
     def prepare_unconditional(self, batch):
         self.require_loaded()
@@ -400,6 +447,17 @@ class Denoiser(nn.Module):
         """Synchronise and raise RuntimeError if a call since the last check handed back NaN-poisoned results (_Engine.check)."""
         self._engine.check(synchronize)
 
+    def set_mask(self, mask, known, noise, slots=None):
+        """Inpainting: give the prepared batch's faces in `slots` (None: all, in order) a mask [n,L,L] or [n,1,L,L] in [0, 1] (1: resample,
+        0: keep), the known latents [n,4,L,L] and their fixed noise [n,4,L,L] (sampling.inpaint_start returns it).  Every following
+        sampling.sample call blends the kept region back after each step; the masks stay until clear_mask, the next prepare of a batch,
+        or prepare_slots of their slot.  ValueError for wrong shapes or a mask outside [0, 1]."""
+        self._engine.set_mask(mask, known, noise, slots)
+
+    def clear_mask(self, slots=None):
+        """Remove the masks of the faces in `slots` (None: of every face)."""
+        self._engine.clear_mask(slots)
+
     def forward(self, latents, timesteps):
         e = self._engine
         e.ensure(latents.device)
@@ -487,6 +545,17 @@ class FacialRefiner(nn.Module):
         if not e.conditional:
             raise RuntimeError("prepare_slots needs the conditional refiner")
         e.prepare_slots(slots, cr_latent, cr_face=cr_face)
+
+    def set_mask(self, mask, known, noise, slots=None):
+        """Inpainting: give the prepared batch's faces in `slots` (None: all, in order) a mask [n,L,L] or [n,1,L,L] in [0, 1] (1: resample,
+        0: keep), the known latents [n,4,L,L] and their fixed noise [n,4,L,L] (sampling.inpaint_start returns it).  Every following
+        sampling.sample call blends the kept region back after each step; the masks stay until clear_mask, the next prepare of a batch,
+        or prepare_slots of their slot.  ValueError for wrong shapes or a mask outside [0, 1]."""
+        self._engine.set_mask(mask, known, noise, slots)
+
+    def clear_mask(self, slots=None):
+        """Remove the masks of the faces in `slots` (None: of every face)."""
+        self._engine.clear_mask(slots)
 
     def invalidate_conditioning(self):
         """Forget the cached conditioning (after writing into cr_face / cr_latent through `.data`, numpy or a DLPack alias,

@@ -70,9 +70,58 @@ def img2img_start(scheduler, cr_latent, strength, noise=None, generator=None):
     return latents, start
 
 
+def inpaint_start(scheduler, known, strength=1.0, noise=None, generator=None):
+    """diffusers' inpaint start: returns (latents, start_steps, noise).  A face of strength 1 (`is_strength_max`) starts from the pure
+    noise at row 0; otherwise this is img2img_start(scheduler, known, strength, noise): face f starts at row n - min(int(n * s_f), n) from
+    add_noise(known_f, noise_f, timesteps[start_f]).  The returned noise is the `known_noise` of sample(mask=...) / set_mask: the one fixed
+    noise tensor the kept region is re-noised with after every step."""
+    B = known.shape[0]
+    s = torch.as_tensor(strength, dtype=torch.float64).flatten().cpu()
+    if s.numel() not in (1, B):
+        raise ValueError(f"strength must be a float or a [{B}] tensor")
+    if bool(((s < 0) | (s > 1)).any()):
+        raise ValueError("strength must lie in [0, 1]")
+    if noise is None:
+        noise = torch.randn(known.shape, generator=generator, dtype=known.dtype,
+                            device=generator.device if generator is not None else known.device)
+    noise = noise.to(device=known.device, dtype=known.dtype)
+    latents, start = img2img_start(scheduler, known, strength, noise=noise)
+    full = (s.expand(B) if s.numel() == 1 else s) == 1
+    if bool(full.any()):                                   # strength 1: the noise itself, not add_noise(known, noise, timesteps[0])
+        idx = full.nonzero().flatten().to(known.device)
+        latents[idx] = noise[idx]
+    return latents, start, noise
+
+
+def region_mask(boxes, latent_res, image_res=128, feather=0):
+    """Latent mask [latent_res, latent_res] (fp32, CPU) of pixel boxes (x0, y0, x1, y1), half-open, in an image_res x image_res image: every
+    latent pixel gets the fraction of its (image_res / latent_res)^2 pixel cell that the union of the boxes covers (1: resample).
+    feather > 0: a box blur of (2 * feather + 1)^2 latent pixels with zero padding, so the values stay in [0, 1].  Host-only torch."""
+    L, R = int(latent_res), int(image_res)
+    if L < 1 or R % L != 0:
+        raise ValueError("image_res must be a multiple of latent_res")
+    cell = R // L
+    px = torch.zeros((R, R), dtype=torch.float64)
+    for b in boxes:
+        if len(b) != 4:
+            raise ValueError("a box is (x0, y0, x1, y1)")
+        x0, y0, x1, y1 = (int(v) for v in b)
+        if not (0 <= x0 <= x1 <= R and 0 <= y0 <= y1 <= R):
+            raise ValueError(f"box {tuple(b)} must satisfy 0 <= x0 <= x1 <= {R} and 0 <= y0 <= y1 <= {R}")
+        px[y0:y1, x0:x1] = 1.0
+    m = px.reshape(L, cell, L, cell).mean(dim=(1, 3))
+    f = int(feather)
+    if f < 0:
+        raise ValueError("feather must be >= 0")
+    if f > 0:
+        k = 2 * f + 1
+        m = torch.nn.functional.avg_pool2d(m[None, None], k, stride=1, padding=f, count_include_pad=True)[0, 0]
+    return m.clamp(0.0, 1.0).to(torch.float32)
+
+
 @torch.no_grad()
 def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, prepare=True, check=True,
-           start_steps=None, n_iters=None, resume=False, face_seeds=None):
+           start_steps=None, n_iters=None, resume=False, face_seeds=None, mask=None, known=None, known_noise=None):
     """Whole loop on the GPU: returns the final latents (a new tensor).
 
     The scheduler's coefficient table picks the entry point: 7 columns (DDIM / DDPM) -> hd_sample, 8 columns
@@ -90,6 +139,11 @@ def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, pr
     [B] bool tensor (multistep): True continues that face's history, False takes its first row first-order (a slot refilled by
     FacialRefiner.prepare_slots).  Either one dispatches to hd_sample_faces / hd_sample_faces_multistep (start_steps default 0).
     For the unconditional `Denoiser` pass cr_face = cr_latent = None.
+    mask / known / known_noise (inpainting; all three or none): [B,L,L] or [B,1,L,L] in [0, 1] (1: resample, 0: keep), [B,4,L,L] and
+    [B,4,L,L] (inpaint_start): set on the engine after preparing (model.set_mask), so after every step the kept region is `known`
+    re-noised to the next row, and exactly `known` after the last.  mask=None with prepare=True removes any mask the engine still holds
+    (the conditioning cache can hit without a new prepare); with prepare=False the engine's masks are left alone (continuous batching,
+    a loop split over calls).
     check=True (the default): ONE stream synchronisation after the whole loop (not per step), then RuntimeError if a persistent
     stage launch gave up during it -- where the reference's loop would have raised (test_refiner.py:89-91), so that the last batch
     of a val_loop cannot end with rc 0 and NaN images.  check=False only enqueues the work (the returned latents are NaN in the
@@ -98,6 +152,11 @@ def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, pr
         face_seeds = face_seeds_arg(face_seeds, latents.shape[0])
     if isinstance(resume, torch.Tensor):
         resume = resume_arg(resume, latents.shape[0])
+    if mask is None and (known is not None or known_noise is not None):
+        raise ValueError("known / known_noise need a mask")
+    if mask is not None:
+        from .refiner import mask_args
+        mask, known, known_noise = mask_args(mask, known, known_noise, latents.shape[0], model.engine.latent_res)
     e = model.engine
     e.ensure(latents.device)
     if latents.shape[0] == 0:                              # empty batch: nothing to sample
@@ -110,6 +169,10 @@ def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, pr
     elif prepare:
         model.prepare(cr_face, cr_latent)
     e.require_loaded()
+    if mask is not None:
+        e.set_mask(mask, known, known_noise)
+    elif prepare:
+        e.clear_mask()
     x = latents.to(device=e.device, dtype=torch.float32).contiguous().clone()
     ts, coef = scheduler.coefficient_table()
     ts, coef = ts.contiguous(), coef.contiguous()
@@ -315,7 +378,7 @@ class ContinuousSampler:
         self.L = model.engine.latent_res
         self.n_steps = int(scheduler.timesteps.numel())
         self.table = SlotTable(self.batch, self.n_steps)
-        self.queue = []                 # (rid, cr_face, cr_latent, seed, strength) in submission order
+        self.queue = []                 # (rid, cr_face, cr_latent, seed, strength, mask) in submission order
         self.finished = {}
         self.seeds = [0] * self.batch
         self.x = None                   # [B,4,L,L] device latents of every slot
@@ -324,8 +387,19 @@ class ContinuousSampler:
         self.calls = 0
         self.refilled = 0
 
-    def submit(self, cr_face, cr_latent, seed, strength=1.0):
+    def submit(self, cr_face, cr_latent, seed, strength=1.0, mask=None):
+        """mask: None, or [L,L] / [1,L,L] in [0, 1] (1: resample): the request is inpainted -- its known latent is cr_latent, the noise of
+        the kept region the z its start is drawn from (inpaint_start; strength 1 starts from pure noise).  Masked and unmasked requests
+        share a batch."""
         L = self.L
+        if mask is not None:
+            if not self.conditional:
+                raise ValueError("a mask needs the refiner: the request's known latent is its cr_latent")
+            from .refiner import mask_args
+            mask = torch.as_tensor(mask)
+            if cr_latent is None:
+                raise ValueError("the refiner needs cr_face and cr_latent")
+            mask = mask_args(mask[None] if mask.dim() == 2 else mask, cr_latent[None], cr_latent[None], 1, L)[0][0].cpu()
         if self.conditional:
             if cr_face is None or cr_latent is None:
                 raise ValueError("the refiner needs cr_face and cr_latent")
@@ -340,27 +414,37 @@ class ContinuousSampler:
             raise ValueError("seed must lie in [0, 2**63)")
         rid = self.next_id
         self.next_id += 1
-        self.queue.append((rid, cr_face, cr_latent, seed, float(strength)))
+        self.queue.append((rid, cr_face, cr_latent, seed, float(strength), mask))
         return rid
 
-    def _start(self, cr_latent, seed, strength):
-        """(initial latents [4,L,L] on the CPU, start row) of one request: img2img_start with a CPU generator seeded by the request."""
-        g = torch.Generator().manual_seed(seed)
-        z = torch.randn((1, 4, self.L, self.L), generator=g)
+    def _z(self, seed):
+        """The request's one CPU-generator noise tensor [1,4,L,L]: its start is drawn from it, and a masked request's kept region is
+        re-noised with it."""
+        return torch.randn((1, 4, self.L, self.L), generator=torch.Generator().manual_seed(seed))
+
+    def _start(self, cr_latent, seed, strength, masked=False):
+        """(initial latents [4,L,L] on the CPU, start row) of one request: img2img_start (inpaint_start for a masked request) with a CPU
+        generator seeded by the request."""
+        z = self._z(seed)
         if cr_latent is None:
             return z[0], 0
-        lat, start = img2img_start(self.scheduler, cr_latent.detach().float().cpu()[None], strength, noise=z)
+        if masked:
+            lat, start, _ = inpaint_start(self.scheduler, cr_latent.detach().float().cpu()[None], strength, noise=z)
+        else:
+            lat, start = img2img_start(self.scheduler, cr_latent.detach().float().cpu()[None], strength, noise=z)
         return lat[0], int(start[0])
 
     def _refill(self, dev):
-        new = []
+        new, masked = [], []
         while self.queue and self.table.free_slots():
-            rid, crf, crl, seed, strength = self.queue.pop(0)
-            lat, start = self._start(crl, seed, strength)
+            rid, crf, crl, seed, strength, mask = self.queue.pop(0)
+            lat, start = self._start(crl, seed, strength, mask is not None)
             slot = self.table.assign(rid, start)
             self.seeds[slot] = seed
             self.x[slot] = lat.to(dev)
             new.append((slot, crf, crl))
+            if mask is not None:
+                masked.append((slot, mask, crl, self._z(seed)[0]))
         if not new or not self.conditional:
             return
         slots = [s for s, _, _ in new]
@@ -377,6 +461,9 @@ class ContinuousSampler:
         else:
             self.model.prepare_slots(slots, crf, crl)
             self.refilled += len(slots)
+        if masked:                      # after the prepare: it has cleared the masks of the slots it filled
+            self.model.set_mask(torch.stack([m for _, m, _, _ in masked]), torch.stack([l.detach().float().cpu() for _, _, l, _ in masked]),
+                                torch.stack([z for _, _, _, z in masked]), slots=[s for s, _, _, _ in masked])
 
     def step(self):
         """Refill free slots from the queue, then run one call of up to refill_every iterations.  Returns the number of iterations."""

@@ -181,6 +181,22 @@ int hd_sample_faces(hd_ctx* ctx, float* x_inout, const hd_schedule* sched, const
 int hd_sample_faces_multistep(hd_ctx* ctx, float* x_inout, const hd_schedule_ms* sched, const int32_t* start_rows, int n_iters,
                               const int32_t* resume, const uint64_t* face_seeds, const float* noise, uint64_t seed, void* stream);
 
+/* Masked sampling (inpainting, diffusers' inpaint loop for a 4-channel UNet with one mask per face).
+ * hd_mask_faces: give n faces of the prepared batch a mask: slots[j] (host [n], distinct, in [0, B); NULL: n == B, faces in order) gets
+ * mask[j] [L,L] in [0, 1] (1: resample, 0: keep), known[j] [4,L,L] and known_noise[j] [4,L,L] (device fp32, copied in stream order: the
+ * caller's tensors are free once the stream has passed the call).  From then on every hd_sample* call (all six loop entry points) ends the
+ * update of row k of such a face with
+ *     x <- m * r + (1 - m) * (b0 * known + b1 * known_noise),   r the scheduler update of that element,
+ * (b0, b1) = (c[1], c[0]) of row k + 1 -- the signal and noise scale of the row, scheduler.add_noise(known, known_noise, timesteps[k+1]) --
+ * and (1, 0) on the last row: the kept region ends exactly on `known`, m == 1 gives r and m == 0 the re-noised known latent bit for bit.
+ * The multistep history keeps the unblended x0; a held face is not written.  mask == known == known_noise == NULL clears the masks of the
+ * given faces.  Masks stay across hd_sample* calls (a loop split over calls keeps them); every hd_prepare* clears all of them and
+ * hd_prepare_slots those of the slots it refills.  Nothing is rebuilt or recaptured, and while no face is masked the step launches read
+ * and compute what they did without this call.  hd_eps and hd_scheduler_step* know no mask.  HD_ERR_NOT_READY without a prepared batch;
+ * HD_ERR_INVALID for a duplicate or out-of-range slot, n outside [1, B], slots == NULL with n != B, some but not all of the three
+ * pointers, or a CoarseRestoration / VAE context. */
+int hd_mask_faces(hd_ctx* ctx, int n, const int32_t* slots, const float* mask, const float* known, const float* known_noise, void* stream);
+
 /* One scheduler update on its own: `scheduler.step(eps, t, x).prev_sample` (test_refiner.py:91) in
  * the coefficient form of hd_schedule (coef7 on the host); x updated in place.  noise/seed/step as in
  * hd_sample.  Needs no context. */
@@ -213,7 +229,8 @@ int hd_debug_write(hd_ctx* ctx, const char* name, const float* host_in, int64_t 
  * placement-independent hand-off form.  hd_get_option: "xcd" (effective), "xcd_stages" (stages built so far);
  * "sample_stage_launches" / "sample_face_stage_launches" / "rows_stage_launches": persistent-stage launches (all / face-cluster only) that
  * the last one-step capture of hd_sample* / hd_sample_rows* recorded (-1 before the first capture; a stage that fell back is not counted);
- * "graph_captures": step graphs instantiated by this context so far (hd_prepare_slots adds none). */
+ * "graph_captures": step graphs instantiated by this context so far (hd_prepare_slots and hd_mask_faces add none); "masked_faces": faces
+ * of the batch that carry a mask (hd_mask_faces; hd_debug_read names "mask", "mask_known", "mask_noise" read the batch's mask buffers). */
 int hd_set_option(hd_ctx* ctx, const char* key, int value);
 int hd_get_option(hd_ctx* ctx, const char* key);
 /* Error status of the asynchronous calls.  hd_eps / hd_sample only enqueue work; a persistent stage launch that has to give
