@@ -9,6 +9,7 @@
 
     python examples/pipeline.py [--batch 8] [--scheduler ddim|dpmpp2m] [--steps 50] [--strength 0.6]
     python examples/pipeline.py --stream 200 [--refill-every 5] [--batch 64]    # continuous batching of 200 requests, mixed strengths
+    python examples/pipeline.py --stream 200 --steps-mix 10,20,50    # the requests cycle through schedules of 10, 20 and 50 steps in one batch
     python examples/pipeline.py --mask-box 32,40,96,72 --mask-box 48,84,80,108 [--strength 0.8]   # inpainting: resample the boxes (pixels of
                                                           # the 128 x 128 face), keep the coarse restoration everywhere else
 """
@@ -38,6 +39,9 @@ def main():
                     help="continuous batching: N synthetic requests with strengths in [0.2, 1.0] through sampling.ContinuousSampler "
                          "(--batch slots), then VAE decode")
     ap.add_argument("--refill-every", type=int, default=5, metavar="K", help="--stream: iterations per call between refills")
+    ap.add_argument("--steps-mix", default=None, metavar="N1,N2,..",
+                    help="--stream: per-request schedules -- the requests cycle through these step counts of --scheduler, all in the same "
+                         "slots (sampling.ScheduleSet, hd_sample_spans)")
     ap.add_argument("--mask-box", action="append", default=None, metavar="x0,y0,x1,y1",
                     help="inpainting: resample this pixel box of the 128 x 128 face and keep cr_latent elsewhere (repeatable; composes with "
                          "--strength, --scheduler and --stream)")
@@ -65,6 +69,8 @@ def main():
                                                      prediction_type="epsilon", solver_order=2, algorithm_type="dpmsolver++")
     steps = a.steps or (50 if a.scheduler == "ddim" else 20)
 
+    if a.steps_mix and a.stream is None:
+        ap.error("--steps-mix needs --stream")
     if a.stream is not None:
         return stream(a, cr, vae, model, sch, steps, dev)
 
@@ -110,9 +116,19 @@ def stream(a, cr, vae, model, sch, steps, dev):
         cr_latent = vae.encode_scaled(cr_face, 128, seed=7 + b)
         reqs += [(cr_face[i], cr_latent[i]) for i in range(n)]
     sch.set_timesteps(steps)
+    pick = [None] * N
+    if a.steps_mix:                                                    # one schedule per step count, every request on its own
+        import copy
+        counts = [int(v) for v in a.steps_mix.split(",")]
+        members = {n: copy.deepcopy(sch) for n in counts}
+        for n, s in members.items():
+            s.set_timesteps(n)
+        sch, steps = sampling.ScheduleSet(members), a.steps_mix
+        pick = [counts[i % len(counts)] for i in range(N)]
     cs = sampling.ContinuousSampler(model, sch, batch=a.batch, refill_every=a.refill_every)
     torch.cuda.synchronize(); t1 = time.time()
-    ids = [cs.submit(f, l, seed=1000 + i, strength=strength[i], mask=a.mask) for i, (f, l) in enumerate(reqs)]
+    ids = [cs.submit(f, l, seed=1000 + i, strength=strength[i], mask=a.mask, **({"schedule": pick[i]} if a.steps_mix else {}))
+           for i, (f, l) in enumerate(reqs)]
     out = cs.drain()
     torch.cuda.synchronize(); t2 = time.time()
     lat = torch.stack([out[i] for i in ids])

@@ -52,9 +52,9 @@ static __global__ __launch_bounds__(EndCfg::THREADS) void hca_ending_conv_kernel
 
     // ---- the next step's FiLM row to its fixed address (ending_conv_kernel's trailing workgroups): every workgroup moves its share ----
     if (PF && p.sa.lat) {
-        // the four workgroups of a face move its row r_f + step + 1 (while it exists: a held face keeps its last row)
+        // the four workgroups of a face move its row r_f + step + 1 (while the face's schedule has it: a held face keeps its last row)
         const int row = st_row(p.sa.st, face) + p.sa.st->step + 1;
-        if (row < p.sa.st->n_steps) {
+        if (row < st_end(p.sa.st, face)) {
             const float4* src = reinterpret_cast<const float4*>(p.sa.film_table + (size_t)row * p.sa.film_total);
             float4* dst = reinterpret_cast<float4*>(p.sa.film_cur + (size_t)face * p.sa.film_total);
             for (int i = qd * K::THREADS + tid; i < p.sa.film_total / 4; i += 4 * K::THREADS) dst[i] = src[i];
@@ -224,7 +224,7 @@ static __global__ __launch_bounds__(EndCfg::THREADS) void hca_ending_conv_kernel
         const int step = p.sa.st->step;
         if constexpr (PF) {
             const int r = st_row(p.sa.st, face), k = r + step;       // workgroup-uniform: one face
-            if (k < p.sa.st->n_steps)
+            if (k < st_end(p.sa.st, face))
                 p.sa.lat[o] = sched_update<true>(p.sa.lat[o], e, p.sa.coef + (size_t)k * 7, p.sa.st, k, (size_t)p.sa.elem0 + o, p.sa.n_total, o,
                                                  st_first(p.sa.st, face, k, r), face, (unsigned)(o - (size_t)face * 4 * S * S), S * S);
         } else {

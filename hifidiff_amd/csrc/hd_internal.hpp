@@ -220,6 +220,9 @@ struct hd_ctx {
     unsigned long long* seeds_dev = nullptr;
     int* first_dev = nullptr;
     int faces_cap = 0;
+    // per-face schedule spans of hd_sample_spans: begin rows [B] | end rows [B] (read through StepState: no graph holds this pointer)
+    int* spans_dev = nullptr;
+    int spans_cap = 0;
     // masked sampling (hd_mask_faces): the batch's masks [B,L,L], known latents and their noise [B,4,L,L], the per-face flags and the slot
     // list of a call (sized like rows_dev, read through StepState: no graph holds these pointers).  mask_face: the host's copy of the flags
     // ([B], empty: none set) -- sample_impl hands the buffers to StepState only while a face is masked.  Masks outlive hd_sample* calls;

@@ -33,6 +33,11 @@ struct StepState {
     const float* mask_known;
     const float* mask_noise;
     const int* mask_on;
+    // per-face schedule spans (hd_sample_spans; NULL: 0 and n_steps for every face): this chain's [B_chain] rows begin_f / end_f.  Face f's
+    // schedule is rows [begin_f, end_f) of the table: it is held from row end_f on, its FiLM row and its mask blend stop there, and its
+    // Philox counter is k - begin_f.  Read by the per-face launches only.
+    const int* begin_rows;
+    const int* end_rows;
 };
 
 // ----------------------------------------------------------------------------------- weight packing
@@ -186,6 +191,9 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 // first-order (h := x0, see below).  PF = false is the code of hd_sample / hd_sample_multistep.
 // face f's start row (the pointer is read from device memory: a global pointer, as in sched_update)
 __device__ __forceinline__ int st_row(const StepState* st, int f) { return ((const __attribute__((address_space(1))) int*)st->start_rows)[f]; }
+// face f's span of the table (hd_sample_spans), or the whole table: the row its noise counter starts from, and the row it is held from
+__device__ __forceinline__ int st_begin(const StepState* st, int f) { return st->begin_rows ? ((const __attribute__((address_space(1))) int*)st->begin_rows)[f] : 0; }
+__device__ __forceinline__ int st_end(const StepState* st, int f) { return st->end_rows ? ((const __attribute__((address_space(1))) int*)st->end_rows)[f] : st->n_steps; }
 // is face f's row k its first-order row: k == r_f and (per face, hd_sample_faces_multistep) face_first[f] or (hd_sample_rows*) hist_first
 __device__ __forceinline__ bool st_first(const StepState* st, int f, int k, int r) {
     return k == r && (st->face_first ? ((const __attribute__((address_space(1))) int*)st->face_first)[f] != 0 : st->hist_first != 0);
@@ -195,6 +203,8 @@ __device__ __forceinline__ bool st_first(const StepState* st, int f, int k, int 
 // re-noised to the next row, x <- m*r + (1 - m)*(b0*known + b1*nz), (b0, b1) = (c1, c0) of row step + 1 -- the row's signal and noise scale
 // -- and (1, 0) on the last row.  In this order m == 1 gives r and m == 0 gives kn exactly, contracted or not.  The history keeps the
 // unblended x0.  f is uniform over the wave (a run lies in one face), so the branch is too.
+// PF with spans (hd_sample_spans): the last row is that of the face's span (step + 1 >= end_f), and the Philox counter is the row inside the
+// span, step - begin_f -- a request's z does not depend on where its schedule sits in the table; an explicit noise tensor keeps the absolute row.
 template <bool PF = false>
 __device__ __forceinline__ float sched_update(float xv, float e, const float* c, const StepState* st, int step, size_t gi, int n_total,
                                              size_t li, bool first, int f, unsigned ef, int ll) {
@@ -209,8 +219,8 @@ __device__ __forceinline__ float sched_update(float xv, float e, const float* c,
         // (the pointer is read from device memory: say that it is a global pointer, or the load is a flat load with a full wait)
         float z;
         if (st->noise) z = ((const __attribute__((address_space(1))) float*)st->noise)[(size_t)step * n_total + gi];
-        else if (PF && st->face_seeds) z = philox_normal(((const __attribute__((address_space(1))) unsigned long long*)st->face_seeds)[f], (unsigned)step, ef);
-        else z = philox_normal(st->seed, (unsigned)step, (unsigned)gi);
+        else if (PF && st->face_seeds) z = philox_normal(((const __attribute__((address_space(1))) unsigned long long*)st->face_seeds)[f], (unsigned)(step - st_begin(st, f)), ef);
+        else z = philox_normal(st->seed, (unsigned)(PF ? step - st_begin(st, f) : step), (unsigned)gi);
         r += c[6] * z;
     }
     if (st->x0_hist) {
@@ -221,7 +231,7 @@ __device__ __forceinline__ float sched_update(float xv, float e, const float* c,
         h[li] = x0;
     }
     if (st->mask && ((const __attribute__((address_space(1))) int*)st->mask_on)[f] != 0) {
-        const bool last = step + 1 >= st->n_steps;
+        const bool last = step + 1 >= (PF ? st_end(st, f) : st->n_steps);
         const float b0 = last ? 1.f : c[7 + 1], b1 = last ? 0.f : c[7 + 0];
         const float m = ((const __attribute__((address_space(1))) float*)st->mask)[(size_t)f * ll + (ef & (unsigned)(ll - 1))];
         const float kn = b0 * ((const __attribute__((address_space(1))) float*)st->mask_known)[li] +
@@ -248,11 +258,11 @@ __global__ __launch_bounds__(256) void ending_conv_kernel(const float* __restric
     const int nseg = B * L * (L / PXS);                                  // runs of PXS pixels (L is a multiple of 16)
     const int nb_conv = (nseg + 3) >> 2;
     if (PF && (int)blockIdx.x >= nb_conv) {
-        // per face: row r_f + step + 1 of the table while it exists (a held face keeps its last row: its eps is discarded)
+        // per face: row r_f + step + 1 of the table while the face's schedule has it (a held face keeps its last row: its eps is discarded)
         const int t = (int)blockIdx.x - nb_conv, np = film_stage_pieces(sa.film_total), f = t / np, piece = t - f * np;
         if (f >= B) return;
         const int row = st_row(sa.st, f) + sa.st->step + 1;
-        if (row >= sa.st->n_steps) return;
+        if (row >= st_end(sa.st, f)) return;
         const float4* src = reinterpret_cast<const float4*>(sa.film_table + (size_t)row * sa.film_total);
         float4* dst = reinterpret_cast<float4*>(sa.film_cur + (size_t)f * sa.film_total);
 #pragma unroll
@@ -335,7 +345,7 @@ __global__ __launch_bounds__(256) void ending_conv_kernel(const float* __restric
         const int step = sa.st->step;
         if constexpr (PF) {
             const int r = st_row(sa.st, bb), k = r + step;          // the wave's run lies in one face: k is wave-uniform
-            if (k < sa.st->n_steps)
+            if (k < st_end(sa.st, bb))
                 sa.lat[o] = sched_update<true>(sa.lat[o], e, sa.coef + (size_t)k * 7, sa.st, k, (size_t)sa.elem0 + o, sa.n_total, o,
                                                st_first(sa.st, bb, k, r), bb, (unsigned)(o - (size_t)bb * 4 * L * L), L * L);
         } else {
@@ -345,11 +355,12 @@ __global__ __launch_bounds__(256) void ending_conv_kernel(const float* __restric
     }
 }
 
-// first FiLM rows of the per-face form: film_pf[f] = film_table[min(r_f, n - 1)] (a face that starts held reads a valid row)
+// first FiLM rows of the per-face form: film_pf[f] = film_table[min(r_f, end_f - 1)] (a face that starts held reads a valid row);
+// ends == NULL: end_f = n
 static __global__ void film_rows_gather_kernel(float* __restrict__ film_pf, const float* __restrict__ film_table, const int* __restrict__ rows,
-                                               int n, int film_total) {
+                                               const int* __restrict__ ends, int n, int film_total) {
     const int f = blockIdx.y;
-    const int row = min(rows[f], n - 1);
+    const int row = max(min(rows[f], (ends ? ends[f] : n) - 1), 0);
     const float4* src = reinterpret_cast<const float4*>(film_table + (size_t)row * film_total);
     float4* dst = reinterpret_cast<float4*>(film_pf + (size_t)f * film_total);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < film_total / 4; i += gridDim.x * blockDim.x) dst[i] = src[i];

@@ -1120,9 +1120,13 @@ int hd_eps(hd_ctx* c, const float* x, const float* timesteps, int n_t, float* ep
 // every chain's StepState carries its start rows; hist_first = !resume.  rows == NULL: n_iters == n, the graphs of hd_sample.
 // hd_sample_faces* (faces = true): the same per-face graphs, and StepState also carries the faces' Philox keys (face_seeds, host [B] or NULL)
 // and first-order flags (first, host [B] or NULL: hist_first).
+// hd_sample_spans (begins / ends: host [B] each, already checked): the same per-face graphs again; StepState also carries every face's span
+// [begin_f, end_f) of the table -- the face is held from row end_f on and its noise counter starts at begin_f.  The table is the concatenation
+// of the members' schedules, so its FiLM table is as long as all of them together (0.5 MB per row at latent 16).
 static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps, const float* coef, int ncoef, const float* noise,
                        uint64_t seed, void* stream, const int32_t* rows = nullptr, int n_iters = 0, int resume = 0,
-                       const uint64_t* face_seeds = nullptr, const int32_t* first = nullptr) {
+                       const uint64_t* face_seeds = nullptr, const int32_t* first = nullptr, const int32_t* begins = nullptr,
+                       const int32_t* ends = nullptr) {
     HIPCHECK(c, hipSetDevice(c->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool ms = ncoef == 8, pf = rows != nullptr;
@@ -1161,6 +1165,13 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
         if (rc) return rc;
         c->rows_cap = c->B;
     }
+    if (begins && c->B > c->spans_cap) {                  // read through StepState: no graph holds this pointer
+        dev_free(c, c->spans_dev);
+        c->spans_dev = nullptr; c->spans_cap = 0;
+        rc = dev_alloc(c, &c->spans_dev, 2 * (size_t)c->B);
+        if (rc) return rc;
+        c->spans_cap = c->B;
+    }
     if (ms && n > c->c7_cap) {                            // read through StepState: no graph holds this pointer
         dev_free(c, c->c7_dev);
         rc = dev_alloc(c, &c->c7_dev, (size_t)n);
@@ -1173,7 +1184,7 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
     // the context, so the caller's host arrays are free on return and nothing here waits for the stream.
     // Layout: coef [n][7] | timesteps [n] | StepState (single-step), or coef | timesteps | c7 [n] | one StepState per chain
     // (multistep, per-face rows or masks) | start rows [B] (per-face rows) | Philox keys [B] (2 words each) | first-order flags [B] (per-face keys /
-    // flags).
+    // flags) | begin rows [B] | end rows [B] (spans).
     StepState st{};
     st.step = -1; st.n_steps = n; st.noise = noise; st.seed = seed;
     {
@@ -1181,7 +1192,8 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
         const size_t st_f = (sizeof(StepState) + 3) / 4, st0 = (size_t)n * (ms ? 9 : 8);
         const size_t nst = (ms || pf || mk) ? c->chains.size() : 1, rows0 = st0 + st_f * nst;
         const size_t seeds0 = rows0 + (pf ? (size_t)c->B : 0), first0 = seeds0 + (face_seeds ? 2 * (size_t)c->B : 0);
-        const size_t need = first0 + (first ? (size_t)c->B : 0);
+        const size_t spans0 = first0 + (first ? (size_t)c->B : 0);
+        const size_t need = spans0 + (begins ? 2 * (size_t)c->B : 0);
         if (sg.pending) { HIPCHECK(c, hipEventSynchronize(sg.ev)); sg.pending = false; }     // the copy issued two calls ago
         if (sg.cap < need) {
             if (sg.host) (void)hipHostFree(sg.host);
@@ -1206,6 +1218,7 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
             if (pf) st.start_rows = c->rows_dev + c->chains[k].face0;
             if (face_seeds) st.face_seeds = c->seeds_dev + c->chains[k].face0;
             if (first) st.face_first = c->first_dev + c->chains[k].face0;
+            if (begins) { st.begin_rows = c->spans_dev + c->chains[k].face0; st.end_rows = c->spans_dev + c->spans_cap + c->chains[k].face0; }
             if (mk) {
                 const size_t f0 = (size_t)c->chains[k].face0, ll = (size_t)c->L * c->L;
                 st.mask = c->mask_dev + f0 * ll; st.mask_known = c->mask_known_dev + f0 * 4 * ll;
@@ -1224,6 +1237,12 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
         if (first) {
             memcpy(sg.host + first0, first, (size_t)c->B * sizeof(int32_t));
             HIPCHECK(c, hipMemcpyAsync(c->first_dev, sg.host + first0, (size_t)c->B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        }
+        if (begins) {
+            memcpy(sg.host + spans0, begins, (size_t)c->B * sizeof(int32_t));
+            memcpy(sg.host + spans0 + c->B, ends, (size_t)c->B * sizeof(int32_t));
+            HIPCHECK(c, hipMemcpyAsync(c->spans_dev, sg.host + spans0, (size_t)c->B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            HIPCHECK(c, hipMemcpyAsync(c->spans_dev + c->spans_cap, sg.host + spans0 + c->B, (size_t)c->B * sizeof(int32_t), hipMemcpyHostToDevice, s));
         }
         memcpy(sg.host + (size_t)n * 7, timesteps, (size_t)n * sizeof(float));
         HIPCHECK(c, hipMemcpyAsync(c->coef_dev, sg.host, (size_t)n * 7 * sizeof(float), hipMemcpyHostToDevice, s));
@@ -1252,7 +1271,8 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
     c->film_from_cur = true;
     c->advance = 1;
     if (pf) {                                           // every face's first row; the ending launch of iteration i stages rows r_f + i + 1
-        hipLaunchKernelGGL(film_rows_gather_kernel, dim3(8, c->B), dim3(256), 0, s, c->film_pf, c->film_table, c->rows_dev, n, c->film_total);
+        hipLaunchKernelGGL(film_rows_gather_kernel, dim3(8, c->B), dim3(256), 0, s, c->film_pf, c->film_table, c->rows_dev,
+                           begins ? c->spans_dev + c->spans_cap : nullptr, n, c->film_total);
         HIPCHECK(c, hipGetLastError());
     } else {
         for (auto& ch : c->chains)                      // step 0's row; the ending launch of step i stages row i+1
@@ -1316,7 +1336,7 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
     // a whole-batch call leaves every face's history (multistep) or none; a multistep rows / faces call that of every face that ran a row
     if (c->hist_B != c->B || c->hist_face.size() != (size_t)c->B) c->hist_face.assign((size_t)c->B, 0);
     if (ms && pf) {
-        for (int f = 0; f < c->B; ++f) if (rows[f] < n) c->hist_face[f] = 1;
+        for (int f = 0; f < c->B; ++f) if (rows[f] < (ends ? ends[f] : n)) c->hist_face[f] = 1;
     } else {
         c->hist_face.assign((size_t)c->B, ms ? 1 : 0);
     }
@@ -1423,6 +1443,41 @@ int hd_sample_faces_multistep(hd_ctx* c, float* x_inout, const hd_schedule_ms* s
     }
     return sample_impl(c, x_inout, sched->n_steps, sched->timesteps, sched->coef, 8, noise, seed, stream, start_rows, n_iters, 0, face_seeds,
                        first.data());
+}
+
+// Per-request schedules: `table` is the concatenation of several schedules and face f runs rows start_f, start_f + 1, .. of its own span
+// [begin_f, end_f).  Everything else is hd_sample_faces_multistep (a 7-column schedule is the same rows with c7 = 0).
+int hd_sample_spans(hd_ctx* c, float* x_inout, const hd_schedule_ms* table, const int32_t* begin_rows, const int32_t* end_rows,
+                    const int32_t* start_rows, int n_iters, const int32_t* resume, const uint64_t* face_seeds, const float* noise,
+                    uint64_t seed, void* stream) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    rc = check_xcd(c);
+    if (rc) return rc;
+    if (!x_inout || !table || table->n_steps <= 0 || !table->timesteps || !table->coef || !begin_rows || !end_rows || !start_rows || !resume)
+        HD_FAIL(c, HD_ERR_INVALID, "hd_sample_spans: bad arguments");
+    const int n = table->n_steps;
+    const bool have = c->hist_B == c->B && c->hist_face.size() == (size_t)c->B;
+    std::vector<int32_t> first((size_t)c->B);
+    int longest = 0;
+    for (int f = 0; f < c->B; ++f) {
+        const int b = begin_rows[f], e = end_rows[f], r = start_rows[f];
+        if (!(0 <= b && b <= r && r <= e && e <= n))
+            HD_FAIL(c, HD_ERR_INVALID, "hd_sample_spans: face %d: need 0 <= begin (%d) <= start (%d) <= end (%d) <= n_steps (%d)", f, b, r, e, n);
+        if (b < n && table->coef[(size_t)b * 8 + 7] != 0.f)
+            HD_FAIL(c, HD_ERR_INVALID, "hd_sample_spans: face %d: row %d begins its schedule and must have c7 == 0 (no history before it)", f, b);
+        if (resume[f] != 0 && resume[f] != 1) HD_FAIL(c, HD_ERR_INVALID, "hd_sample_spans: resume[%d] = %d is not 0 or 1", f, resume[f]);
+        if (resume[f] && r == b)
+            HD_FAIL(c, HD_ERR_INVALID, "hd_sample_spans: resume[%d] = 1 but face %d starts at its begin row %d (nothing to resume)", f, f, b);
+        if (resume[f] && !(have && c->hist_face[f]))
+            HD_FAIL(c, HD_ERR_INVALID, "hd_sample_spans: resume[%d] = 1 but face %d has no multistep history (no multistep row since "
+                                       "hd_prepare*, hd_prepare_slots refilled it, or a single-step call in between)", f, f);
+        first[f] = resume[f] ? 0 : 1;
+        if (e - r > longest) longest = e - r;
+    }
+    if (n_iters < 1 || n_iters > longest) HD_FAIL(c, HD_ERR_INVALID, "hd_sample_spans: n_iters = %d outside [1, %d]", n_iters, longest);
+    return sample_impl(c, x_inout, n, table->timesteps, table->coef, 8, noise, seed, stream, start_rows, n_iters, 0, face_seeds, first.data(),
+                       begin_rows, end_rows);
 }
 
 // Replace the conditioning of n slots.  The prologue (FPG, ResNet-50 or the given embedding, HCA gates, idc_conv) runs at batch n on the

@@ -119,9 +119,78 @@ def region_mask(boxes, latent_res, image_res=128, feather=0):
     return m.clamp(0.0, 1.0).to(torch.float32)
 
 
+class ScheduleSet:
+    """Several schedules as one table, for batches whose faces run different step counts or solvers (hd_sample_spans).
+
+    schedulers: a dict name -> scheduler, or a list (the keys are then 0, 1, ..); every member has had set_timesteps called.  The members'
+    coefficient tables are concatenated in order into one (timesteps [N], coef [N,8]) table -- a 7-column member (DDIM / DDPM) is padded
+    with c7 = 0 -- and span(key) is the member's rows [begin, end) of it.  The table is cached like a scheduler's coefficient_table() and
+    rebuilt when a member's table changes (a new set_timesteps).  The library keeps one FiLM row per table row (0.5 MB at latent 16), so
+    the memory price of a set is that of the sum of its members' lengths."""
+
+    def __init__(self, schedulers):
+        items = list(schedulers.items()) if isinstance(schedulers, dict) else list(enumerate(schedulers))
+        if not items:
+            raise ValueError("a ScheduleSet needs at least one scheduler")
+        for k, m in items:
+            ts = getattr(m, "timesteps", None)
+            if ts is None or len(ts) == 0 or not hasattr(m, "coefficient_table"):
+                raise ValueError(f"schedule {k!r} has no timesteps: call set_timesteps first")
+        self.keys = [k for k, _ in items]
+        self.members = dict(items)
+        self._cache = None
+
+    def __len__(self):
+        return len(self.keys)
+
+    def __contains__(self, key):
+        return key in self.members
+
+    def member(self, key):
+        if key not in self.members:
+            raise KeyError(f"no schedule {key!r} in the set (members: {self.keys})")
+        return self.members[key]
+
+    def _built(self):
+        tabs = [self.members[k].coefficient_table() for k in self.keys]
+        # the members hand out their cached tensors: a member's table has changed exactly when it returns another tensor
+        ident = tuple((id(t), id(c)) for t, c in tabs)
+        if self._cache is None or self._cache[0] != ident:
+            coefs, spans, at = [], {}, 0
+            for k, (t, c) in zip(self.keys, tabs):
+                if c.shape[1] == 7:
+                    c = torch.cat([c, torch.zeros((c.shape[0], 1), dtype=c.dtype)], dim=1)
+                coefs.append(c)
+                spans[k] = (at, at + int(t.numel()))
+                at += int(t.numel())
+            self._cache = (ident, tabs, torch.cat([t for t, _ in tabs]).contiguous(), torch.cat(coefs).contiguous(), spans)
+        return self._cache
+
+    def coefficient_table(self):
+        """(timesteps [N] fp32, coef [N,8] fp32): the members' tables one after the other (hd_schedule_ms form); read-only for the caller."""
+        b = self._built()
+        return b[2], b[3]
+
+    def span(self, key):
+        """(begin, end): the member's rows of the concatenated table."""
+        self.member(key)
+        return self._built()[4][key]
+
+    def spans(self, schedules, B):
+        """schedules (one key, or one key per face) -> (begin [B], end [B]) int32 CPU tensors."""
+        if isinstance(schedules, (list, tuple)):
+            keys = list(schedules)
+        else:
+            keys = [schedules] * B
+        if len(keys) != B:
+            raise ValueError(f"schedules must be one key or {B} keys (one per face), got {len(keys)}")
+        se = [self.span(k) for k in keys]
+        return (torch.tensor([b for b, _ in se], dtype=torch.int32), torch.tensor([e for _, e in se], dtype=torch.int32))
+
+
 @torch.no_grad()
 def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, prepare=True, check=True,
-           start_steps=None, n_iters=None, resume=False, face_seeds=None, mask=None, known=None, known_noise=None):
+           start_steps=None, n_iters=None, resume=False, face_seeds=None, mask=None, known=None, known_noise=None, schedules=None):
     """Whole loop on the GPU: returns the final latents (a new tensor).
 
     The scheduler's coefficient table picks the entry point: 7 columns (DDIM / DDPM) -> hd_sample, 8 columns
@@ -144,13 +213,23 @@ def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, pr
     re-noised to the next row, and exactly `known` after the last.  mask=None with prepare=True removes any mask the engine still holds
     (the conditioning cache can hit without a new prepare); with prepare=False the engine's masks are left alone (continuous batching,
     a loop split over calls).
+    scheduler may be a ScheduleSet (per-request schedules, hd_sample_spans): `schedules` is then one member key or one per face, face f
+    runs its member's rows only and is held after them, start_steps is relative to the face's own schedule (0 .. n_f, default 0), n_iters
+    defaults to the longest remaining run, and resume (a bool or a [B] tensor) continues a face's history as above -- it needs
+    start_steps[f] > 0.  A face's z counts rows from the start of its own schedule; an explicit noise tensor is indexed by the row of the
+    concatenated table ([N, B, 4, L, L]).  With a plain scheduler `schedules` must stay None.
     check=True (the default): ONE stream synchronisation after the whole loop (not per step), then RuntimeError if a persistent
     stage launch gave up during it -- where the reference's loop would have raised (test_refiner.py:89-91), so that the last batch
     of a val_loop cannot end with rc 0 and NaN images.  check=False only enqueues the work (the returned latents are NaN in the
     failing case either way; `model.check()` reports it later).  bench.py times the loop with its own synchronisation."""
-    if face_seeds is not None:                             # argument errors before any device work
+    span_rows = None
+    if isinstance(scheduler, ScheduleSet):                 # argument errors before any device work
+        span_rows = _span_args(scheduler, schedules, start_steps, latents.shape[0])
+    elif schedules is not None:
+        raise ValueError("schedules needs a ScheduleSet as the scheduler")
+    if face_seeds is not None:
         face_seeds = face_seeds_arg(face_seeds, latents.shape[0])
-    if isinstance(resume, torch.Tensor):
+    if isinstance(resume, torch.Tensor) or span_rows is not None:
         resume = resume_arg(resume, latents.shape[0])
     if mask is None and (known is not None or known_noise is not None):
         raise ValueError("known / known_noise need a mask")
@@ -189,6 +268,8 @@ def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, pr
         nptr = noise.data_ptr()
     stream = torch.cuda.current_stream(e.device).cuda_stream
     B = x.shape[0]
+    if span_rows is not None:
+        return _sample_spans(e, x, sch, span_rows, nptr, seed, stream, n_iters, resume, face_seeds, check)
     per_face_resume = isinstance(resume, torch.Tensor)
     if face_seeds is not None or per_face_resume:
         return _sample_faces(e, x, sch, ts, multistep, nptr, seed, stream, start_steps, n_iters, resume, face_seeds, check)
@@ -266,6 +347,36 @@ def resume_arg(resume, B):
     return r.to(torch.int32).contiguous()
 
 
+def _span_args(sset, schedules, start_steps, B):
+    """(begin, end, start) int32 [B] CPU tensors of a ScheduleSet call: start_steps is relative to each face's own schedule."""
+    if schedules is None:
+        raise ValueError("a ScheduleSet needs schedules=: one member key, or one per face")
+    begin, end = sset.spans(schedules, B)
+    rel = _rows_arg(start_steps, B)
+    if bool(((rel < 0) | (rel > end - begin)).any()):
+        f = int(((rel < 0) | (rel > end - begin)).nonzero()[0])
+        raise ValueError(f"start_steps[{f}] = {int(rel[f])} outside face {f}'s schedule [0, {int(end[f] - begin[f])}]")
+    return begin.contiguous(), end.contiguous(), (begin + rel).contiguous()
+
+
+def _sample_spans(e, x, sch, span_rows, nptr, seed, stream, n_iters, resume, face_seeds, check):
+    """hd_sample_spans: per-face spans of a concatenated table, with per-face start rows, Philox keys and resumption."""
+    begin, end, rows = span_rows
+    if n_iters is None:
+        n_iters = int((end - rows).max())
+        if n_iters == 0:
+            return x
+    i32 = lambda t: ctypes.cast(t.data_ptr(), ctypes.POINTER(ctypes.c_int32))   # noqa: E731
+    sptr = face_seeds.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if face_seeds is not None else None
+    with torch.cuda.device(e.device):
+        rc = _lib.lib().hd_sample_spans(e.ctx, x.data_ptr(), ctypes.byref(sch), i32(begin), i32(end), i32(rows), int(n_iters), i32(resume),
+                                        sptr, nptr, int(seed), stream)
+        _lib.check(rc, e.ctx)
+    if check:
+        e.check()
+    return x
+
+
 def _sample_faces(e, x, sch, ts, multistep, nptr, seed, stream, start_steps, n_iters, resume, face_seeds, check):
     """hd_sample_faces / hd_sample_faces_multistep: per-face start rows, Philox keys and (multistep) resumption."""
     B = x.shape[0]
@@ -299,7 +410,11 @@ class SlotTable:
     A request placed in a slot starts at its own row (img2img_start's convention) and is "fresh": its first row is taken first-order
     (resume 0).  After a call of n_iters iterations every occupied slot advances by n_iters rows; a slot that ran at least one row has a
     history of its own from then on (resume 1), and a slot whose row reached n_steps is complete and free again.  An empty slot is held
-    (start row n_steps) and is never resumed."""
+    (start row n_steps) and is never resumed.
+
+    Per-request schedules (ScheduleSet): assign(req, start_row, begin, end) gives the slot the span [begin, end) of a table of n_steps rows
+    as its own schedule; start_row is a row of the table inside the span, and the slot is complete when it reaches `end`.  Without a span
+    a slot's schedule is the whole table."""
 
     def __init__(self, batch, n_steps):
         if batch < 1 or n_steps < 1:
@@ -308,6 +423,8 @@ class SlotTable:
         self.req = [None] * self.batch          # request id per slot (None: empty)
         self.row = [self.n_steps] * self.batch  # schedule row of the slot's next iteration
         self.fresh = [False] * self.batch       # True until the slot's request has run a row (first-order first row)
+        self.begin = [0] * self.batch           # the slot's own schedule: rows [begin, end) of the table
+        self.end = [self.n_steps] * self.batch
 
     def free_slots(self):
         return [i for i, r in enumerate(self.req) if r is None]
@@ -315,20 +432,33 @@ class SlotTable:
     def occupied(self):
         return [i for i, r in enumerate(self.req) if r is not None]
 
-    def assign(self, req_id, start_row):
-        """Place a request in the lowest free slot at row start_row (0 <= start_row <= n_steps); returns the slot."""
-        if not 0 <= int(start_row) <= self.n_steps:
-            raise ValueError(f"start row {start_row} outside [0, {self.n_steps}]")
+    def assign(self, req_id, start_row, begin=None, end=None):
+        """Place a request in the lowest free slot at row start_row of its schedule [begin, end) (default: the whole table,
+        0 <= begin <= start_row <= end <= n_steps); returns the slot."""
+        begin, end = 0 if begin is None else int(begin), self.n_steps if end is None else int(end)
+        if not 0 <= begin <= end <= self.n_steps:
+            raise ValueError(f"span [{begin}, {end}) outside the table [0, {self.n_steps}]")
+        if not begin <= int(start_row) <= end:
+            raise ValueError(f"start row {start_row} outside [{begin}, {end}]")
         free = self.free_slots()
         if not free:
             raise RuntimeError("no free slot")
         i = free[0]
         self.req[i], self.row[i], self.fresh[i] = req_id, int(start_row), True
+        self.begin[i], self.end[i] = begin, end
         return i
 
     def start_rows(self):
         """Start rows of the next call: the slot's row, n_steps (held) for an empty slot."""
         return [self.row[i] if self.req[i] is not None else self.n_steps for i in range(self.batch)]
+
+    def begin_rows(self):
+        """Begin rows of the next call (hd_sample_spans): the slot's span, n_steps for an empty slot (held: begin == start == end)."""
+        return [self.begin[i] if self.req[i] is not None else self.n_steps for i in range(self.batch)]
+
+    def end_rows(self):
+        """End rows of the next call: the slot's span, n_steps for an empty slot."""
+        return [self.end[i] if self.req[i] is not None else self.n_steps for i in range(self.batch)]
 
     def resume_flags(self):
         """Multistep resumption of the next call: 1 for a slot whose request has already run a row, else 0."""
@@ -337,17 +467,17 @@ class SlotTable:
     def iters(self, limit):
         """Iterations of the next call: `limit`, or fewer when no occupied slot has that many rows left (0: nothing runs).  A slot that
         reaches its last row inside the call is held for the rest of it: refills come every `limit` iterations, not at every finish."""
-        left = [self.n_steps - self.row[i] for i in self.occupied() if self.row[i] < self.n_steps]
+        left = [self.end[i] - self.row[i] for i in self.occupied() if self.row[i] < self.end[i]]
         return min(int(limit), max(left)) if left else 0
 
     def advance(self, n_iters):
         """Account for a call of n_iters iterations; returns [(slot, request id)] of the requests it completed (their slots are free)."""
         done = []
         for i in self.occupied():
-            if self.row[i] < self.n_steps and n_iters > 0:
+            if self.row[i] < self.end[i] and n_iters > 0:
                 self.fresh[i] = False
-            self.row[i] = min(self.row[i] + int(n_iters), self.n_steps)
-            if self.row[i] >= self.n_steps:
+            self.row[i] = min(self.row[i] + int(n_iters), self.end[i])
+            if self.row[i] >= self.end[i]:
                 done.append((i, self.req[i]))
                 self.req[i], self.fresh[i] = None, False
         return done
@@ -367,7 +497,11 @@ class ContinuousSampler:
     step() runs one call of refill_every iterations (fewer when no slot has that many rows left) after refilling free slots from the
     queue; a face that reaches its last row inside the call is held (not evaluated further) until the next refill;
     poll() returns what has finished since the last poll.  The model is the sampler's own while it runs: any other prepare / forward
-    on it replaces the batch.  For the unconditional Denoiser pass cr_face = cr_latent = None (pure-noise start, strength 1)."""
+    on it replaces the batch.  For the unconditional Denoiser pass cr_face = cr_latent = None (pure-noise start, strength 1).
+
+    Per-request schedules: pass a ScheduleSet instead of a scheduler and pick a member per request, submit(..., schedule=key) (default: the
+    set's first member).  Requests of different step counts and solvers then share the batch (hd_sample_spans): each runs its own member's
+    rows, its strength maps onto that member's row count, and its result is what it would be on that member alone."""
 
     def __init__(self, model, scheduler, batch=64, refill_every=5):
         if batch < 1 or refill_every < 1:
@@ -376,9 +510,10 @@ class ContinuousSampler:
         self.batch, self.refill_every = int(batch), int(refill_every)
         self.conditional = model.engine.conditional
         self.L = model.engine.latent_res
-        self.n_steps = int(scheduler.timesteps.numel())
+        self.sset = scheduler if isinstance(scheduler, ScheduleSet) else None
+        self.n_steps = int(scheduler.coefficient_table()[0].numel()) if self.sset else int(scheduler.timesteps.numel())
         self.table = SlotTable(self.batch, self.n_steps)
-        self.queue = []                 # (rid, cr_face, cr_latent, seed, strength, mask) in submission order
+        self.queue = []                 # (rid, cr_face, cr_latent, seed, strength, mask, schedule) in submission order
         self.finished = {}
         self.seeds = [0] * self.batch
         self.x = None                   # [B,4,L,L] device latents of every slot
@@ -387,11 +522,18 @@ class ContinuousSampler:
         self.calls = 0
         self.refilled = 0
 
-    def submit(self, cr_face, cr_latent, seed, strength=1.0, mask=None):
-        """mask: None, or [L,L] / [1,L,L] in [0, 1] (1: resample): the request is inpainted -- its known latent is cr_latent, the noise of
+    def submit(self, cr_face, cr_latent, seed, strength=1.0, mask=None, schedule=None):
+        """schedule: the member of the ScheduleSet this request runs (None: the first member; without a set it must stay None).
+        mask: None, or [L,L] / [1,L,L] in [0, 1] (1: resample): the request is inpainted -- its known latent is cr_latent, the noise of
         the kept region the z its start is drawn from (inpaint_start; strength 1 starts from pure noise).  Masked and unmasked requests
         share a batch."""
         L = self.L
+        if self.sset is None:
+            if schedule is not None:
+                raise ValueError("schedule= needs a ContinuousSampler over a ScheduleSet")
+        else:
+            schedule = self.sset.keys[0] if schedule is None else schedule
+            self.sset.member(schedule)
         if mask is not None:
             if not self.conditional:
                 raise ValueError("a mask needs the refiner: the request's known latent is its cr_latent")
@@ -414,7 +556,7 @@ class ContinuousSampler:
             raise ValueError("seed must lie in [0, 2**63)")
         rid = self.next_id
         self.next_id += 1
-        self.queue.append((rid, cr_face, cr_latent, seed, float(strength), mask))
+        self.queue.append((rid, cr_face, cr_latent, seed, float(strength), mask, schedule))
         return rid
 
     def _z(self, seed):
@@ -422,24 +564,30 @@ class ContinuousSampler:
         re-noised with it."""
         return torch.randn((1, 4, self.L, self.L), generator=torch.Generator().manual_seed(seed))
 
-    def _start(self, cr_latent, seed, strength, masked=False):
+    def _start(self, cr_latent, seed, strength, masked=False, schedule=None):
         """(initial latents [4,L,L] on the CPU, start row) of one request: img2img_start (inpaint_start for a masked request) with a CPU
-        generator seeded by the request."""
+        generator seeded by the request.  Over a ScheduleSet the start row is relative to the request's member `schedule`, whose
+        timesteps and row count the strength maps onto."""
+        sch = self.scheduler if self.sset is None else self.sset.member(self.sset.keys[0] if schedule is None else schedule)
         z = self._z(seed)
         if cr_latent is None:
             return z[0], 0
         if masked:
-            lat, start, _ = inpaint_start(self.scheduler, cr_latent.detach().float().cpu()[None], strength, noise=z)
+            lat, start, _ = inpaint_start(sch, cr_latent.detach().float().cpu()[None], strength, noise=z)
         else:
-            lat, start = img2img_start(self.scheduler, cr_latent.detach().float().cpu()[None], strength, noise=z)
+            lat, start = img2img_start(sch, cr_latent.detach().float().cpu()[None], strength, noise=z)
         return lat[0], int(start[0])
 
     def _refill(self, dev):
         new, masked = [], []
         while self.queue and self.table.free_slots():
-            rid, crf, crl, seed, strength, mask = self.queue.pop(0)
-            lat, start = self._start(crl, seed, strength, mask is not None)
-            slot = self.table.assign(rid, start)
+            rid, crf, crl, seed, strength, mask, schedule = self.queue.pop(0)
+            lat, start = self._start(crl, seed, strength, mask is not None, schedule)
+            if self.sset is None:
+                slot = self.table.assign(rid, start)
+            else:
+                begin, end = self.sset.span(schedule)
+                slot = self.table.assign(rid, begin + start, begin, end)
             self.seeds[slot] = seed
             self.x[slot] = lat.to(dev)
             new.append((slot, crf, crl))
@@ -478,11 +626,32 @@ class ContinuousSampler:
             kw = dict(start_steps=torch.tensor(self.table.start_rows()), n_iters=n, face_seeds=list(self.seeds))
             if multistep:
                 kw["resume"] = torch.tensor(self.table.resume_flags(), dtype=torch.bool)
-            self.x = sample(self.model, self.x, None, None, self.scheduler, prepare=False, **kw)
+            if self.sset is None:
+                self.x = sample(self.model, self.x, None, None, self.scheduler, prepare=False, **kw)
+            else:
+                self.x = self._step_spans(e, n, kw)
             self.calls += 1
         for slot, rid in self.table.advance(n):
             self.finished[rid] = self.x[slot].clone()
         return n
+
+    def _step_spans(self, e, n, kw):
+        """One call over the set: the slots' spans and absolute start rows go to hd_sample_spans as they stand in the table."""
+        ts, coef = self.sset.coefficient_table()
+        sch = _lib.ScheduleMS()
+        sch.n_steps = ts.numel()
+        sch.timesteps = ctypes.cast(ts.data_ptr(), ctypes.POINTER(ctypes.c_float))
+        sch.coef = ctypes.cast(coef.data_ptr(), ctypes.POINTER(ctypes.c_float))
+        e.ensure(self.x.device)
+        if not e.conditional:
+            e.prepare_unconditional(self.batch)
+        e.require_loaded()
+        t = self.table
+        rows = (torch.tensor(t.begin_rows(), dtype=torch.int32), torch.tensor(t.end_rows(), dtype=torch.int32),
+                torch.tensor(t.start_rows(), dtype=torch.int32))
+        x = self.x.to(device=e.device, dtype=torch.float32).contiguous().clone()
+        return _sample_spans(e, x, sch, rows, None, 0, torch.cuda.current_stream(e.device).cuda_stream, n,
+                             resume_arg(kw["resume"], self.batch), face_seeds_arg(kw["face_seeds"], self.batch), True)
 
     def busy(self):
         return bool(self.queue) or bool(self.table.occupied())

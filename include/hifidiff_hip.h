@@ -180,6 +180,26 @@ int hd_sample_faces(hd_ctx* ctx, float* x_inout, const hd_schedule* sched, const
                     const float* noise, uint64_t seed, void* stream);
 int hd_sample_faces_multistep(hd_ctx* ctx, float* x_inout, const hd_schedule_ms* sched, const int32_t* start_rows, int n_iters,
                               const int32_t* resume, const uint64_t* face_seeds, const float* noise, uint64_t seed, void* stream);
+/* Per-request schedules: mixed step counts and solvers in one batch.  `table` is the concatenation of several schedules in hd_schedule_ms
+ * form (a DDIM / DDPM row is the same row with c[7] = 0), and face f owns the span [begin_rows[f], end_rows[f]) of it as its schedule (host
+ * [B] each, like start_rows): at iteration i the face is evaluated at row k = start_rows[f] + i while k < end_f and held from then on (its
+ * latents, its history and its FiLM row are not written; a masked face's kept region ends exactly on `known` at row end_f - 1).
+ *   rows: 0 <= begin_f <= start_f <= end_f <= n_steps; a face with start_f == end_f is held for the whole call (an empty slot).
+ *   n_iters in [1, max_f (end_f - start_f)].
+ *   every row that is some face's begin must have c[7] == 0 (no history before the first row of a schedule).
+ *   resume[f] == 1 continues face f's history under the rules of hd_sample_faces_multistep and needs start_f > begin_f; 0 takes row
+ *   start_f first-order.
+ *   face_seeds / seed: z of face f at row k is Philox(key; k - begin_f, element): the counter is the row inside the face's own schedule,
+ *   so a request's z does not depend on where its schedule sits in the table.  An explicit `noise` tensor [n_steps][B,4,L,L] stays
+ *   indexed by the absolute row k of the table.
+ * HD_ERR_INVALID, with a message that names the face, for each violation.  With begin_f = 0 and end_f = n_steps for every face this is
+ * hd_sample_faces_multistep bit for bit.  The captured per-face graphs are those of hd_sample_rows* / hd_sample_faces* (the spans are read
+ * through the loop state: alternating between the entry points captures nothing), and a multistep history is left for every face that ran
+ * a row.  The FiLM table of the whole concatenated table is computed once and cached by its timesteps, as for every other entry point; it
+ * costs about 0.5 MB per row at latent 16 (0.5 GB for a table of 1000 rows), so a set of long schedules is paid for in memory. */
+int hd_sample_spans(hd_ctx* ctx, float* x_inout, const hd_schedule_ms* table, const int32_t* begin_rows, const int32_t* end_rows,
+                    const int32_t* start_rows, int n_iters, const int32_t* resume, const uint64_t* face_seeds, const float* noise,
+                    uint64_t seed, void* stream);
 
 /* Masked sampling (inpainting, diffusers' inpaint loop for a 4-channel UNet with one mask per face).
  * hd_mask_faces: give n faces of the prepared batch a mask: slots[j] (host [n], distinct, in [0, B); NULL: n == B, faces in order) gets

@@ -6,7 +6,10 @@ Forms: static batching -- 64 requests at a time through sample(start_steps=...),
 sampling.ContinuousSampler at refill_every K = 1, 5, 10.  Each configuration is timed end to end (queue to last result, device
 synchronised), in alternating runs; reported: median and spread of faces/s, and the mean request latency (finish time - 0).
 Also: hd_prepare_slots for n = 1, 8, 32, 64 against hd_prepare at 64, hd_sample_faces ms/step against hd_sample_rows, and where the time
-of a continuous run goes (refills against sampling calls; an instrumented run with a synchronisation around each part)."""
+of a continuous run goes (refills against sampling calls; an instrumented run with a synchronisation around each part).
+--mixed-steps 10,20,50 runs one scenario instead (and appends to --out): the requests cycle through DDIM schedules of these step counts,
+strengths uniform in [0.2, 1.0]; one ContinuousSampler over a sampling.ScheduleSet (hd_sample_spans: all step counts share the 64 slots)
+against one ContinuousSampler per step count, run one after the other, shortest schedule first (what a single-schedule batch allows)."""
 import argparse
 import ctypes
 import os
@@ -78,11 +81,77 @@ def run_continuous(m, sch, reqs, K, instrument=False):
     return total, statistics.mean(lat), t_refill[0], cs.calls
 
 
+def run_set(m, sset, reqs, keys, K):
+    """One ContinuousSampler over the set: every request on its own member."""
+    from hifidiff_amd import sampling
+    cs = sampling.ContinuousSampler(m, sset, batch=64, refill_every=K)
+    sync()
+    t0 = time.perf_counter()
+    for r, k in zip(reqs, keys):
+        cs.submit(*r, schedule=k)
+    lat = []
+    while cs.busy():
+        cs.step()
+        lat += [time.perf_counter() - t0] * len(cs.poll())
+    return time.perf_counter() - t0, statistics.mean(lat)
+
+
+def run_one_by_one(m, sset, reqs, keys, K):
+    """One ContinuousSampler per member, one after the other (shortest schedule first); latencies count from the common t = 0."""
+    from hifidiff_amd import sampling
+    sync()
+    t0 = time.perf_counter()
+    lat = []
+    for key in sorted(sset.keys):
+        cs = sampling.ContinuousSampler(m, sset.member(key), batch=64, refill_every=K)
+        for r, k in zip(reqs, keys):
+            if k == key:
+                cs.submit(*r)
+        while cs.busy():
+            cs.step()
+            lat += [time.perf_counter() - t0] * len(cs.poll())
+    return time.perf_counter() - t0, statistics.mean(lat)
+
+
+def mixed_steps(m, a):
+    from hifidiff_amd import sampling, schedulers
+    counts = [int(v) for v in a.mixed_steps.split(",")]
+    members = {}
+    for n in counts:
+        members[n] = schedulers.DDIMScheduler(clip_sample_range=3.0)
+        members[n].set_timesteps(n)
+    sset = sampling.ScheduleSet(members)
+    reqs = requests(a.requests, True)
+    keys = [counts[i % len(counts)] for i in range(len(reqs))]
+    n = len(reqs)
+    out = [f"\n# tools/stream_bench.py --mixed-steps {a.mixed_steps}: {n} requests queued at t = 0, DDIM, step counts cycling over the requests, "
+           f"strength U[0.2, 1.0], batch 64, latent 16; {a.runs} alternating runs (median [min, max])",
+           "form                              faces/s median [min, max]        mean latency s   vs one by one"]
+    forms = [(f"{name} K={K}", fn, K) for K in (5, 10) for name, fn in (("one sampler per count", run_one_by_one), ("one sampler, set", run_set))]
+    for _, fn, K in forms:                                                # warm: captures, FiLM tables, staging chain
+        fn(m, sset, reqs[:96], keys[:96], K)
+    res = {f: [] for f, _, _ in forms}
+    for _ in range(a.runs):
+        for f, fn, K in forms:
+            res[f].append(fn(m, sset, reqs, keys, K))
+    for f, _, K in forms:
+        base = statistics.median(n / t for t, _ in res[f"one sampler per count K={K}"])
+        fps = [n / t for t, _ in res[f]]
+        lat = statistics.median(l for _, l in res[f])
+        out.append(f"{f:<33} {statistics.median(fps):8.1f} [{min(fps):7.1f}, {max(fps):7.1f}]   {lat:10.3f}      {statistics.median(fps) / base:5.2f}x")
+    txt = "\n".join(out) + "\n"
+    print(txt)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "a") as fh:
+        fh.write(txt)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--requests", type=int, default=512)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08_stream_bench.txt"))
+    ap.add_argument("--mixed-steps", help="comma-separated step counts: run the mixed-schedule scenario only, appended to --out")
     a = ap.parse_args()
     from hifidiff_amd import _lib, schedulers, synth
     from hifidiff_amd.refiner import FacialRefiner
@@ -90,6 +159,8 @@ def main():
     m = FacialRefiner(16)
     m.load_state_dict(synth.refiner_state_dict(16))
     m.to("cuda:0")
+    if a.mixed_steps:
+        return mixed_steps(m, a)
     L = _lib.lib()
     out = ["# tools/stream_bench.py: batch 64, latent 16, synthetic weights, one MI355X; requests queued at t = 0; "
            f"{a.runs} alternating runs per configuration (median [min, max])"]
