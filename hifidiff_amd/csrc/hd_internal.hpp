@@ -82,6 +82,36 @@ struct Op {
 
 struct Level { int C, H, M; float *X, *Y, *T1, *pooled, *S; unsigned short *G, *Xb, *Yb, *Xg, *pooled16; float2 *sx, *sy; };
 
+// One call of the sampling loop as its entry point describes it to sample_impl (hd_lib.hip): a table of n rows of ncoef (7, or 8:
+// multistep) coefficients, and the caller's host [B] arrays -- NULL where the entry point has none, and then NULL in StepState too.
+struct SampleCall {
+    const char* fn = "";                                  // the entry point, for messages
+    int n = 0, ncoef = 7;
+    const float *timesteps = nullptr, *coef = nullptr;
+    const float* noise = nullptr;                         // [n][B*4*L*L] on the device, or NULL: Philox(seed)
+    uint64_t seed = 0;
+    const int32_t* start_rows = nullptr;                  // hd_sample_rows* / _faces* / _spans: the per-face graphs, n_iters iterations
+    int n_iters = 0;
+    const int32_t *begin_rows = nullptr, *end_rows = nullptr;   // hd_sample_spans
+    const uint64_t* face_seeds = nullptr;                 // hd_sample_faces* / _spans (optional there)
+    const int32_t* first = nullptr;                       // !resume[f]: hd_sample_faces_multistep / _spans
+    int resume = 0;                                       // batch-wide (hd_sample_rows_multistep): hist_first = !resume
+};
+// The per-face argument block of a call for B faces, on the device and in the staging buffer alike: Philox keys [B] (8 bytes each, so
+// the base is 8-byte aligned) | start rows | first-order flags | begin rows | end rows ([B] int32 each).
+constexpr size_t kFaceArgBytes = sizeof(uint64_t) + 4 * sizeof(int32_t);
+struct FaceArgs { unsigned long long* seeds; int *rows, *first, *begins, *ends; };
+inline FaceArgs face_args(void* base, int B) {
+    unsigned long long* seeds = static_cast<unsigned long long*>(base);
+    int* rows = reinterpret_cast<int*>(seeds + B);
+    return FaceArgs{seeds, rows, rows + B, rows + 2 * B, rows + 3 * B};
+}
+// Hands out the regions of a staging buffer in order, each 8-byte aligned; `at` ends as the size needed.
+struct StageCursor {
+    size_t at = 0;
+    size_t take(size_t bytes) { const size_t o = at; at += (bytes + 7) / 8 * 8; return o; }
+};
+
 }  // namespace hdi
 using namespace hdi;
 
@@ -201,13 +231,15 @@ struct hd_ctx {
     float* c7_dev = nullptr;                  // [n] history coefficients of a multistep schedule (StepState::c7, not captured)
     int c7_cap = 0;
     // per-face schedule positions (hd_sample_rows*): film_pf [B][film_total] holds every face's FiLM row of the current iteration (the
-    // LayerNorm loaders read it with film_face_stride = film_total while film_pf_mode is set, i.e. while the per-face graphs are captured);
-    // rows_dev [B] the faces' start rows.  rows_gen: bumped wherever the captured graphs go stale (Chain::rows_gen).
+    // LayerNorm loaders read it with film_face_stride = film_total while film_pf_mode is set, i.e. while the per-face graphs are captured).
+    // rows_gen: bumped wherever the captured graphs go stale (Chain::rows_gen).
     float* film_pf = nullptr;
     size_t film_pf_cap = 0;
-    int* rows_dev = nullptr;
-    int rows_cap = 0;
     bool film_pf_mode = false;
+    // the per-face arguments of a sampling call (FaceArgs): one device block for faces_cap faces, laid out per call for its batch and
+    // uploaded with one copy.  Read through StepState and by the gather launch of the call: no graph holds a pointer into it.
+    unsigned long long* faces_dev = nullptr;
+    int faces_cap = 0;
     unsigned rows_gen = 1;
     // the x0 history left by the last multistep call (hd_sample_rows_multistep resume = 1 continues it): valid for batch hist_B until
     // hd_prepare* or a single-step sampling call
@@ -216,15 +248,8 @@ struct hd_ctx {
     // the same per face (hd_sample_faces_multistep resume[f] = 1 needs hist_face[f]): [hist_B] flags, cleared where hist_valid is, per slot
     // by hd_prepare_slots; set for every face that ran a row of a multistep rows / faces call
     std::vector<char> hist_face;
-    // per-face Philox keys and first-order flags of hd_sample_faces* ([B] each, read through StepState: no graph holds these pointers)
-    unsigned long long* seeds_dev = nullptr;
-    int* first_dev = nullptr;
-    int faces_cap = 0;
-    // per-face schedule spans of hd_sample_spans: begin rows [B] | end rows [B] (read through StepState: no graph holds this pointer)
-    int* spans_dev = nullptr;
-    int spans_cap = 0;
     // masked sampling (hd_mask_faces): the batch's masks [B,L,L], known latents and their noise [B,4,L,L], the per-face flags and the slot
-    // list of a call (sized like rows_dev, read through StepState: no graph holds these pointers).  mask_face: the host's copy of the flags
+    // list of a call (sized by the batch like faces_dev, read through StepState: no graph holds these pointers).  mask_face: the host's copy of the flags
     // ([B], empty: none set) -- sample_impl hands the buffers to StepState only while a face is masked.  Masks outlive hd_sample* calls;
     // every hd_prepare* clears them all, hd_prepare_slots those of the slots it refills.
     float *mask_dev = nullptr, *mask_known_dev = nullptr, *mask_noise_dev = nullptr;

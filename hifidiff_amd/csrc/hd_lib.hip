@@ -1113,25 +1113,51 @@ int hd_eps(hd_ctx* c, const float* x, const float* timesteps, int n_t, float* ep
     return HD_OK;
 }
 
-// hd_sample (ncoef 7) and hd_sample_multistep (ncoef 8: c7 goes to its own [n] table, and every chain's StepState carries
-// its x0 history).  One captured graph serves both: the single-step path keeps its [n][7] table and a StepState whose
-// x0_hist is NULL, so its launches and their memory traffic are those of a single-step-only build.
-// hd_sample_rows* (rows != NULL: host [B] start rows, already checked): n_iters iterations of the per-face graphs (Chain::graph_rows_*),
-// every chain's StepState carries its start rows; hist_first = !resume.  rows == NULL: n_iters == n, the graphs of hd_sample.
-// hd_sample_faces* (faces = true): the same per-face graphs, and StepState also carries the faces' Philox keys (face_seeds, host [B] or NULL)
-// and first-order flags (first, host [B] or NULL: hist_first).
-// hd_sample_spans (begins / ends: host [B] each, already checked): the same per-face graphs again; StepState also carries every face's span
-// [begin_f, end_f) of the table -- the face is held from row end_f on and its noise counter starts at begin_f.  The table is the concatenation
-// of the members' schedules, so its FiLM table is as long as all of them together (0.5 MB per row at latent 16).
-static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps, const float* coef, int ncoef, const float* noise,
-                       uint64_t seed, void* stream, const int32_t* rows = nullptr, int n_iters = 0, int resume = 0,
-                       const uint64_t* face_seeds = nullptr, const int32_t* first = nullptr, const int32_t* begins = nullptr,
-                       const int32_t* ends = nullptr) {
-    HIPCHECK(c, hipSetDevice(c->device));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool ms = ncoef == 8, pf = rows != nullptr;
-    const bool mk = c->mask_face.size() == (size_t)c->B && masked_faces(c) > 0;   // a face carries a mask (hd_mask_faces)
-    if (!pf) n_iters = n;
+// The sampling loop.  Every hd_sample* entry point checks its own arguments, describes the call in a SampleCall (hd_internal.hpp) and runs
+// sample_impl: a sequence of steps that each read the descriptor.  What the descriptor leaves NULL stays NULL in StepState, and the kernels
+// branch on those pointers: hd_sample (ncoef 7) keeps its [n][7] table and one StepState whose x0_hist is NULL, so its launches and their
+// memory traffic are those of a single-step-only build; hd_sample_multistep (ncoef 8) sends c7 to its own [n] table and gives every chain's
+// StepState its x0 history.  start_rows (hd_sample_rows*, host [B], already checked): n_iters iterations of the per-face graphs
+// (Chain::graph_rows_*), StepState carries the start rows and hist_first = !resume; without them n_iters = n on the graphs of hd_sample.
+// face_seeds / first (hd_sample_faces*): StepState also carries the faces' Philox keys and first-order flags (in place of hist_first).
+// begin_rows / end_rows (hd_sample_spans): StepState also carries every face's span [begin_f, end_f) of the table -- the face is held from
+// row end_f on and its noise counter starts at begin_f.  The table is the concatenation of the members' schedules, so its FiLM table is as
+// long as all of them together (0.5 MB per row at latent 16).
+// The staging buffer written two calls ago, at least `bytes` large: its copy-done event is the only thing a call ever waits for.  The
+// caller fills it, issues its copies on s and ends with stage_submit.
+static int stage_acquire(hd_ctx* c, size_t bytes, hd_ctx::Stage** out) {
+    auto& sg = c->stage[c->stage_idx ^= 1];
+    const size_t need = (bytes + sizeof(float) - 1) / sizeof(float);
+    if (sg.pending) { HIPCHECK(c, hipEventSynchronize(sg.ev)); sg.pending = false; }
+    if (sg.cap < need) {
+        if (sg.host) (void)hipHostFree(sg.host);
+        sg.host = nullptr; sg.cap = 0;
+        HIPCHECK(c, hipHostMalloc(reinterpret_cast<void**>(&sg.host), need * sizeof(float), hipHostMallocDefault));
+        sg.cap = need;
+    }
+    if (!sg.ev) HIPCHECK(c, hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
+    *out = &sg;
+    return HD_OK;
+}
+static int stage_submit(hd_ctx* c, hd_ctx::Stage* sg, hipStream_t s) {
+    HIPCHECK(c, hipEventRecord(sg->ev, s));
+    sg->pending = true;
+    return HD_OK;
+}
+// a slot list of n entries to `dev`: the caller's array is free on return and nothing waits for the stream
+static int stage_slots(hd_ctx* c, int* dev, const int32_t* slots, int n, hipStream_t s) {
+    hd_ctx::Stage* sg;
+    int rc = stage_acquire(c, (size_t)n * sizeof(int32_t), &sg);
+    if (rc) return rc;
+    memcpy(sg->host, slots, (size_t)n * sizeof(int32_t));
+    HIPCHECK(c, hipMemcpyAsync(dev, sg->host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    return stage_submit(c, sg, s);
+}
+
+static bool any_mask(const hd_ctx* c) { return c->mask_face.size() == (size_t)c->B && masked_faces(c) > 0; }   // hd_mask_faces
+
+static int grow_loop_buffers(hd_ctx* c, const SampleCall& call) {
+    const int n = call.n;
     int rc = ensure_film_rows(c, n);
     if (rc) return rc;
     if (n > c->coef_cap) {
@@ -1144,305 +1170,327 @@ static int sample_impl(hd_ctx* c, float* x_inout, int n, const float* timesteps,
         for (auto& kv : c->ws_cache) kv.second.graphs_valid = false;
         ++c->rows_gen;
     }
-    if (pf && (size_t)c->B * c->film_total > c->film_pf_cap) {   // the per-face graphs hold this pointer
+    if (call.start_rows && (size_t)c->B * c->film_total > c->film_pf_cap) {   // the per-face graphs hold this pointer
         dev_free(c, c->film_pf);
         rc = dev_alloc(c, &c->film_pf, (size_t)c->B * c->film_total);
         if (rc) return rc;
         c->film_pf_cap = (size_t)c->B * c->film_total;
         ++c->rows_gen;
     }
-    if ((face_seeds || first) && c->B > c->faces_cap) {   // read through StepState: no graph holds these pointers
-        dev_free(c, c->seeds_dev); dev_free(c, c->first_dev);
-        c->seeds_dev = nullptr; c->first_dev = nullptr; c->faces_cap = 0;
-        rc = dev_alloc(c, &c->seeds_dev, (size_t)c->B);
-        if (!rc) rc = dev_alloc(c, &c->first_dev, (size_t)c->B);
+    if (call.start_rows && c->B > c->faces_cap) {         // read through StepState and by the gather launch: no graph holds this pointer
+        dev_free(c, c->faces_dev);
+        c->faces_dev = nullptr; c->faces_cap = 0;
+        rc = dev_alloc(c, &c->faces_dev, (size_t)c->B * kFaceArgBytes / sizeof(*c->faces_dev));
         if (rc) return rc;
         c->faces_cap = c->B;
     }
-    if (pf && c->B > c->rows_cap) {                       // read through StepState: no graph holds this pointer
-        dev_free(c, c->rows_dev);
-        rc = dev_alloc(c, &c->rows_dev, (size_t)c->B);
-        if (rc) return rc;
-        c->rows_cap = c->B;
-    }
-    if (begins && c->B > c->spans_cap) {                  // read through StepState: no graph holds this pointer
-        dev_free(c, c->spans_dev);
-        c->spans_dev = nullptr; c->spans_cap = 0;
-        rc = dev_alloc(c, &c->spans_dev, 2 * (size_t)c->B);
-        if (rc) return rc;
-        c->spans_cap = c->B;
-    }
-    if (ms && n > c->c7_cap) {                            // read through StepState: no graph holds this pointer
+    if (call.ncoef == 8 && n > c->c7_cap) {               // read through StepState: no graph holds this pointer
         dev_free(c, c->c7_dev);
         rc = dev_alloc(c, &c->c7_dev, (size_t)n);
         if (rc) return rc;
         c->c7_cap = n;
     }
-    const size_t per_face = (size_t)4 * c->L * c->L;
-    const size_t nlat = (size_t)c->B * per_face;
-    // schedule and loop state (step = -1: each chain's intro kernel pre-increments) go through a pinned staging buffer of
-    // the context, so the caller's host arrays are free on return and nothing here waits for the stream.
-    // Layout: coef [n][7] | timesteps [n] | StepState (single-step), or coef | timesteps | c7 [n] | one StepState per chain
-    // (multistep, per-face rows or masks) | start rows [B] (per-face rows) | Philox keys [B] (2 words each) | first-order flags [B] (per-face keys /
-    // flags) | begin rows [B] | end rows [B] (spans).
+    return HD_OK;
+}
+
+// Schedule and loop state (step = -1: each chain's intro kernel pre-increments) go through the pinned staging buffer, so the caller's
+// host arrays are free on return and nothing here waits for the stream.  Regions, in order: coef [n][7] | timesteps [n] | c7 [n]
+// (multistep) | one StepState (single-step, whole batch, no masks) or one per chain | the per-face argument block (per-face calls).
+static int stage_loop_state(hd_ctx* c, const SampleCall& call, bool upload_timesteps, hipStream_t s) {
+    const int n = call.n;
+    const bool ms = call.ncoef == 8, pf = call.start_rows != nullptr;
+    const bool mk = any_mask(c);
+    const size_t nst = (ms || pf || mk) ? c->chains.size() : 1;
+    StageCursor cur;
+    const size_t coef0 = cur.take((size_t)n * 7 * sizeof(float)), ts0 = cur.take((size_t)n * sizeof(float));
+    const size_t c70 = cur.take(ms ? (size_t)n * sizeof(float) : 0), st0 = cur.take(nst * sizeof(StepState));
+    const size_t faces0 = cur.take(pf ? (size_t)c->B * kFaceArgBytes : 0);
+    hd_ctx::Stage* sg;
+    int rc = stage_acquire(c, cur.at, &sg);
+    if (rc) return rc;
+    char* host = reinterpret_cast<char*>(sg->host);
+    float* hcoef = reinterpret_cast<float*>(host + coef0);
     StepState st{};
-    st.step = -1; st.n_steps = n; st.noise = noise; st.seed = seed;
-    {
-        auto& sg = c->stage[c->stage_idx ^= 1];
-        const size_t st_f = (sizeof(StepState) + 3) / 4, st0 = (size_t)n * (ms ? 9 : 8);
-        const size_t nst = (ms || pf || mk) ? c->chains.size() : 1, rows0 = st0 + st_f * nst;
-        const size_t seeds0 = rows0 + (pf ? (size_t)c->B : 0), first0 = seeds0 + (face_seeds ? 2 * (size_t)c->B : 0);
-        const size_t spans0 = first0 + (first ? (size_t)c->B : 0);
-        const size_t need = spans0 + (begins ? 2 * (size_t)c->B : 0);
-        if (sg.pending) { HIPCHECK(c, hipEventSynchronize(sg.ev)); sg.pending = false; }     // the copy issued two calls ago
-        if (sg.cap < need) {
-            if (sg.host) (void)hipHostFree(sg.host);
-            sg.host = nullptr; sg.cap = 0;
-            HIPCHECK(c, hipHostMalloc(reinterpret_cast<void**>(&sg.host), need * sizeof(float), hipHostMallocDefault));
-            sg.cap = need;
+    st.step = -1; st.n_steps = n; st.noise = call.noise; st.seed = call.seed;
+    if (!ms) {
+        memcpy(hcoef, call.coef, (size_t)n * 7 * sizeof(float));
+    } else {
+        float* hc7 = reinterpret_cast<float*>(host + c70);
+        for (int i = 0; i < n; ++i) {
+            memcpy(hcoef + (size_t)i * 7, call.coef + (size_t)i * 8, 7 * sizeof(float));
+            hc7[i] = call.coef[(size_t)i * 8 + 7];
         }
-        if (!sg.ev) HIPCHECK(c, hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
-        if (!ms) {
-            memcpy(sg.host, coef, (size_t)n * 7 * sizeof(float));
-        } else {
-            for (int i = 0; i < n; ++i) {
-                memcpy(sg.host + (size_t)i * 7, coef + (size_t)i * 8, 7 * sizeof(float));
-                sg.host[(size_t)n * 8 + i] = coef[(size_t)i * 8 + 7];
-            }
-            st.c7 = c->c7_dev;
-            HIPCHECK(c, hipMemcpyAsync(c->c7_dev, sg.host + (size_t)n * 8, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+        st.c7 = c->c7_dev;
+        HIPCHECK(c, hipMemcpyAsync(c->c7_dev, hc7, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+    }
+    memcpy(host + ts0, call.timesteps, (size_t)n * sizeof(float));
+    if (pf) st.hist_first = call.resume ? 0 : 1;
+    const FaceArgs dev = face_args(c->faces_dev, c->B);    // only the arrays the call gave are handed on
+    for (size_t k = 0; k < nst; ++k) {
+        const size_t f0 = (size_t)c->chains[k].face0;
+        if (ms) st.x0_hist = c->chains[k].x0_hist;
+        if (pf) st.start_rows = dev.rows + f0;
+        if (call.face_seeds) st.face_seeds = dev.seeds + f0;
+        if (call.first) st.face_first = dev.first + f0;
+        if (call.begin_rows) { st.begin_rows = dev.begins + f0; st.end_rows = dev.ends + f0; }
+        if (mk) {
+            const size_t ll = (size_t)c->L * c->L;
+            st.mask = c->mask_dev + f0 * ll; st.mask_known = c->mask_known_dev + f0 * 4 * ll;
+            st.mask_noise = c->mask_noise_dev + f0 * 4 * ll; st.mask_on = c->mask_on_dev + f0;
         }
-        if (pf) st.hist_first = resume ? 0 : 1;
-        for (size_t k = 0; k < nst; ++k) {
-            if (ms) st.x0_hist = c->chains[k].x0_hist;
-            if (pf) st.start_rows = c->rows_dev + c->chains[k].face0;
-            if (face_seeds) st.face_seeds = c->seeds_dev + c->chains[k].face0;
-            if (first) st.face_first = c->first_dev + c->chains[k].face0;
-            if (begins) { st.begin_rows = c->spans_dev + c->chains[k].face0; st.end_rows = c->spans_dev + c->spans_cap + c->chains[k].face0; }
-            if (mk) {
-                const size_t f0 = (size_t)c->chains[k].face0, ll = (size_t)c->L * c->L;
-                st.mask = c->mask_dev + f0 * ll; st.mask_known = c->mask_known_dev + f0 * 4 * ll;
-                st.mask_noise = c->mask_noise_dev + f0 * 4 * ll; st.mask_on = c->mask_on_dev + f0;
-            }
-            memcpy(sg.host + st0 + k * st_f, &st, sizeof(st));
-        }
-        if (pf) {
-            memcpy(sg.host + rows0, rows, (size_t)c->B * sizeof(int32_t));
-            HIPCHECK(c, hipMemcpyAsync(c->rows_dev, sg.host + rows0, (size_t)c->B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        }
-        if (face_seeds) {
-            memcpy(sg.host + seeds0, face_seeds, (size_t)c->B * sizeof(uint64_t));
-            HIPCHECK(c, hipMemcpyAsync(c->seeds_dev, sg.host + seeds0, (size_t)c->B * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        }
-        if (first) {
-            memcpy(sg.host + first0, first, (size_t)c->B * sizeof(int32_t));
-            HIPCHECK(c, hipMemcpyAsync(c->first_dev, sg.host + first0, (size_t)c->B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        }
-        if (begins) {
-            memcpy(sg.host + spans0, begins, (size_t)c->B * sizeof(int32_t));
-            memcpy(sg.host + spans0 + c->B, ends, (size_t)c->B * sizeof(int32_t));
-            HIPCHECK(c, hipMemcpyAsync(c->spans_dev, sg.host + spans0, (size_t)c->B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            HIPCHECK(c, hipMemcpyAsync(c->spans_dev + c->spans_cap, sg.host + spans0 + c->B, (size_t)c->B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        }
-        memcpy(sg.host + (size_t)n * 7, timesteps, (size_t)n * sizeof(float));
-        HIPCHECK(c, hipMemcpyAsync(c->coef_dev, sg.host, (size_t)n * 7 * sizeof(float), hipMemcpyHostToDevice, s));
-        for (size_t k = 0; k < c->chains.size(); ++k)
-            HIPCHECK(c, hipMemcpyAsync(c->chains[k].step_state, sg.host + st0 + (nst > 1 ? k * st_f : 0), sizeof(st), hipMemcpyHostToDevice, s));
-        const bool same_sched = c->film_valid && c->film_sched.size() == (size_t)n &&
-                                memcmp(c->film_sched.data(), timesteps, (size_t)n * sizeof(float)) == 0;
-        if (!same_sched) HIPCHECK(c, hipMemcpyAsync(c->t_dev, sg.host + (size_t)n * 7, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
-        HIPCHECK(c, hipEventRecord(sg.ev, s));
-        sg.pending = true;
-        HIPCHECK(c, hipMemcpyAsync(c->lat, x_inout, nlat * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if (!same_sched) {                                // FiLM table of the whole schedule (0.5 GB at 1000 steps): once per schedule
-            c->film_valid = false;
-            rc = compute_film(c, c->t_dev, n, s);
-            if (rc) return rc;
-            if (!c->film_ev) HIPCHECK(c, hipEventCreateWithFlags(&c->film_ev, hipEventDisableTiming));
-            HIPCHECK(c, hipEventRecord(c->film_ev, s));
-            c->film_sched.assign(timesteps, timesteps + n);
-            c->film_valid = true;
-        } else {
-            HIPCHECK(c, hipStreamWaitEvent(s, c->film_ev, 0));       // no-op on the stream that computed it
-        }
+        memcpy(host + st0 + k * sizeof(StepState), &st, sizeof(st));
+    }
+    if (pf) {                                             // one upload; an array the call did not give is zero and nothing reads it
+        const FaceArgs h = face_args(host + faces0, c->B);
+        const size_t B = (size_t)c->B;
+        memset(host + faces0, 0, B * kFaceArgBytes);
+        memcpy(h.rows, call.start_rows, B * sizeof(int32_t));
+        if (call.face_seeds) memcpy(h.seeds, call.face_seeds, B * sizeof(uint64_t));
+        if (call.first) memcpy(h.first, call.first, B * sizeof(int32_t));
+        if (call.begin_rows) { memcpy(h.begins, call.begin_rows, B * sizeof(int32_t)); memcpy(h.ends, call.end_rows, B * sizeof(int32_t)); }
+        HIPCHECK(c, hipMemcpyAsync(c->faces_dev, host + faces0, B * kFaceArgBytes, hipMemcpyHostToDevice, s));
+    }
+    HIPCHECK(c, hipMemcpyAsync(c->coef_dev, hcoef, (size_t)n * 7 * sizeof(float), hipMemcpyHostToDevice, s));
+    for (size_t k = 0; k < c->chains.size(); ++k)
+        HIPCHECK(c, hipMemcpyAsync(c->chains[k].step_state, host + st0 + (nst > 1 ? k : 0) * sizeof(StepState), sizeof(st), hipMemcpyHostToDevice, s));
+    if (upload_timesteps) HIPCHECK(c, hipMemcpyAsync(c->t_dev, host + ts0, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+    return stage_submit(c, sg, s);
+}
+
+// The FiLM table of the whole schedule (0.5 GB at 1000 steps) is computed once per schedule from t_dev; then the row(s) of the first
+// iteration are staged: the ending launch of iteration i stages those of iteration i + 1.
+static int film_for_call(hd_ctx* c, const SampleCall& call, bool reuse, hipStream_t s) {
+    if (!reuse) {
+        c->film_valid = false;
+        int rc = compute_film(c, c->t_dev, call.n, s);
+        if (rc) return rc;
+        if (!c->film_ev) HIPCHECK(c, hipEventCreateWithFlags(&c->film_ev, hipEventDisableTiming));
+        HIPCHECK(c, hipEventRecord(c->film_ev, s));
+        c->film_sched.assign(call.timesteps, call.timesteps + call.n);
+        c->film_valid = true;
+    } else {
+        HIPCHECK(c, hipStreamWaitEvent(s, c->film_ev, 0));       // no-op on the stream that computed it
     }
     c->film_step_stride = c->film_total;
     c->film_face_stride = 0;
     c->film_from_cur = true;
     c->advance = 1;
-    if (pf) {                                           // every face's first row; the ending launch of iteration i stages rows r_f + i + 1
-        hipLaunchKernelGGL(film_rows_gather_kernel, dim3(8, c->B), dim3(256), 0, s, c->film_pf, c->film_table, c->rows_dev,
-                           begins ? c->spans_dev + c->spans_cap : nullptr, n, c->film_total);
+    if (call.start_rows) {                                // every face's row r_f (clamped to its last row)
+        const FaceArgs dev = face_args(c->faces_dev, c->B);
+        hipLaunchKernelGGL(film_rows_gather_kernel, dim3(8, c->B), dim3(256), 0, s, c->film_pf, c->film_table, dev.rows,
+                           call.end_rows ? dev.ends : nullptr, call.n, c->film_total);
         HIPCHECK(c, hipGetLastError());
     } else {
-        for (auto& ch : c->chains)                      // step 0's row; the ending launch of step i stages row i+1
+        for (auto& ch : c->chains)                      // row 0
             HIPCHECK(c, hipMemcpyAsync(ch.film_cur, c->film_table, (size_t)c->film_total * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
+    return HD_OK;
+}
+
+// One graph pair per chain: its launch program + its scheduler update, one step and kGraphSteps steps back to back (fewer graph
+// launches).  Faces never interact, so the chains are independent over the whole loop and each graph is replayed on the chain's own
+// stream.  pf: the per-face pair (Chain::graph_rows_*) -- the LayerNorm loaders read film_pf with a face stride while the program is
+// captured.  Nothing is captured while the pair asked for is current.
+static int capture_step_graphs(hd_ctx* c, bool pf) {
     bool stale = !c->graphs_valid || c->graph_film != c->film_table || c->graph_B != c->B;
     if (pf) {
         stale = false;
         for (auto& ch : c->chains) stale |= !ch.graph_rows_exec || ch.rows_gen != c->rows_gen || ch.rows_film != c->film_table;
     }
-    if (stale) {
-        // One graph per chain: its launch program + its scheduler update.  Faces never interact, so the
-        // chains are independent over the whole loop and each graph is replayed on the chain's own stream.
-        // (per-face rows: the LayerNorm loaders read film_pf with a face stride while the program is captured)
-        if (pf) { c->film_pf_mode = true; c->film_face_stride = c->film_total; }
-        c->stage_count = c->face_stage_count = 0;
-        for (auto& ch : c->chains) {
-            hipGraphExec_t& g1 = pf ? ch.graph_rows_exec : ch.graph_exec;
-            hipGraphExec_t& gm = pf ? ch.graph_rows_multi : ch.graph_multi;
-            if (g1) { (void)hipGraphExecDestroy(g1); g1 = nullptr; }
-            if (gm) { (void)hipGraphExecDestroy(gm); gm = nullptr; }
-            for (int multi = 0; multi < 2; ++multi) {       // one step, and kGraphSteps steps back to back (fewer graph launches)
-                hipGraph_t graph = nullptr;
-                hipError_t e = hipStreamBeginCapture(ch.stream, hipStreamCaptureModeThreadLocal);
-                if (e == hipSuccess) {
-                    for (int r = 0; r < (multi ? graph_steps() : 1) && e == hipSuccess; ++r)
-                        for (size_t k = 0; k < ch.program.size() && e == hipSuccess; ++k) e = ch.program[k].run(ch.stream);
-                    hipError_t e2 = hipStreamEndCapture(ch.stream, &graph);
-                    if (e == hipSuccess) e = e2;
-                }
-                if (e == hipSuccess) e = hipGraphInstantiate(multi ? &gm : &g1, graph, nullptr, nullptr, 0);
-                if (e == hipSuccess) ++c->graph_captures;
-                if (graph) (void)hipGraphDestroy(graph);
-                if (e != hipSuccess) { c->film_pf_mode = false; c->film_face_stride = 0; HD_FAIL(c, HD_ERR_HIP, "graph capture/instantiate failed: %s", hipGetErrorString(e)); }
-                if (multi == 0 && &ch == &c->chains[0]) {      // the one-step program of chain 0: what hd_get_option reports
-                    (pf ? c->rows_stages : c->sample_stages) = c->stage_count;
-                    if (!pf) c->sample_face_stages = c->face_stage_count;
-                }
+    if (!stale) return HD_OK;
+    if (pf) { c->film_pf_mode = true; c->film_face_stride = c->film_total; }
+    c->stage_count = c->face_stage_count = 0;
+    for (auto& ch : c->chains) {
+        hipGraphExec_t& g1 = pf ? ch.graph_rows_exec : ch.graph_exec;
+        hipGraphExec_t& gm = pf ? ch.graph_rows_multi : ch.graph_multi;
+        if (g1) { (void)hipGraphExecDestroy(g1); g1 = nullptr; }
+        if (gm) { (void)hipGraphExecDestroy(gm); gm = nullptr; }
+        for (int multi = 0; multi < 2; ++multi) {
+            hipGraph_t graph = nullptr;
+            hipError_t e = hipStreamBeginCapture(ch.stream, hipStreamCaptureModeThreadLocal);
+            if (e == hipSuccess) {
+                for (int r = 0; r < (multi ? graph_steps() : 1) && e == hipSuccess; ++r)
+                    for (size_t k = 0; k < ch.program.size() && e == hipSuccess; ++k) e = ch.program[k].run(ch.stream);
+                hipError_t e2 = hipStreamEndCapture(ch.stream, &graph);
+                if (e == hipSuccess) e = e2;
             }
-            if (pf) { ch.rows_gen = c->rows_gen; ch.rows_film = c->film_table; }
+            if (e == hipSuccess) e = hipGraphInstantiate(multi ? &gm : &g1, graph, nullptr, nullptr, 0);
+            if (e == hipSuccess) ++c->graph_captures;
+            if (graph) (void)hipGraphDestroy(graph);
+            if (e != hipSuccess) { c->film_pf_mode = false; c->film_face_stride = 0; HD_FAIL(c, HD_ERR_HIP, "graph capture/instantiate failed: %s", hipGetErrorString(e)); }
+            if (multi == 0 && &ch == &c->chains[0]) {      // the one-step program of chain 0: what hd_get_option reports
+                (pf ? c->rows_stages : c->sample_stages) = c->stage_count;
+                if (!pf) c->sample_face_stages = c->face_stage_count;
+            }
         }
-        c->film_pf_mode = false; c->film_face_stride = 0;
-        if (!pf) { c->graphs_valid = true; c->graph_film = c->film_table; c->graph_B = c->B; }
+        if (pf) { ch.rows_gen = c->rows_gen; ch.rows_film = c->film_table; }
     }
+    c->film_pf_mode = false; c->film_face_stride = 0;
+    if (!pf) { c->graphs_valid = true; c->graph_film = c->film_table; c->graph_B = c->B; }
+    return HD_OK;
+}
+
+static int replay_step_graphs(hd_ctx* c, bool pf, int n_iters, hipStream_t s) {
     if (c->profiling) HIPCHECK(c, hipEventRecord(c->ev0, s));
     HIPCHECK(c, hipEventRecord(c->fork_ev, s));
     for (auto& ch : c->chains) HIPCHECK(c, hipStreamWaitEvent(ch.stream, c->fork_ev, 0));
-    {
-        int i = 0;
-        for (; i + graph_steps() <= n_iters; i += graph_steps())
-            for (auto& ch : c->chains) HIPCHECK(c, hipGraphLaunch(pf ? ch.graph_rows_multi : ch.graph_multi, ch.stream));
-        for (; i < n_iters; ++i)
-            for (auto& ch : c->chains) HIPCHECK(c, hipGraphLaunch(pf ? ch.graph_rows_exec : ch.graph_exec, ch.stream));
-    }
+    int i = 0;
+    for (; i + graph_steps() <= n_iters; i += graph_steps())
+        for (auto& ch : c->chains) HIPCHECK(c, hipGraphLaunch(pf ? ch.graph_rows_multi : ch.graph_multi, ch.stream));
+    for (; i < n_iters; ++i)
+        for (auto& ch : c->chains) HIPCHECK(c, hipGraphLaunch(pf ? ch.graph_rows_exec : ch.graph_exec, ch.stream));
     for (auto& ch : c->chains) {
         HIPCHECK(c, hipEventRecord(ch.done, ch.stream));
         HIPCHECK(c, hipStreamWaitEvent(s, ch.done, 0));
     }
     if (c->profiling) { HIPCHECK(c, hipEventRecord(c->ev1, s)); c->last_steps = n_iters; }
-    // what a later hd_sample_rows_multistep(resume = 1) may continue, and per face what hd_sample_faces_multistep(resume[f] = 1) may:
-    // a whole-batch call leaves every face's history (multistep) or none; a multistep rows / faces call that of every face that ran a row
+    return HD_OK;
+}
+
+// What a later hd_sample_rows_multistep(resume = 1) may continue, and per face what hd_sample_faces_multistep / hd_sample_spans
+// (resume[f] = 1) may: a whole-batch call leaves every face's history (multistep) or none; a multistep per-face call that of every face
+// that ran a row.  hist_valid after a rows-multistep call holds regardless of held faces; after a call with per-face flags
+// (faces / spans) only when every face has a history.
+static void record_history(hd_ctx* c, const SampleCall& call) {
+    const bool ms = call.ncoef == 8;
     if (c->hist_B != c->B || c->hist_face.size() != (size_t)c->B) c->hist_face.assign((size_t)c->B, 0);
-    if (ms && pf) {
-        for (int f = 0; f < c->B; ++f) if (rows[f] < (ends ? ends[f] : n)) c->hist_face[f] = 1;
+    if (ms && call.start_rows) {
+        for (int f = 0; f < c->B; ++f) if (call.start_rows[f] < (call.end_rows ? call.end_rows[f] : call.n)) c->hist_face[f] = 1;
     } else {
         c->hist_face.assign((size_t)c->B, ms ? 1 : 0);
     }
     c->hist_valid = ms; c->hist_B = c->B;
-    if (ms && first) for (char h : c->hist_face) c->hist_valid = c->hist_valid && h;   // hd_sample_faces_multistep: only when every face has one
+    if (ms && call.first) for (char h : c->hist_face) c->hist_valid = c->hist_valid && h;
+}
+
+static int sample_impl(hd_ctx* c, float* x_inout, const SampleCall& call, void* stream) {
+    HIPCHECK(c, hipSetDevice(c->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const bool pf = call.start_rows != nullptr;
+    const int n_iters = pf ? call.n_iters : call.n;
+    const size_t nlat = (size_t)c->B * 4 * c->L * c->L;
+    int rc = grow_loop_buffers(c, call);
+    if (rc) return rc;
+    const bool reuse_film = c->film_valid && c->film_sched.size() == (size_t)call.n &&
+                            memcmp(c->film_sched.data(), call.timesteps, (size_t)call.n * sizeof(float)) == 0;
+    rc = stage_loop_state(c, call, !reuse_film, s);
+    if (rc) return rc;
+    HIPCHECK(c, hipMemcpyAsync(c->lat, x_inout, nlat * sizeof(float), hipMemcpyDeviceToDevice, s));
+    rc = film_for_call(c, call, reuse_film, s);
+    if (!rc) rc = capture_step_graphs(c, pf);
+    if (!rc) rc = replay_step_graphs(c, pf, n_iters, s);
+    if (rc) return rc;
+    record_history(c, call);
     rc = poison_on_abort(c, c->lat, nlat, s);
     if (rc) return rc;
     HIPCHECK(c, hipMemcpyAsync(x_inout, c->lat, nlat * sizeof(float), hipMemcpyDeviceToDevice, s));
     return HD_OK;
 }
 
-int hd_sample(hd_ctx* c, float* x_inout, const hd_schedule* sched, const float* noise, uint64_t seed, void* stream) {
+// What every sampling entry point opens with: the context is ready and no stage of an earlier call gave up, the latents and the table
+// are there (args_ok: the entry point's other required arguments are, too); then the table goes into the descriptor.
+static int sample_enter(hd_ctx* c, const char* fn, const float* x, const hd_schedule* sched, int ncoef, bool args_ok, const float* noise,
+                        uint64_t seed, SampleCall& call) {
     int rc = check_ready(c, true);
     if (rc) return rc;
     rc = check_xcd(c);
     if (rc) return rc;
-    if (!x_inout || !sched || sched->n_steps <= 0 || !sched->timesteps || !sched->coef) HD_FAIL(c, HD_ERR_INVALID, "hd_sample: bad arguments");
-    return sample_impl(c, x_inout, sched->n_steps, sched->timesteps, sched->coef, 7, noise, seed, stream);
+    if (!x || !sched || sched->n_steps <= 0 || !sched->timesteps || !sched->coef || !args_ok) HD_FAIL(c, HD_ERR_INVALID, "%s: bad arguments", fn);
+    call.fn = fn;
+    call.n = sched->n_steps; call.timesteps = sched->timesteps; call.coef = sched->coef;
+    call.ncoef = ncoef;
+    call.noise = noise; call.seed = seed;
+    return HD_OK;
+}
+
+// hd_schedule_ms is hd_schedule with 8 coefficients per row
+static const hd_schedule* as_rows_of_8(const hd_schedule_ms* s) { return reinterpret_cast<const hd_schedule*>(s); }
+static_assert(sizeof(hd_schedule) == sizeof(hd_schedule_ms), "the two schedule structs share one layout");
+
+// start rows in [0, n], n_iters in [1, n - min r_f]; then they go into the descriptor
+static int check_rows(hd_ctx* c, SampleCall& call, const int32_t* rows, int n_iters) {
+    const int n = call.n;
+    int rmin = n;
+    for (int f = 0; f < c->B; ++f) {
+        if (rows[f] < 0 || rows[f] > n) HD_FAIL(c, HD_ERR_INVALID, "%s: start_rows[%d] = %d outside [0, %d]", call.fn, f, rows[f], n);
+        if (rows[f] < rmin) rmin = rows[f];
+    }
+    if (n_iters < 1 || n_iters > n - rmin) HD_FAIL(c, HD_ERR_INVALID, "%s: n_iters = %d outside [1, %d]", call.fn, n_iters, n - rmin);
+    call.start_rows = rows; call.n_iters = n_iters;
+    return HD_OK;
+}
+
+// resume[f] of hd_sample_faces_multistep / hd_sample_spans: 0 or 1, and 1 only for a face that has a history; first_f = !resume_f
+static int check_face_resume(hd_ctx* c, const char* fn, int f, int32_t resume_f, int32_t* first_f) {
+    if (resume_f != 0 && resume_f != 1) HD_FAIL(c, HD_ERR_INVALID, "%s: resume[%d] = %d is not 0 or 1", fn, f, resume_f);
+    const bool have = c->hist_B == c->B && c->hist_face.size() == (size_t)c->B;
+    if (resume_f && !(have && c->hist_face[f]))
+        HD_FAIL(c, HD_ERR_INVALID, "%s: resume[%d] = 1 but face %d has no multistep history (no multistep row since "
+                                   "hd_prepare*, hd_prepare_slots refilled it, or a single-step call in between)", fn, f, f);
+    *first_f = resume_f ? 0 : 1;
+    return HD_OK;
+}
+
+int hd_sample(hd_ctx* c, float* x_inout, const hd_schedule* sched, const float* noise, uint64_t seed, void* stream) {
+    SampleCall call;
+    int rc = sample_enter(c, "hd_sample", x_inout, sched, 7, true, noise, seed, call);
+    return rc ? rc : sample_impl(c, x_inout, call, stream);
 }
 
 int hd_sample_multistep(hd_ctx* c, float* x_inout, const hd_schedule_ms* sched, const float* noise, uint64_t seed, void* stream) {
-    int rc = check_ready(c, true);
+    SampleCall call;
+    int rc = sample_enter(c, "hd_sample_multistep", x_inout, as_rows_of_8(sched), 8, true, noise, seed, call);
     if (rc) return rc;
-    rc = check_xcd(c);
-    if (rc) return rc;
-    if (!x_inout || !sched || sched->n_steps <= 0 || !sched->timesteps || !sched->coef)
-        HD_FAIL(c, HD_ERR_INVALID, "hd_sample_multistep: bad arguments");
     // the first step has no previous x0: the history of the call starts there (never inherited from an earlier call)
     if (sched->coef[7] != 0.f) HD_FAIL(c, HD_ERR_INVALID, "hd_sample_multistep: row 0 must have c7 == 0 (no history before the first step)");
-    return sample_impl(c, x_inout, sched->n_steps, sched->timesteps, sched->coef, 8, noise, seed, stream);
-}
-
-// start rows in [0, n], n_iters in [1, n - min r_f]
-static int check_rows(hd_ctx* c, const char* fn, int n, const int32_t* rows, int n_iters) {
-    int rmin = n;
-    for (int f = 0; f < c->B; ++f) {
-        if (rows[f] < 0 || rows[f] > n) HD_FAIL(c, HD_ERR_INVALID, "%s: start_rows[%d] = %d outside [0, %d]", fn, f, rows[f], n);
-        if (rows[f] < rmin) rmin = rows[f];
-    }
-    if (n_iters < 1 || n_iters > n - rmin) HD_FAIL(c, HD_ERR_INVALID, "%s: n_iters = %d outside [1, %d]", fn, n_iters, n - rmin);
-    return HD_OK;
+    return sample_impl(c, x_inout, call, stream);
 }
 
 int hd_sample_rows(hd_ctx* c, float* x_inout, const hd_schedule* sched, const int32_t* start_rows, int n_iters, const float* noise,
                    uint64_t seed, void* stream) {
-    int rc = check_ready(c, true);
+    SampleCall call;
+    int rc = sample_enter(c, "hd_sample_rows", x_inout, sched, 7, start_rows != nullptr, noise, seed, call);
+    if (!rc) rc = check_rows(c, call, start_rows, n_iters);
     if (rc) return rc;
-    rc = check_xcd(c);
-    if (rc) return rc;
-    if (!x_inout || !sched || sched->n_steps <= 0 || !sched->timesteps || !sched->coef || !start_rows)
-        HD_FAIL(c, HD_ERR_INVALID, "hd_sample_rows: bad arguments");
-    rc = check_rows(c, "hd_sample_rows", sched->n_steps, start_rows, n_iters);
-    if (rc) return rc;
-    return sample_impl(c, x_inout, sched->n_steps, sched->timesteps, sched->coef, 7, noise, seed, stream, start_rows, n_iters, 0);
+    return sample_impl(c, x_inout, call, stream);
 }
 
 int hd_sample_rows_multistep(hd_ctx* c, float* x_inout, const hd_schedule_ms* sched, const int32_t* start_rows, int n_iters, int resume,
                              const float* noise, uint64_t seed, void* stream) {
-    int rc = check_ready(c, true);
-    if (rc) return rc;
-    rc = check_xcd(c);
-    if (rc) return rc;
-    if (!x_inout || !sched || sched->n_steps <= 0 || !sched->timesteps || !sched->coef || !start_rows || (resume != 0 && resume != 1))
-        HD_FAIL(c, HD_ERR_INVALID, "hd_sample_rows_multistep: bad arguments");
-    rc = check_rows(c, "hd_sample_rows_multistep", sched->n_steps, start_rows, n_iters);
+    SampleCall call;
+    int rc = sample_enter(c, "hd_sample_rows_multistep", x_inout, as_rows_of_8(sched), 8, start_rows && (resume == 0 || resume == 1), noise, seed, call);
+    if (!rc) rc = check_rows(c, call, start_rows, n_iters);
     if (rc) return rc;
     if (resume && !(c->hist_valid && c->hist_B == c->B))
         HD_FAIL(c, HD_ERR_INVALID, "hd_sample_rows_multistep: resume = 1 but no multistep history of this batch (no earlier multistep call, "
                                    "hd_prepare since, another batch size or a single-step call in between)");
-    return sample_impl(c, x_inout, sched->n_steps, sched->timesteps, sched->coef, 8, noise, seed, stream, start_rows, n_iters, resume);
+    call.resume = resume;
+    return sample_impl(c, x_inout, call, stream);
 }
 
 int hd_sample_faces(hd_ctx* c, float* x_inout, const hd_schedule* sched, const int32_t* start_rows, int n_iters, const uint64_t* face_seeds,
                     const float* noise, uint64_t seed, void* stream) {
-    int rc = check_ready(c, true);
+    SampleCall call;
+    int rc = sample_enter(c, "hd_sample_faces", x_inout, sched, 7, start_rows != nullptr, noise, seed, call);
+    if (!rc) rc = check_rows(c, call, start_rows, n_iters);
     if (rc) return rc;
-    rc = check_xcd(c);
-    if (rc) return rc;
-    if (!x_inout || !sched || sched->n_steps <= 0 || !sched->timesteps || !sched->coef || !start_rows)
-        HD_FAIL(c, HD_ERR_INVALID, "hd_sample_faces: bad arguments");
-    rc = check_rows(c, "hd_sample_faces", sched->n_steps, start_rows, n_iters);
-    if (rc) return rc;
-    return sample_impl(c, x_inout, sched->n_steps, sched->timesteps, sched->coef, 7, noise, seed, stream, start_rows, n_iters, 0, face_seeds);
+    call.face_seeds = face_seeds;
+    return sample_impl(c, x_inout, call, stream);
 }
 
 int hd_sample_faces_multistep(hd_ctx* c, float* x_inout, const hd_schedule_ms* sched, const int32_t* start_rows, int n_iters,
                               const int32_t* resume, const uint64_t* face_seeds, const float* noise, uint64_t seed, void* stream) {
-    int rc = check_ready(c, true);
+    SampleCall call;
+    int rc = sample_enter(c, "hd_sample_faces_multistep", x_inout, as_rows_of_8(sched), 8, start_rows && resume, noise, seed, call);
+    if (!rc) rc = check_rows(c, call, start_rows, n_iters);
     if (rc) return rc;
-    rc = check_xcd(c);
-    if (rc) return rc;
-    if (!x_inout || !sched || sched->n_steps <= 0 || !sched->timesteps || !sched->coef || !start_rows || !resume)
-        HD_FAIL(c, HD_ERR_INVALID, "hd_sample_faces_multistep: bad arguments");
-    rc = check_rows(c, "hd_sample_faces_multistep", sched->n_steps, start_rows, n_iters);
-    if (rc) return rc;
-    const bool have = c->hist_B == c->B && c->hist_face.size() == (size_t)c->B;
     std::vector<int32_t> first((size_t)c->B);
     for (int f = 0; f < c->B; ++f) {
-        if (resume[f] != 0 && resume[f] != 1) HD_FAIL(c, HD_ERR_INVALID, "hd_sample_faces_multistep: resume[%d] = %d is not 0 or 1", f, resume[f]);
-        if (resume[f] && !(have && c->hist_face[f]))
-            HD_FAIL(c, HD_ERR_INVALID, "hd_sample_faces_multistep: resume[%d] = 1 but face %d has no multistep history (no multistep row since "
-                                       "hd_prepare*, hd_prepare_slots refilled it, or a single-step call in between)", f, f);
-        first[f] = resume[f] ? 0 : 1;
+        rc = check_face_resume(c, call.fn, f, resume[f], &first[f]);
+        if (rc) return rc;
     }
-    return sample_impl(c, x_inout, sched->n_steps, sched->timesteps, sched->coef, 8, noise, seed, stream, start_rows, n_iters, 0, face_seeds,
-                       first.data());
+    call.face_seeds = face_seeds; call.first = first.data();
+    return sample_impl(c, x_inout, call, stream);
 }
 
 // Per-request schedules: `table` is the concatenation of several schedules and face f runs rows start_f, start_f + 1, .. of its own span
@@ -1450,14 +1498,10 @@ int hd_sample_faces_multistep(hd_ctx* c, float* x_inout, const hd_schedule_ms* s
 int hd_sample_spans(hd_ctx* c, float* x_inout, const hd_schedule_ms* table, const int32_t* begin_rows, const int32_t* end_rows,
                     const int32_t* start_rows, int n_iters, const int32_t* resume, const uint64_t* face_seeds, const float* noise,
                     uint64_t seed, void* stream) {
-    int rc = check_ready(c, true);
+    SampleCall call;
+    int rc = sample_enter(c, "hd_sample_spans", x_inout, as_rows_of_8(table), 8, begin_rows && end_rows && start_rows && resume, noise, seed, call);
     if (rc) return rc;
-    rc = check_xcd(c);
-    if (rc) return rc;
-    if (!x_inout || !table || table->n_steps <= 0 || !table->timesteps || !table->coef || !begin_rows || !end_rows || !start_rows || !resume)
-        HD_FAIL(c, HD_ERR_INVALID, "hd_sample_spans: bad arguments");
-    const int n = table->n_steps;
-    const bool have = c->hist_B == c->B && c->hist_face.size() == (size_t)c->B;
+    const int n = call.n;
     std::vector<int32_t> first((size_t)c->B);
     int longest = 0;
     for (int f = 0; f < c->B; ++f) {
@@ -1466,18 +1510,17 @@ int hd_sample_spans(hd_ctx* c, float* x_inout, const hd_schedule_ms* table, cons
             HD_FAIL(c, HD_ERR_INVALID, "hd_sample_spans: face %d: need 0 <= begin (%d) <= start (%d) <= end (%d) <= n_steps (%d)", f, b, r, e, n);
         if (b < n && table->coef[(size_t)b * 8 + 7] != 0.f)
             HD_FAIL(c, HD_ERR_INVALID, "hd_sample_spans: face %d: row %d begins its schedule and must have c7 == 0 (no history before it)", f, b);
-        if (resume[f] != 0 && resume[f] != 1) HD_FAIL(c, HD_ERR_INVALID, "hd_sample_spans: resume[%d] = %d is not 0 or 1", f, resume[f]);
-        if (resume[f] && r == b)
+        if (resume[f] == 1 && r == b)
             HD_FAIL(c, HD_ERR_INVALID, "hd_sample_spans: resume[%d] = 1 but face %d starts at its begin row %d (nothing to resume)", f, f, b);
-        if (resume[f] && !(have && c->hist_face[f]))
-            HD_FAIL(c, HD_ERR_INVALID, "hd_sample_spans: resume[%d] = 1 but face %d has no multistep history (no multistep row since "
-                                       "hd_prepare*, hd_prepare_slots refilled it, or a single-step call in between)", f, f);
-        first[f] = resume[f] ? 0 : 1;
+        rc = check_face_resume(c, call.fn, f, resume[f], &first[f]);
+        if (rc) return rc;
         if (e - r > longest) longest = e - r;
     }
     if (n_iters < 1 || n_iters > longest) HD_FAIL(c, HD_ERR_INVALID, "hd_sample_spans: n_iters = %d outside [1, %d]", n_iters, longest);
-    return sample_impl(c, x_inout, n, table->timesteps, table->coef, 8, noise, seed, stream, start_rows, n_iters, 0, face_seeds, first.data(),
-                       begin_rows, end_rows);
+    call.start_rows = start_rows; call.n_iters = n_iters;
+    call.begin_rows = begin_rows; call.end_rows = end_rows;
+    call.face_seeds = face_seeds; call.first = first.data();
+    return sample_impl(c, x_inout, call, stream);
 }
 
 // Replace the conditioning of n slots.  The prologue (FPG, ResNet-50 or the given embedding, HCA gates, idc_conv) runs at batch n on the
@@ -1529,22 +1572,8 @@ int hd_prepare_slots(hd_ctx* c, int n, const int32_t* slots, const float* cr_lat
     if (!cr_face) HIPCHECK(c, hipMemcpyAsync(sc.id_emb, id_emb, (size_t)n * 2048 * sizeof(float), hipMemcpyDeviceToDevice, s));
     rc = run_ops(c, prog, s);
     if (rc) return rc;
-    // slots: through the pinned staging buffer (the caller's array is free on return; nothing waits for the stream)
-    {
-        auto& sg = c->stage[c->stage_idx ^= 1];
-        if (sg.pending) { HIPCHECK(c, hipEventSynchronize(sg.ev)); sg.pending = false; }
-        if (sg.cap < (size_t)n) {
-            if (sg.host) (void)hipHostFree(sg.host);
-            sg.host = nullptr; sg.cap = 0;
-            HIPCHECK(c, hipHostMalloc(reinterpret_cast<void**>(&sg.host), (size_t)n * sizeof(float), hipHostMallocDefault));
-            sg.cap = n;
-        }
-        if (!sg.ev) HIPCHECK(c, hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
-        memcpy(sg.host, slots, (size_t)n * sizeof(int32_t));
-        HIPCHECK(c, hipMemcpyAsync(c->slots_dev, sg.host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIPCHECK(c, hipEventRecord(sg.ev, s));
-        sg.pending = true;
-    }
+    rc = stage_slots(c, c->slots_dev, slots, n, s);
+    if (rc) return rc;
     SlotScatterP p{};
     int b = 0;
     for (int i = 0; i < 5; ++i) {
@@ -1623,20 +1652,9 @@ int hd_mask_faces(hd_ctx* c, int n, const int32_t* slots, const float* mask, con
         HIPCHECK(c, hipMemsetAsync(c->mask_noise_dev, 0, (size_t)c->B * 4 * ll * sizeof(float), s));
         HIPCHECK(c, hipMemsetAsync(c->mask_on_dev, 0, (size_t)c->B * sizeof(int), s));
     }
-    if (slots) {                                           // through the pinned staging buffer, as hd_prepare_slots does
-        auto& sg = c->stage[c->stage_idx ^= 1];
-        if (sg.pending) { HIPCHECK(c, hipEventSynchronize(sg.ev)); sg.pending = false; }
-        if (sg.cap < (size_t)n) {
-            if (sg.host) (void)hipHostFree(sg.host);
-            sg.host = nullptr; sg.cap = 0;
-            HIPCHECK(c, hipHostMalloc(reinterpret_cast<void**>(&sg.host), (size_t)n * sizeof(float), hipHostMallocDefault));
-            sg.cap = n;
-        }
-        if (!sg.ev) HIPCHECK(c, hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
-        memcpy(sg.host, slots, (size_t)n * sizeof(int32_t));
-        HIPCHECK(c, hipMemcpyAsync(c->mask_slots_dev, sg.host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIPCHECK(c, hipEventRecord(sg.ev, s));
-        sg.pending = true;
+    if (slots) {
+        rc = stage_slots(c, c->mask_slots_dev, slots, n, s);
+        if (rc) return rc;
     }
     MaskScatterP p{};
     p.mask = mask; p.known = known; p.noise = known_noise;

@@ -222,84 +222,98 @@ def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, pr
     stage launch gave up during it -- where the reference's loop would have raised (test_refiner.py:89-91), so that the last batch
     of a val_loop cannot end with rc 0 and NaN images.  check=False only enqueues the work (the returned latents are NaN in the
     failing case either way; `model.check()` reports it later).  bench.py times the loop with its own synchronisation."""
-    span_rows = None
+    B = latents.shape[0]
+    rows, spans = start_steps, None
     if isinstance(scheduler, ScheduleSet):                 # argument errors before any device work
-        span_rows = _span_args(scheduler, schedules, start_steps, latents.shape[0])
+        begin, end, rows = _span_args(scheduler, schedules, start_steps, B)
+        spans = (begin, end)
     elif schedules is not None:
         raise ValueError("schedules needs a ScheduleSet as the scheduler")
     if face_seeds is not None:
-        face_seeds = face_seeds_arg(face_seeds, latents.shape[0])
-    if isinstance(resume, torch.Tensor) or span_rows is not None:
-        resume = resume_arg(resume, latents.shape[0])
+        face_seeds = face_seeds_arg(face_seeds, B)
+    if isinstance(resume, torch.Tensor) or spans is not None:
+        resume = resume_arg(resume, B)
     if mask is None and (known is not None or known_noise is not None):
         raise ValueError("known / known_noise need a mask")
     if mask is not None:
         from .refiner import mask_args
-        mask, known, known_noise = mask_args(mask, known, known_noise, latents.shape[0], model.engine.latent_res)
+        mask, known, known_noise = mask_args(mask, known, known_noise, B, model.engine.latent_res)
     e = model.engine
     e.ensure(latents.device)
-    if latents.shape[0] == 0:                              # empty batch: nothing to sample
+    if B == 0:                                             # empty batch: nothing to sample
         return latents.to(device=e.device, dtype=torch.float32).clone()
-    if not e.conditional:
-        if cr_face is not None or cr_latent is not None:
-            raise RuntimeError("the unconditional Denoiser takes no cr_face / cr_latent")
-        e.require_loaded()
-        e.prepare_unconditional(latents.shape[0])
-    elif prepare:
-        model.prepare(cr_face, cr_latent)
-    e.require_loaded()
+    _ready(model, B, cr_face, cr_latent, prepare)
     if mask is not None:
         e.set_mask(mask, known, known_noise)
     elif prepare:
         e.clear_mask()
     x = latents.to(device=e.device, dtype=torch.float32).contiguous().clone()
-    ts, coef = scheduler.coefficient_table()
-    ts, coef = ts.contiguous(), coef.contiguous()
-    multistep = coef.shape[1] == 8                         # DPMSolverMultistepScheduler: one history term (hd_schedule_ms)
+    return _run(e, x, scheduler.coefficient_table(), rows, spans, n_iters, resume, face_seeds, noise, seed, check)
+
+
+def _ready(model, B, cr_face=None, cr_latent=None, prepare=False):
+    """The engine (device chosen) before a loop on a batch of B: weights loaded, the batch prepared (always for the unconditional
+    Denoiser, else with prepare=True)."""
+    e = model.engine
+    if not e.conditional:
+        if cr_face is not None or cr_latent is not None:
+            raise RuntimeError("the unconditional Denoiser takes no cr_face / cr_latent")
+        e.require_loaded()
+        e.prepare_unconditional(B)
+    elif prepare:
+        model.prepare(cr_face, cr_latent)
+    e.require_loaded()
+
+
+def _run(e, x, table, start_steps=None, spans=None, n_iters=None, resume=False, face_seeds=None, noise=None, seed=0, check=True):
+    """The one path to the library's sampling loop: runs it in place on x ([B,4,L,L] fp32 on the engine's device) and returns x.
+
+    table: (timesteps [n], coef [n,7] or [n,8]).  The entry point follows sample()'s rule: spans ((begin, end) int32 [B] CPU tensors, with
+    start_steps the absolute rows) -> hd_sample_spans; face_seeds (a face_seeds_arg array) or a tensor resume -> hd_sample_faces*;
+    start_steps -> hd_sample_rows*; else hd_sample*; 8 columns pick the multistep form.  n_iters defaults to the longest remaining run,
+    and when that is 0 nothing is called."""
+    ts, coef = (t.contiguous() for t in table)
+    n, B, multistep = ts.numel(), x.shape[0], coef.shape[1] == 8   # 8: DPMSolverMultistepScheduler, one history term (hd_schedule_ms)
+    ptr = lambda t, ty=ctypes.c_int32: ctypes.cast(t.data_ptr(), ctypes.POINTER(ty))   # noqa: E731
     sch = _lib.ScheduleMS() if multistep else _lib.Schedule()
-    sch.n_steps = ts.numel()
-    sch.timesteps = ctypes.cast(ts.data_ptr(), ctypes.POINTER(ctypes.c_float))
-    sch.coef = ctypes.cast(coef.data_ptr(), ctypes.POINTER(ctypes.c_float))
+    sch.n_steps, sch.timesteps, sch.coef = n, ptr(ts, ctypes.c_float), ptr(coef, ctypes.c_float)
     nptr = None
     if noise is not None:
         noise = noise.to(device=e.device, dtype=torch.float32).contiguous()
-        if noise.numel() != ts.numel() * x.numel():
+        if noise.numel() != n * x.numel():
             raise RuntimeError("noise must be [n_steps, B, 4, L, L]")
         nptr = noise.data_ptr()
-    stream = torch.cuda.current_stream(e.device).cuda_stream
-    B = x.shape[0]
-    if span_rows is not None:
-        return _sample_spans(e, x, sch, span_rows, nptr, seed, stream, n_iters, resume, face_seeds, check)
-    per_face_resume = isinstance(resume, torch.Tensor)
-    if face_seeds is not None or per_face_resume:
-        return _sample_faces(e, x, sch, ts, multistep, nptr, seed, stream, start_steps, n_iters, resume, face_seeds, check)
-    if start_steps is None:
+    L = _lib.lib()
+    faces = spans is not None or face_seeds is not None or isinstance(resume, torch.Tensor)
+    if start_steps is None and not faces:
         if n_iters is not None or resume:
             raise ValueError("n_iters / resume need start_steps")
-        with torch.cuda.device(e.device):
-            run = _lib.lib().hd_sample_multistep if multistep else _lib.lib().hd_sample
-            _lib.check(run(e.ctx, x.data_ptr(), ctypes.byref(sch), nptr, int(seed), stream), e.ctx)
+        fn, args = (L.hd_sample_multistep if multistep else L.hd_sample), ()
     else:
-        rows = torch.as_tensor(start_steps).to(device="cpu", dtype=torch.int32).flatten()
-        if rows.numel() == 1:
-            rows = rows.expand(B)
-        rows = rows.contiguous()
-        if rows.numel() != B:
-            raise ValueError(f"start_steps must be an int or a [{B}] tensor")
-        if n_iters is None:
-            n_iters = ts.numel() - int(rows.min())
-            if n_iters == 0:                               # every face starts past the last row (strength 0): nothing to run
-                return x
-        if resume and not multistep:
+        rows = _rows_arg(start_steps, B)
+        bad_resume = (isinstance(resume, torch.Tensor) or resume) and not multistep
+        if faces and bad_resume:
             raise ValueError("resume applies to multistep schedules only")
-        rptr = ctypes.cast(rows.data_ptr(), ctypes.POINTER(ctypes.c_int32))
-        with torch.cuda.device(e.device):
-            if multistep:
-                rc = _lib.lib().hd_sample_rows_multistep(e.ctx, x.data_ptr(), ctypes.byref(sch), rptr, int(n_iters), int(bool(resume)),
-                                                         nptr, int(seed), stream)
-            else:
-                rc = _lib.lib().hd_sample_rows(e.ctx, x.data_ptr(), ctypes.byref(sch), rptr, int(n_iters), nptr, int(seed), stream)
-            _lib.check(rc, e.ctx)
+        if n_iters is None:
+            n_iters = int(((n if spans is None else spans[1]) - rows).max())
+            if n_iters == 0:                               # every face starts past its last row (strength 0): nothing to run
+                return x
+        if bad_resume:
+            raise ValueError("resume applies to multistep schedules only")
+        sptr = face_seeds.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if face_seeds is not None else None
+        res = resume_arg(resume, B) if faces and multistep else None
+        if spans is not None:
+            fn, args = L.hd_sample_spans, (ptr(spans[0]), ptr(spans[1]), ptr(rows), int(n_iters), ptr(res), sptr)
+        elif faces and multistep:
+            fn, args = L.hd_sample_faces_multistep, (ptr(rows), int(n_iters), ptr(res), sptr)
+        elif faces:
+            fn, args = L.hd_sample_faces, (ptr(rows), int(n_iters), sptr)
+        elif multistep:
+            fn, args = L.hd_sample_rows_multistep, (ptr(rows), int(n_iters), int(bool(resume)))
+        else:
+            fn, args = L.hd_sample_rows, (ptr(rows), int(n_iters))
+    with torch.cuda.device(e.device):
+        _lib.check(fn(e.ctx, x.data_ptr(), ctypes.byref(sch), *args, nptr, int(seed), torch.cuda.current_stream(e.device).cuda_stream), e.ctx)
     if check:
         e.check()
     return x
@@ -357,50 +371,6 @@ def _span_args(sset, schedules, start_steps, B):
         f = int(((rel < 0) | (rel > end - begin)).nonzero()[0])
         raise ValueError(f"start_steps[{f}] = {int(rel[f])} outside face {f}'s schedule [0, {int(end[f] - begin[f])}]")
     return begin.contiguous(), end.contiguous(), (begin + rel).contiguous()
-
-
-def _sample_spans(e, x, sch, span_rows, nptr, seed, stream, n_iters, resume, face_seeds, check):
-    """hd_sample_spans: per-face spans of a concatenated table, with per-face start rows, Philox keys and resumption."""
-    begin, end, rows = span_rows
-    if n_iters is None:
-        n_iters = int((end - rows).max())
-        if n_iters == 0:
-            return x
-    i32 = lambda t: ctypes.cast(t.data_ptr(), ctypes.POINTER(ctypes.c_int32))   # noqa: E731
-    sptr = face_seeds.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if face_seeds is not None else None
-    with torch.cuda.device(e.device):
-        rc = _lib.lib().hd_sample_spans(e.ctx, x.data_ptr(), ctypes.byref(sch), i32(begin), i32(end), i32(rows), int(n_iters), i32(resume),
-                                        sptr, nptr, int(seed), stream)
-        _lib.check(rc, e.ctx)
-    if check:
-        e.check()
-    return x
-
-
-def _sample_faces(e, x, sch, ts, multistep, nptr, seed, stream, start_steps, n_iters, resume, face_seeds, check):
-    """hd_sample_faces / hd_sample_faces_multistep: per-face start rows, Philox keys and (multistep) resumption."""
-    B = x.shape[0]
-    rows = _rows_arg(start_steps, B)
-    if (isinstance(resume, torch.Tensor) or resume) and not multistep:
-        raise ValueError("resume applies to multistep schedules only")
-    seeds = face_seeds                                     # already a uint64 array (sample) or None
-    if n_iters is None:
-        n_iters = ts.numel() - int(rows.min())
-        if n_iters == 0:
-            return x
-    rptr = ctypes.cast(rows.data_ptr(), ctypes.POINTER(ctypes.c_int32))
-    sptr = seeds.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if seeds is not None else None
-    with torch.cuda.device(e.device):
-        if multistep:
-            res = resume_arg(resume, B)
-            rc = _lib.lib().hd_sample_faces_multistep(e.ctx, x.data_ptr(), ctypes.byref(sch), rptr, int(n_iters),
-                                                      ctypes.cast(res.data_ptr(), ctypes.POINTER(ctypes.c_int32)), sptr, nptr, int(seed), stream)
-        else:
-            rc = _lib.lib().hd_sample_faces(e.ctx, x.data_ptr(), ctypes.byref(sch), rptr, int(n_iters), sptr, nptr, int(seed), stream)
-        _lib.check(rc, e.ctx)
-    if check:
-        e.check()
-    return x
 
 
 class SlotTable:
@@ -621,37 +591,18 @@ class ContinuousSampler:
             self.x = torch.zeros((self.batch, 4, self.L, self.L), device=dev)
         self._refill(dev)
         n = self.table.iters(self.refill_every)
-        if n > 0:
-            multistep = self.scheduler.coefficient_table()[1].shape[1] == 8
-            kw = dict(start_steps=torch.tensor(self.table.start_rows()), n_iters=n, face_seeds=list(self.seeds))
-            if multistep:
-                kw["resume"] = torch.tensor(self.table.resume_flags(), dtype=torch.bool)
-            if self.sset is None:
-                self.x = sample(self.model, self.x, None, None, self.scheduler, prepare=False, **kw)
-            else:
-                self.x = self._step_spans(e, n, kw)
+        if n > 0:                       # the slots' rows (and spans) go to the library as they stand in the table
+            t, i32 = self.table, lambda v: torch.tensor(v, dtype=torch.int32)   # noqa: E731
+            table = self.scheduler.coefficient_table()
+            e.ensure(self.x.device)
+            _ready(self.model, self.batch)
+            x = self.x.to(device=e.device, dtype=torch.float32).contiguous().clone()
+            self.x = _run(e, x, table, i32(t.start_rows()), None if self.sset is None else (i32(t.begin_rows()), i32(t.end_rows())), n,
+                          i32(t.resume_flags()) if table[1].shape[1] == 8 else False, face_seeds_arg(self.seeds, self.batch))
             self.calls += 1
         for slot, rid in self.table.advance(n):
             self.finished[rid] = self.x[slot].clone()
         return n
-
-    def _step_spans(self, e, n, kw):
-        """One call over the set: the slots' spans and absolute start rows go to hd_sample_spans as they stand in the table."""
-        ts, coef = self.sset.coefficient_table()
-        sch = _lib.ScheduleMS()
-        sch.n_steps = ts.numel()
-        sch.timesteps = ctypes.cast(ts.data_ptr(), ctypes.POINTER(ctypes.c_float))
-        sch.coef = ctypes.cast(coef.data_ptr(), ctypes.POINTER(ctypes.c_float))
-        e.ensure(self.x.device)
-        if not e.conditional:
-            e.prepare_unconditional(self.batch)
-        e.require_loaded()
-        t = self.table
-        rows = (torch.tensor(t.begin_rows(), dtype=torch.int32), torch.tensor(t.end_rows(), dtype=torch.int32),
-                torch.tensor(t.start_rows(), dtype=torch.int32))
-        x = self.x.to(device=e.device, dtype=torch.float32).contiguous().clone()
-        return _sample_spans(e, x, sch, rows, None, 0, torch.cuda.current_stream(e.device).cuda_stream, n,
-                             resume_arg(kw["resume"], self.batch), face_seeds_arg(kw["face_seeds"], self.batch), True)
 
     def busy(self):
         return bool(self.queue) or bool(self.table.occupied())
