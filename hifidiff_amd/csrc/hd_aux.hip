@@ -407,6 +407,7 @@ static int build_vae_encode(hd_ctx* c, int B, int in_res, int R, const float* im
                             hipLaunchKernelGGL(nchw_to_nhwc8_bf16_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, src, in8, 3, HW, npix, vae_range);
                             return hipGetLastError();
                         }});
+        prog.back().out = in8; prog.back().out_elems = npix * 8; prog.back().out_bf16 = 1;
     }
     vae_conv3(c, prog, "encoder.conv_in", w.enc_in, reinterpret_cast<const unsigned short*>(v.in8), B, R, 1, v.X, nullptr, nullptr);
     int H = R;
@@ -446,6 +447,7 @@ static int build_vae_decode(hd_ctx* c, int B, int L, const float* latents, float
                             hipLaunchKernelGGL(vae_decode_entry_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, latents, pw, pb, in8, HW, npix, 1.0f / 0.18215f);
                             return hipGetLastError();
                         }});
+        prog.back().out = in8; prog.back().out_elems = npix * 8; prog.back().out_bf16 = 1;
     }
     vae_conv3(c, prog, "decoder.conv_in", w.dec_in, reinterpret_cast<const unsigned short*>(v.in8), B, H, 1, v.X, nullptr, nullptr);
     vae_resnet(c, prog, w.dec_mid[0], B, H, nullptr);
@@ -460,6 +462,7 @@ static int build_vae_decode(hd_ctx* c, int B, int L, const float* latents, float
                                 hipLaunchKernelGGL(upsample2x_bf16_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65535)), dim3(256), 0, s, x, u, B, Hc, Hc, C);
                                 return hipGetLastError();
                             }});
+            prog.back().out = u; prog.back().out_elems = (size_t)B * 4 * Hc * Hc * C; prog.back().out_bf16 = 1;
             H *= 2;
             vae_conv3(c, prog, "decoder.up_blocks." + std::to_string(i) + ".upsamplers.0.conv", w.dec_up[i], v.U, B, H, 1, v.X, nullptr, nullptr);
         }
