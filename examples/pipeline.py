@@ -10,6 +10,8 @@
     python examples/pipeline.py [--batch 8] [--scheduler ddim|dpmpp2m] [--steps 50] [--strength 0.6]
     python examples/pipeline.py --stream 200 [--refill-every 5] [--batch 64]    # continuous batching of 200 requests, mixed strengths
     python examples/pipeline.py --stream 200 --steps-mix 10,20,50    # the requests cycle through schedules of 10, 20 and 50 steps in one batch
+    python examples/pipeline.py --preview-every 10          # decode every 10th row's denoised estimate: how the image forms
+    python examples/pipeline.py --stream 200 --preview-every 1      # one progress line per step() of the serving loop
     python examples/pipeline.py --mask-box 32,40,96,72 --mask-box 48,84,80,108 [--strength 0.8]   # inpainting: resample the boxes (pixels of
                                                           # the 128 x 128 face), keep the coarse restoration everywhere else
 """
@@ -45,7 +47,12 @@ def main():
     ap.add_argument("--mask-box", action="append", default=None, metavar="x0,y0,x1,y1",
                     help="inpainting: resample this pixel box of the 128 x 128 face and keep cr_latent elsewhere (repeatable; composes with "
                          "--strength, --scheduler and --stream)")
+    ap.add_argument("--preview-every", type=int, default=None, metavar="N",
+                    help="progress previews: decode the denoised estimate of every N-th row through the VAE and print its mean absolute "
+                         "difference to the final image; with --stream: one progress line per step()")
     a = ap.parse_args()
+    if a.preview_every is not None and a.preview_every < 1:
+        ap.error("--preview-every must be >= 1")
     a.mask = None
     if a.mask_box:
         a.mask = sampling.region_mask([tuple(int(v) for v in b.split(",")) for b in a.mask_box], 16)
@@ -84,18 +91,28 @@ def main():
     cr_latent = vae.encode_scaled(cr_face, 128, seed=7)                # bicubic (identity at 128) + encode + sample + x 0.18215
     torch.cuda.synchronize(); t2 = time.time()
     sch.set_timesteps(steps)
+    pv = {} if a.preview_every is None else {"previews": a.preview_every}
     if a.mask is not None:                                             # inpainting: the boxes are resampled, the rest stays cr_latent
         latent, start, nz = sampling.inpaint_start(sch, cr_latent, 1.0 if a.strength is None else a.strength, noise=latent)
         out = sampling.sample(model, latent, cr_face, cr_latent, sch, start_steps=start, mask=a.mask[None].expand(B, 16, 16),
-                              known=cr_latent, known_noise=nz)
+                              known=cr_latent, known_noise=nz, **pv)
     elif a.strength is None:
-        out = sampling.sample(model, latent, cr_face, cr_latent, sch)  # conditioning once + graph-replayed loop
+        out = sampling.sample(model, latent, cr_face, cr_latent, sch, **pv)   # conditioning once + graph-replayed loop
     else:                                                              # img2img: noise cr_latent to timesteps[start], run the remaining rows
         latent, start = sampling.img2img_start(sch, cr_latent, a.strength, noise=latent)
-        out = sampling.sample(model, latent, cr_face, cr_latent, sch, start_steps=start)
+        out = sampling.sample(model, latent, cr_face, cr_latent, sch, start_steps=start, **pv)
+    snaps = None
+    if pv:
+        out, snaps, snap_rows = out
     torch.cuda.synchronize(); t3 = time.time()
     images = vae.decode(out / 0.18215).sample                          # the reference's call form; decode_scaled(out) is the fused one
     torch.cuda.synchronize(); t4 = time.time()
+    for s in range(0 if snaps is None else snaps.shape[0]):            # the estimate of every N-th row as an image (hd_vae_decode)
+        ran = snap_rows[s] >= 0                                        # img2img: a face that started later has not run this row
+        if bool(ran.any()):
+            img = vae.decode(snaps[s][ran] / 0.18215).sample
+            print(f"preview {s}: row {int(snap_rows[s][ran].max())} of {steps}, {int(ran.sum())} faces, mean |image - final| "
+                  f"{float((img - images[ran]).abs().mean()):.4f}")
     print(f"batch {B}: coarse restoration {1e3 * (t1 - t0):.1f} ms, VAE encode {1e3 * (t2 - t1):.1f} ms, {steps}-step {a.scheduler} "
           f"{1e3 * (t3 - t2):.1f} ms, VAE decode {1e3 * (t4 - t3):.1f} ms; latent range [{float(out.min()):.2f}, {float(out.max()):.2f}], "
           f"images {tuple(images.shape)} finite {bool(torch.isfinite(images).all())}")
@@ -125,11 +142,21 @@ def stream(a, cr, vae, model, sch, steps, dev):
             s.set_timesteps(n)
         sch, steps = sampling.ScheduleSet(members), a.steps_mix
         pick = [counts[i % len(counts)] for i in range(N)]
-    cs = sampling.ContinuousSampler(model, sch, batch=a.batch, refill_every=a.refill_every)
+    cs = sampling.ContinuousSampler(model, sch, batch=a.batch, refill_every=a.refill_every, previews=a.preview_every is not None)
     torch.cuda.synchronize(); t1 = time.time()
     ids = [cs.submit(f, l, seed=1000 + i, strength=strength[i], mask=a.mask, **({"schedule": pick[i]} if a.steps_mix else {}))
            for i, (f, l) in enumerate(reqs)]
-    out = cs.drain()
+    out = {}
+    while cs.busy():
+        cs.step()
+        out.update(cs.poll())
+        if a.preview_every is not None:                                # what a front end would show: every running request's x0
+            pr = cs.previews()
+            if pr:
+                done = sum(d for d, _, _ in pr.values()) / sum(t for _, t, _ in pr.values())
+                spread = torch.stack([x0 for _, _, x0 in pr.values()]).std()
+                print(f"call {cs.calls}: {len(pr)} requests running, {100 * done:.0f}% of their rows done, {len(out)} finished, "
+                      f"x0 std {float(spread):.3f}")
     torch.cuda.synchronize(); t2 = time.time()
     lat = torch.stack([out[i] for i in ids])
     images = vae.decode(lat / 0.18215).sample

@@ -256,6 +256,13 @@ struct hd_ctx {
     int *mask_on_dev = nullptr, *mask_slots_dev = nullptr;
     int mask_cap = 0;
     std::vector<char> mask_face;
+    // progress previews (hd_preview_config): the configuration (it survives hd_prepare*), and the planes of the batch they were allocated
+    // for (pv_B faces, pv_planes snapshot planes): x0 [B,4,L,L], snapshots [pv_planes][B,4,L,L], rows [1 + pv_planes][B] (latest, then one
+    // per snapshot plane; -1: none) and the slot list of a read.  Read and written through StepState: no graph holds these pointers.
+    bool pv_on = false;
+    int pv_every = 1, pv_snaps = 0, pv_B = 0, pv_planes = 0;
+    float *pv_x0_dev = nullptr, *pv_snap_dev = nullptr;
+    int *pv_row_dev = nullptr, *pv_slots_dev = nullptr;
     int graph_captures = 0;                   // step-graph instantiations of this context (hd_get_option "graph_captures")
     // persistent-stage launches recorded by the last one-step capture of each form (hd_get_option "sample_stage_launches",
     // "sample_face_stage_launches", "rows_stage_launches"); stage_count / face_stage_count count while a capture runs

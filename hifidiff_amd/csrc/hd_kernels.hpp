@@ -38,6 +38,14 @@ struct StepState {
     // Philox counter is k - begin_f.  Read by the per-face launches only.
     const int* begin_rows;
     const int* end_rows;
+    // progress previews (hd_preview_config; all NULL / 0 while previews are off): this chain's [B_chain,4,L,L] plane of the latest denoised
+    // estimate p = x0 (a masked face: m*x0 + (1 - m)*known), pv_snaps snapshot planes with a stride of pv_batch faces -- row j of a face's
+    // own schedule (j = k - begin_f) with (j + 1) % pv_every == 0 also goes to plane (j + 1)/pv_every - 1 -- and the rows: pv_row[f] is the
+    // table row k of face f's latest estimate, pv_row[(1 + s)*pv_batch + f] that of its snapshot s.  A held face writes none of them.
+    float* pv_x0;
+    int* pv_row;
+    float* pv_snap;
+    int pv_every, pv_snaps, pv_batch;
 };
 
 // ----------------------------------------------------------------------------------- weight packing
@@ -205,6 +213,8 @@ __device__ __forceinline__ bool st_first(const StepState* st, int f, int k, int 
 // unblended x0.  f is uniform over the wave (a run lies in one face), so the branch is too.
 // PF with spans (hd_sample_spans): the last row is that of the face's span (step + 1 >= end_f), and the Philox counter is the row inside the
 // span, step - begin_f -- a request's z does not depend on where its schedule sits in the table; an explicit noise tensor keeps the absolute row.
+// Previews (st->pv_x0 != NULL, hd_preview_config): the estimate p -- x0, blended with the known latent of a masked face in the order of the
+// blend above, so m == 1 gives x0 and m == 0 gives known exactly -- is stored as one more output (StepState::pv_*).  NULL: nothing is read or written.
 template <bool PF = false>
 __device__ __forceinline__ float sched_update(float xv, float e, const float* c, const StepState* st, int step, size_t gi, int n_total,
                                              size_t li, bool first, int f, unsigned ef, int ll) {
@@ -237,6 +247,22 @@ __device__ __forceinline__ float sched_update(float xv, float e, const float* c,
         const float kn = b0 * ((const __attribute__((address_space(1))) float*)st->mask_known)[li] +
                          b1 * ((const __attribute__((address_space(1))) float*)st->mask_noise)[li];
         r = m * r + (1.f - m) * kn;
+    }
+    if (st->pv_x0) {                                       // previews on: uniform over the launch
+        float p = x0;
+        if (st->mask && ((const __attribute__((address_space(1))) int*)st->mask_on)[f] != 0) {
+            const float m = ((const __attribute__((address_space(1))) float*)st->mask)[(size_t)f * ll + (ef & (unsigned)(ll - 1))];
+            p = m * x0 + (1.f - m) * ((const __attribute__((address_space(1))) float*)st->mask_known)[li];
+        }
+        ((__attribute__((address_space(1))) float*)st->pv_x0)[li] = p;
+        const int j1 = step - (PF ? st_begin(st, f) : 0) + 1, s = j1 / st->pv_every - 1;      // wave-uniform
+        const bool snap = j1 % st->pv_every == 0 && s < st->pv_snaps;
+        if (snap) ((__attribute__((address_space(1))) float*)st->pv_snap)[(size_t)s * st->pv_batch * 4 * ll + li] = p;
+        if (ef == 0) {                                     // one lane of the face
+            __attribute__((address_space(1))) int* rows = (__attribute__((address_space(1))) int*)st->pv_row;
+            rows[f] = step;
+            if (snap) rows[(size_t)(1 + s) * st->pv_batch + f] = step;
+        }
     }
     return r;
 }
@@ -384,6 +410,25 @@ static __global__ void mask_scatter_kernel(const MaskScatterP p) {
         p.dknown[(size_t)slot * 4 * p.ll + i] = p.known[(size_t)j * 4 * p.ll + i];
         p.dnoise[(size_t)slot * 4 * p.ll + i] = p.noise[(size_t)j * 4 * p.ll + i];
     }
+}
+
+// Progress previews (hd_preview_config).  ll4 = 4*L*L.  preview_reset_kernel (hd_prepare_slots): slot slots[j] (j < n = gridDim.y) has no
+// estimate -- its latest plane and its `snaps` snapshot planes are zeroed and their rows set to -1.  preview_gather_kernel (hd_preview_read):
+// face slots[j] (NULL: j) of one plane and its row go to out[j] / rows_out[j] (rows_out may be NULL).
+struct PreviewP { float *x0, *snap; int* rows; const int* slots; int B, snaps, ll4; };
+static __global__ void preview_reset_kernel(const PreviewP p) {
+    const int slot = p.slots[blockIdx.y];
+    for (int pl = 0; pl <= p.snaps; ++pl) {
+        float* d = (pl ? p.snap + (size_t)(pl - 1) * p.B * p.ll4 : p.x0) + (size_t)slot * p.ll4;
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < p.ll4; i += gridDim.x * blockDim.x) d[i] = 0.f;
+        if (blockIdx.x == 0 && threadIdx.x == 0) p.rows[(size_t)pl * p.B + slot] = -1;
+    }
+}
+struct PreviewReadP { const float* plane; const int* rows; const int* slots; float* out; int* rows_out; int ll4; };
+static __global__ void preview_gather_kernel(const PreviewReadP p) {
+    const int j = blockIdx.y, slot = p.slots ? p.slots[j] : j;
+    if (p.rows_out && blockIdx.x == 0 && threadIdx.x == 0) p.rows_out[j] = p.rows[slot];
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < p.ll4; i += gridDim.x * blockDim.x) p.out[(size_t)j * p.ll4 + i] = p.plane[(size_t)slot * p.ll4 + i];
 }
 
 // hd_prepare_slots: copy face j (< n) of the n-face conditioning (the staging chain's buffers: 5 priors NHWC, 5 w_c, 5 w_s, the idc term and

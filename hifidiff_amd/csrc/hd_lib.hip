@@ -931,11 +931,36 @@ static int masked_faces(const hd_ctx* c) {
     for (char m : c->mask_face) n += m != 0;
     return n;
 }
-// every hd_prepare*: the new batch has no masks
+// Progress previews (hd_preview_config): the planes are sized by the batch in use and the configuration, like the mask buffers.
+static void free_previews(hd_ctx* c) {
+    dev_free(c, c->pv_x0_dev); dev_free(c, c->pv_snap_dev); dev_free(c, c->pv_row_dev); dev_free(c, c->pv_slots_dev);
+    c->pv_x0_dev = c->pv_snap_dev = nullptr; c->pv_row_dev = c->pv_slots_dev = nullptr; c->pv_B = 0;
+}
+// every face: no estimate (rows -1, zeroed planes); the planes are (re)allocated when the batch or the snapshot count has changed
+static int reset_previews(hd_ctx* c, hipStream_t s) {
+    if (!c->pv_on) return HD_OK;
+    const size_t B = (size_t)c->B, per_face = (size_t)4 * c->L * c->L, planes = (size_t)c->pv_snaps;
+    if (c->pv_B != c->B || c->pv_planes != c->pv_snaps) {
+        free_previews(c);
+        int rc = dev_alloc(c, &c->pv_x0_dev, B * per_face);
+        if (!rc) rc = dev_alloc(c, &c->pv_snap_dev, (planes ? planes : 1) * B * per_face);
+        if (!rc) rc = dev_alloc(c, &c->pv_row_dev, (1 + planes) * B);
+        if (!rc) rc = dev_alloc(c, &c->pv_slots_dev, B);
+        if (rc) { free_previews(c); return rc; }
+        c->pv_B = c->B; c->pv_planes = c->pv_snaps;
+    }
+    HIPCHECK(c, hipMemsetAsync(c->pv_x0_dev, 0, B * per_face * sizeof(float), s));
+    if (planes) HIPCHECK(c, hipMemsetAsync(c->pv_snap_dev, 0, planes * B * per_face * sizeof(float), s));
+    HIPCHECK(c, hipMemsetAsync(c->pv_row_dev, 0xff, (1 + planes) * B * sizeof(int), s));      // -1
+    return HD_OK;
+}
+static bool previews_ready(const hd_ctx* c) { return c->pv_on && c->pv_x0_dev && c->pv_B == c->B && c->pv_planes == c->pv_snaps; }
+
+// every hd_prepare*: the new batch has no masks and no previews
 static int clear_masks(hd_ctx* c, hipStream_t s) {
     if (masked_faces(c) > 0) HIPCHECK(c, hipMemsetAsync(c->mask_on_dev, 0, (size_t)c->mask_cap * sizeof(int), s));
     c->mask_face.clear();
-    return HD_OK;
+    return reset_previews(c, s);
 }
 
 #define HD_NEED_CONDITIONAL(c, what) \
@@ -1195,12 +1220,12 @@ static int grow_loop_buffers(hd_ctx* c, const SampleCall& call) {
 
 // Schedule and loop state (step = -1: each chain's intro kernel pre-increments) go through the pinned staging buffer, so the caller's
 // host arrays are free on return and nothing here waits for the stream.  Regions, in order: coef [n][7] | timesteps [n] | c7 [n]
-// (multistep) | one StepState (single-step, whole batch, no masks) or one per chain | the per-face argument block (per-face calls).
+// (multistep) | one StepState (single-step, whole batch, no masks, no previews) or one per chain | the per-face argument block (per-face calls).
 static int stage_loop_state(hd_ctx* c, const SampleCall& call, bool upload_timesteps, hipStream_t s) {
     const int n = call.n;
     const bool ms = call.ncoef == 8, pf = call.start_rows != nullptr;
-    const bool mk = any_mask(c);
-    const size_t nst = (ms || pf || mk) ? c->chains.size() : 1;
+    const bool mk = any_mask(c), pv = previews_ready(c);
+    const size_t nst = (ms || pf || mk || pv) ? c->chains.size() : 1;
     StageCursor cur;
     const size_t coef0 = cur.take((size_t)n * 7 * sizeof(float)), ts0 = cur.take((size_t)n * sizeof(float));
     const size_t c70 = cur.take(ms ? (size_t)n * sizeof(float) : 0), st0 = cur.take(nst * sizeof(StepState));
@@ -1237,6 +1262,11 @@ static int stage_loop_state(hd_ctx* c, const SampleCall& call, bool upload_times
             const size_t ll = (size_t)c->L * c->L;
             st.mask = c->mask_dev + f0 * ll; st.mask_known = c->mask_known_dev + f0 * 4 * ll;
             st.mask_noise = c->mask_noise_dev + f0 * 4 * ll; st.mask_on = c->mask_on_dev + f0;
+        }
+        if (pv) {
+            const size_t per_face = (size_t)4 * c->L * c->L;
+            st.pv_x0 = c->pv_x0_dev + f0 * per_face; st.pv_snap = c->pv_snap_dev + f0 * per_face; st.pv_row = c->pv_row_dev + f0;
+            st.pv_every = c->pv_every; st.pv_snaps = c->pv_snaps; st.pv_batch = c->B;
         }
         memcpy(host + st0 + k * sizeof(StepState), &st, sizeof(st));
     }
@@ -1604,6 +1634,13 @@ int hd_prepare_slots(hd_ctx* c, int n, const int32_t* slots, const float* cr_lat
             HIPCHECK(c, hipGetLastError());
         }
     }
+    if (previews_ready(c)) {                               // ... and no preview: row -1, zeroed planes
+        PreviewP pp{};
+        pp.x0 = c->pv_x0_dev; pp.snap = c->pv_snap_dev; pp.rows = c->pv_row_dev; pp.slots = c->slots_dev;
+        pp.B = c->B; pp.snaps = c->pv_snaps; pp.ll4 = 4 * c->L * c->L;
+        hipLaunchKernelGGL(preview_reset_kernel, dim3(4, n), dim3(256), 0, s, pp);
+        HIPCHECK(c, hipGetLastError());
+    }
     // the refilled faces have no multistep history; hd_sample_rows_multistep(resume = 1) no longer continues the whole batch
     if (c->hist_B == c->B && c->hist_face.size() == (size_t)c->B)
         for (int j = 0; j < n; ++j) c->hist_face[slots[j]] = 0;
@@ -1666,6 +1703,64 @@ int hd_mask_faces(hd_ctx* c, int n, const int32_t* slots, const float* mask, con
     return HD_OK;
 }
 
+// Progress previews: the denoised estimate of the row a face last ran (and every pv_every-th row of its schedule) as an output of the step
+// kernels.  The planes belong to the context and are reached through StepState, like the masks: switching them on or off rebuilds no
+// launch program and recaptures no graph, and while they are off the loop's launches read and write nothing of this.
+int hd_preview_config(hd_ctx* c, int on, int every, int snapshots) {
+    if (!c) return HD_ERR_INVALID;
+    if (c->cr || c->vae) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_config: this context holds CoarseRestoration or the VAE (no sampling loop)");
+    if (on != 0 && on != 1) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_config: on = %d is not 0 or 1", on);
+    if (every < 1) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_config: every = %d must be >= 1", every);
+    if (snapshots < 0 || snapshots > 64) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_config: snapshots = %d outside [0, 64]", snapshots);
+    HIPCHECK(c, hipSetDevice(c->device));
+    c->pv_on = on != 0; c->pv_every = every; c->pv_snaps = snapshots;
+    if (!on) {
+        if (c->pv_x0_dev) HIPCHECK(c, hipDeviceSynchronize());      // a loop in flight may still write them
+        free_previews(c);
+        return HD_OK;
+    }
+    if (!c->finalized || !c->prepared) return HD_OK;         // allocated by the next hd_prepare*
+    HIPCHECK(c, hipDeviceSynchronize());
+    const int rc = reset_previews(c, nullptr);
+    if (rc) return rc;
+    HIPCHECK(c, hipStreamSynchronize(nullptr));              // the chains' queues do not wait for the null stream
+    return HD_OK;
+}
+
+int hd_preview_read(hd_ctx* c, int n, const int32_t* slots, int snapshot, float* x0_out, int32_t* rows_out, void* stream) {
+    if (!c) return HD_ERR_INVALID;
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    if (!previews_ready(c)) HD_FAIL(c, HD_ERR_NOT_READY, "hd_preview_read: previews are off (hd_preview_config)");
+    if (!x0_out) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: x0_out is NULL");
+    if (n < 1 || n > c->B) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: n = %d outside [1, %d]", n, c->B);
+    if (!slots && n != c->B) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: slots == NULL needs n == batch (%d), got %d", c->B, n);
+    if (snapshot < -1 || snapshot >= c->pv_snaps)
+        HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: snapshot = %d outside [-1, %d)", snapshot, c->pv_snaps);
+    if (slots) {
+        std::vector<char> seen((size_t)c->B, 0);
+        for (int j = 0; j < n; ++j) {
+            if (slots[j] < 0 || slots[j] >= c->B) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: slots[%d] = %d outside [0, %d)", j, slots[j], c->B);
+            if (seen[slots[j]]) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: slot %d given twice", slots[j]);
+            seen[slots[j]] = 1;
+        }
+    }
+    HIPCHECK(c, hipSetDevice(c->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (slots) {
+        rc = stage_slots(c, c->pv_slots_dev, slots, n, s);
+        if (rc) return rc;
+    }
+    const size_t per_face = (size_t)4 * c->L * c->L;
+    PreviewReadP p{};
+    p.plane = snapshot < 0 ? c->pv_x0_dev : c->pv_snap_dev + (size_t)snapshot * c->B * per_face;
+    p.rows = c->pv_row_dev + (size_t)(1 + snapshot) * c->B;
+    p.slots = slots ? c->pv_slots_dev : nullptr; p.out = x0_out; p.rows_out = rows_out; p.ll4 = (int)per_face;
+    hipLaunchKernelGGL(preview_gather_kernel, dim3(4, n), dim3(256), 0, s, p);
+    HIPCHECK(c, hipGetLastError());
+    return HD_OK;
+}
+
 static std::vector<Op>* which_program(hd_ctx* c, int which) {
     static std::vector<Op> empty;
     if (c->cr) return &c->cr_program;
@@ -1715,6 +1810,17 @@ int64_t hd_debug_read(hd_ctx* c, const char* name, float* host_out, int64_t max_
             if (!c->mask_dev || c->B < 1 || c->B > c->mask_cap) HD_FAIL(c, HD_ERR_INVALID, "debug buffer %s: no mask has been set for this batch", name);
             const size_t ll = (size_t)c->L * c->L;
             return read_to_host(c, m ? c->mask_dev : mkn ? c->mask_known_dev : c->mask_noise_dev, (size_t)c->B * (m ? ll : 4 * ll), 0, host_out, max_elems);
+        }
+    }
+    {                                                      // the preview planes too (preview_rows: the int32 rows as they are, 4 bytes each)
+        const std::string k = name;
+        const bool px = k == "x0_preview", pr = k == "preview_rows", ps = k == "preview_snaps";
+        if (px || pr || ps) {
+            if (!previews_ready(c)) HD_FAIL(c, HD_ERR_INVALID, "debug buffer %s: previews are off or no batch has been prepared since", name);
+            const size_t n = (size_t)c->B * 4 * c->L * c->L;
+            if (ps && c->pv_snaps == 0) return 0;
+            return read_to_host(c, px ? (const void*)c->pv_x0_dev : pr ? (const void*)c->pv_row_dev : (const void*)c->pv_snap_dev,
+                                px ? n : pr ? (size_t)c->B : (size_t)c->pv_snaps * n, 0, host_out, max_elems);
         }
     }
     auto it = c->dbg.find(name);
@@ -1775,6 +1881,7 @@ int hd_get_option(hd_ctx* c, const char* key) {
     if (k == "sample_face_stage_launches") return c->sample_face_stages;
     if (k == "rows_stage_launches") return c->rows_stages;
     if (k == "masked_faces") return c->mask_face.size() == (size_t)c->B ? masked_faces(c) : 0;   // faces that carry a mask (hd_mask_faces)
+    if (k == "preview") return c->pv_on ? 1 : 0;                 // hd_preview_config
     if (k == "graph_captures") return c->graph_captures;         // step graphs instantiated by this context (hd_prepare_slots adds none)
     // the folds of the program built for the batch in use (0 before the first call): the decisions build_denoiser_program made, and
     // whether the launch that carries them still runs -- the face-stage entries need the face stages on and a single chain

@@ -97,6 +97,40 @@ def mask_args(mask, known, noise, n, L):
     return mask, known.to(torch.float32), noise.to(torch.float32)
 
 
+def preview_args(every, snapshots):
+    """Argument checks of enable_previews, before any device work: ints with every >= 1 and 0 <= snapshots <= 64; ValueError otherwise."""
+    for name, v in (("every", every), ("snapshots", snapshots)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{name} must be an int, got {v!r}")
+    if every < 1:
+        raise ValueError(f"every must be >= 1, got {every}")
+    if not 0 <= snapshots <= 64:
+        raise ValueError(f"snapshots must lie in [0, 64], got {snapshots}")
+    return every, snapshots
+
+
+class _Previews:
+    """model.enable_previews / disable_previews / previews of both model classes (they share the engine's methods)."""
+
+    def enable_previews(self, every=1, snapshots=0):
+        """Progress previews: from now on every sampling.sample call also stores each face's denoised estimate x0 of the row it last ran
+        (diffusers' pred_original_sample; a masked face: blended with its known latent), and the estimate of every `every`-th row of the
+        face's own schedule in one of `snapshots` (0..64) snapshot planes.  The final latents do not change by a bit and nothing is
+        recaptured.  A new prepare resets the previews, prepare_slots those of its slots; the setting stays until disable_previews().
+        ValueError for every < 1 or snapshots outside [0, 64]."""
+        self._engine.enable_previews(every, snapshots)
+
+    def disable_previews(self):
+        """Switch the previews off and free their buffers."""
+        self._engine.disable_previews()
+
+    def previews(self, slots=None, snapshot=None):
+        """(x0 [n,4,L,L] fp32, rows [n] int32) on the model's device, in stream order: the latest estimate (snapshot=None) or snapshot
+        plane `snapshot` of the prepared batch's faces in `slots` (None: all, in order), and the table row each was taken at -- -1 (and a
+        zero plane) for a face that has not written it since it was prepared or refilled."""
+        return self._engine.previews(slots, snapshot)
+
+
 class _Engine:
     """Owns the hd_ctx of one (latent_res, device)."""
 
@@ -109,6 +143,7 @@ class _Engine:
         self.loaded = False
         self.cond_key = None
         self.batch = None
+        self.preview_cfg = None    # (every, snapshots) while previews are on: given to every context this engine creates
 
     def ensure(self, device):
         device = torch.device(device)
@@ -128,6 +163,8 @@ class _Engine:
         L = _lib.lib()
         ctx = ctypes.c_void_p()
         _lib.check((L.hd_create if self.conditional else L.hd_create_unconditional)(ctypes.byref(ctx), self.latent_res, idx))
+        if self.preview_cfg is not None:
+            _lib.check(L.hd_preview_config(ctx, 1, *self.preview_cfg), ctx)
         return ctx
 
     def manifest(self):
@@ -259,6 +296,38 @@ class _Engine:
         sp = None if sl is None else ctypes.cast(sl.data_ptr(), ctypes.POINTER(ctypes.c_int32))
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().hd_mask_faces(self.ctx, n, sp, None, None, None, _stream(self.device)), self.ctx)
+
+    def enable_previews(self, every=1, snapshots=0):
+        """hd_preview_config(on = 1): see FacialRefiner.enable_previews.  Before the model has a device only the setting is kept."""
+        self.preview_cfg = preview_args(every, snapshots)
+        if self.ctx is not None:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().hd_preview_config(self.ctx, 1, *self.preview_cfg), self.ctx)
+
+    def disable_previews(self):
+        self.preview_cfg = None
+        if self.ctx is not None:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().hd_preview_config(self.ctx, 0, 1, 0), self.ctx)
+
+    def previews(self, slots=None, snapshot=None):
+        """hd_preview_read: (x0 [n,4,L,L], rows int32 [n]) of the faces in `slots` (None: the whole batch), the latest plane or `snapshot`."""
+        if self.preview_cfg is None:
+            raise RuntimeError("previews are off: call enable_previews() first")
+        snap = -1 if snapshot is None else int(snapshot)
+        if not -1 <= snap < self.preview_cfg[1] or (snapshot is not None and snap < 0):
+            raise ValueError(f"snapshot must be None or lie in [0, {self.preview_cfg[1]}), got {snapshot!r}")
+        sl = None if slots is None else slots_arg(slots, self.batch)
+        self.require_loaded()
+        if self.batch is None:
+            raise RuntimeError("no batch is prepared: previews belong to a prepared batch")
+        n, L = self.batch if sl is None else sl.numel(), self.latent_res
+        x0 = torch.empty((n, 4, L, L), dtype=torch.float32, device=self.device)
+        rows = torch.empty((n,), dtype=torch.int32, device=self.device)
+        sp = None if sl is None else ctypes.cast(sl.data_ptr(), ctypes.POINTER(ctypes.c_int32))
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().hd_preview_read(self.ctx, n, sp, snap, x0.data_ptr(), rows.data_ptr(), _stream(self.device)), self.ctx)
+        return x0, rows
 
     def prepare_unconditional(self, batch):
         self.require_loaded()
@@ -406,7 +475,7 @@ class FusedDenoiser(_SubModule):
         self._engine.prior_key = None
 
 
-class Denoiser(nn.Module):
+class Denoiser(_Previews, nn.Module):
     """The unconditional pre-training network (models/denoiser/model.py:32-134): `model(latents, t).sample`, as the
     sampling loop of pretrain_denoiser.py:101-110 calls it.  State-dict keys are the reference's (no prefix)."""
 
@@ -467,7 +536,7 @@ class Denoiser(nn.Module):
         return UNet2DOutput(e.eps(latents, timesteps))
 
 
-class FacialRefiner(nn.Module):
+class FacialRefiner(_Previews, nn.Module):
     def __init__(self, latent_res=16, idc_ckpt=None, denoiser_ckpt=None, cache_conditioning=True):
         super().__init__()
         if latent_res % 16 != 0 or latent_res < 16:

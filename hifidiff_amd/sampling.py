@@ -190,7 +190,8 @@ class ScheduleSet:
 
 @torch.no_grad()
 def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, prepare=True, check=True,
-           start_steps=None, n_iters=None, resume=False, face_seeds=None, mask=None, known=None, known_noise=None, schedules=None):
+           start_steps=None, n_iters=None, resume=False, face_seeds=None, mask=None, known=None, known_noise=None, schedules=None,
+           previews=None):
     """Whole loop on the GPU: returns the final latents (a new tensor).
 
     The scheduler's coefficient table picks the entry point: 7 columns (DDIM / DDPM) -> hd_sample, 8 columns
@@ -218,13 +219,26 @@ def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, pr
     defaults to the longest remaining run, and resume (a bool or a [B] tensor) continues a face's history as above -- it needs
     start_steps[f] > 0.  A face's z counts rows from the start of its own schedule; an explicit noise tensor is indexed by the row of the
     concatenated table ([N, B, 4, L, L]).  With a plain scheduler `schedules` must stay None.
+    previews: None, or an int k >= 1: the call also returns every k-th denoised estimate of each face -- (latents, x0_snaps [S,B,4,L,L],
+    rows [S,B] int32) with S = ceil(longest schedule / k) (at most 64): x0_snaps[s, f] is face f's x0 of row (s + 1) * k - 1 of its own
+    schedule (a masked face: blended with its known latent) and rows[s, f] that row of the table, or zeros and -1 where the face did
+    not run that row in this call.  The latents are bit for bit those of previews=None; previews are switched on for the call
+    (model.enable_previews(k, S), which forgets earlier previews) and the model's own setting is restored afterwards.
     check=True (the default): ONE stream synchronisation after the whole loop (not per step), then RuntimeError if a persistent
     stage launch gave up during it -- where the reference's loop would have raised (test_refiner.py:89-91), so that the last batch
     of a val_loop cannot end with rc 0 and NaN images.  check=False only enqueues the work (the returned latents are NaN in the
     failing case either way; `model.check()` reports it later).  bench.py times the loop with its own synchronisation."""
     B = latents.shape[0]
     rows, spans = start_steps, None
-    if isinstance(scheduler, ScheduleSet):                 # argument errors before any device work
+    if previews is not None:                               # argument errors before any device work
+        if isinstance(previews, bool) or not isinstance(previews, int) or previews < 1:
+            raise ValueError(f"previews must be None or an int >= 1, got {previews!r}")
+        longest = (max(e - b for b, e in (scheduler.span(k) for k in scheduler.keys)) if isinstance(scheduler, ScheduleSet)
+                   else int(scheduler.coefficient_table()[0].numel()))
+        n_snaps = -(-longest // previews)
+        if n_snaps > 64:
+            raise ValueError(f"previews={previews} would take {n_snaps} snapshots of a {longest}-row schedule; at most 64 are kept")
+    if isinstance(scheduler, ScheduleSet):
         begin, end, rows = _span_args(scheduler, schedules, start_steps, B)
         spans = (begin, end)
     elif schedules is not None:
@@ -241,14 +255,29 @@ def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, pr
     e = model.engine
     e.ensure(latents.device)
     if B == 0:                                             # empty batch: nothing to sample
-        return latents.to(device=e.device, dtype=torch.float32).clone()
+        x = latents.to(device=e.device, dtype=torch.float32).clone()
+        if previews is None:
+            return x
+        return x, x.new_zeros((n_snaps,) + tuple(x.shape)), torch.zeros((n_snaps, 0), dtype=torch.int32, device=e.device)
     _ready(model, B, cr_face, cr_latent, prepare)
     if mask is not None:
         e.set_mask(mask, known, known_noise)
     elif prepare:
         e.clear_mask()
     x = latents.to(device=e.device, dtype=torch.float32).contiguous().clone()
-    return _run(e, x, scheduler.coefficient_table(), rows, spans, n_iters, resume, face_seeds, noise, seed, check)
+    if previews is None:
+        return _run(e, x, scheduler.coefficient_table(), rows, spans, n_iters, resume, face_seeds, noise, seed, check)
+    before = e.preview_cfg
+    e.enable_previews(previews, n_snaps)                   # after the prepare: every face starts without a preview
+    try:
+        x = _run(e, x, scheduler.coefficient_table(), rows, spans, n_iters, resume, face_seeds, noise, seed, check)
+        snaps = [e.previews(None, s) for s in range(n_snaps)]
+    finally:
+        if before is None:
+            e.disable_previews()
+        else:
+            e.enable_previews(*before)
+    return x, torch.stack([p for p, _ in snaps]), torch.stack([r for _, r in snaps])
 
 
 def _ready(model, B, cr_face=None, cr_latent=None, prepare=False):
@@ -440,6 +469,14 @@ class SlotTable:
         left = [self.end[i] - self.row[i] for i in self.occupied() if self.row[i] < self.end[i]]
         return min(int(limit), max(left)) if left else 0
 
+    def progress(self, slot, row):
+        """(rows done, rows of the schedule) of the request in `slot` whose latest preview was taken at table row `row` (hd_preview_read):
+        row - begin + 1 of end - begin, relative to the slot's own schedule.  None for an empty slot, a request that has not run a row yet
+        (its slot may still hold its predecessor's preview) or a row outside the slot's span."""
+        if self.req[slot] is None or self.fresh[slot] or not self.begin[slot] <= int(row) < self.end[slot]:
+            return None
+        return int(row) - self.begin[slot] + 1, self.end[slot] - self.begin[slot]
+
     def advance(self, n_iters):
         """Account for a call of n_iters iterations; returns [(slot, request id)] of the requests it completed (their slots are free)."""
         done = []
@@ -471,12 +508,18 @@ class ContinuousSampler:
 
     Per-request schedules: pass a ScheduleSet instead of a scheduler and pick a member per request, submit(..., schedule=key) (default: the
     set's first member).  Requests of different step counts and solvers then share the batch (hd_sample_spans): each runs its own member's
-    rows, its strength maps onto that member's row count, and its result is what it would be on that member alone."""
+    rows, its strength maps onto that member's row count, and its result is what it would be on that member alone.
 
-    def __init__(self, model, scheduler, batch=64, refill_every=5):
+    previews=True: previews() returns, between two step() calls, the progress and the current denoised estimate of every request that
+    is in a slot and has run a row; like its result, a request's preview does not depend on its slot or neighbours."""
+
+    def __init__(self, model, scheduler, batch=64, refill_every=5, previews=False):
         if batch < 1 or refill_every < 1:
             raise ValueError("batch and refill_every must be >= 1")
         self.model, self.scheduler = model, scheduler
+        self.want_previews = bool(previews)
+        if self.want_previews:          # the latest estimate of every slot; the model keeps the setting (model.disable_previews())
+            model.enable_previews(1, 0)
         self.batch, self.refill_every = int(batch), int(refill_every)
         self.conditional = model.engine.conditional
         self.L = model.engine.latent_res
@@ -603,6 +646,23 @@ class ContinuousSampler:
         for slot, rid in self.table.advance(n):
             self.finished[rid] = self.x[slot].clone()
         return n
+
+    def previews(self):
+        """{request id: (rows_done, rows_total, x0 [4,L,L] on the device)} of every request in a slot that has run a row: rows_done of the
+        rows_total rows of its own schedule (from its start row on: a request of strength < 1 begins with rows_done > 1), and the x0 of
+        the last of them.  A request that finished in the last step() has left its slot: poll() has its result."""
+        if not self.want_previews:
+            raise RuntimeError("this ContinuousSampler was created without previews=True")
+        slots = [i for i in self.table.occupied() if not self.table.fresh[i]]
+        if not slots:
+            return {}
+        x0, rows = self.model.previews(slots)
+        out = {}
+        for j, (slot, row) in enumerate(zip(slots, rows.cpu().tolist())):
+            p = self.table.progress(slot, row)
+            if p is not None:
+                out[self.table.req[slot]] = (p[0], p[1], x0[j])
+        return out
 
     def busy(self):
         return bool(self.queue) or bool(self.table.occupied())

@@ -217,6 +217,33 @@ int hd_sample_spans(hd_ctx* ctx, float* x_inout, const hd_schedule_ms* table, co
  * pointers, or a CoarseRestoration / VAE context. */
 int hd_mask_faces(hd_ctx* ctx, int n, const int32_t* slots, const float* mask, const float* known, const float* known_noise, void* stream);
 
+/* Progress previews: the denoised estimate of the row a face last ran, as an output of the sampling loop (diffusers'
+ * `pred_original_sample` / `callback_on_step_end`).
+ * hd_preview_config(on = 1, every, snapshots): from the next hd_prepare* on -- at once, when a batch is prepared -- the context owns the
+ * planes x0_preview [B,4,L,L], preview_rows [B] and preview_snaps [snapshots][B,4,L,L] (every >= 1, 0 <= snapshots <= 64; hd_debug_read
+ * reads them under these names, the rows as their int32 bits), and every hd_sample* call (all seven loop entry points) ends the update of
+ * row k of face f by storing
+ *     p = clamp((x - c0*eps)/c1, +-c2)            the x0 of that row: the value a multistep schedule keeps as its history
+ *     p = m * x0 + (1 - m) * known                for a face that carries a mask (hd_mask_faces), in this order: m == 1 gives x0 and
+ *                                                 m == 0 gives known bit for bit; the history keeps the unblended x0
+ * to the face's latest plane, with k as its row, and -- j = k - begin_f the row inside the face's own schedule (begin_f = 0 without
+ * hd_sample_spans), when (j + 1) % every == 0 and s = (j + 1)/every - 1 < snapshots -- to snapshot plane s as well.  A held face (past its
+ * end row, or an empty slot with start == end) writes nothing.  Nothing is rebuilt or recaptured by switching previews on or off or
+ * changing their size ("graph_captures" does not move), and while they are off the step launches read and compute what they did without
+ * this call: x_inout is bit for bit the same either way.  on = 0 frees the planes.  The configuration survives hd_prepare*; like the
+ * masks, every hd_prepare* resets all faces (row -1, zeroed planes), hd_prepare_slots the slots it refills, hd_preview_config(on = 1)
+ * itself all faces, and hd_sample* calls never do: a loop split over calls keeps its previews.  hd_get_option "preview" returns `on`.
+ * hd_eps and hd_scheduler_step* know no preview.  If a persistent stage gives up during a call (hd_check), the previews that call wrote
+ * are unspecified.  The call synchronises the device (not for the hot path).  HD_ERR_INVALID on a CoarseRestoration / VAE context, for
+ * every < 1, snapshots outside [0, 64] or on outside {0, 1}.
+ * hd_preview_read: copy, in stream order, the latest plane (snapshot == -1) or snapshot plane `snapshot` of faces slots[j] (host [n],
+ * distinct, in [0, B); NULL: n == B, faces in order) to x0_out [n,4,L,L] (device fp32), and to rows_out [n] (device int32, or NULL) the
+ * table row of that estimate: for a snapshot plane begin_f + (snapshot + 1)*every - 1; -1 when the face has not written the plane since it
+ * was prepared or refilled (its plane is then zero).  HD_ERR_NOT_READY without a prepared batch or with previews off; HD_ERR_INVALID for a
+ * duplicate or out-of-range slot, n outside [1, B], slots == NULL with n != B, or snapshot outside [-1, snapshots). */
+int hd_preview_config(hd_ctx* ctx, int on, int every, int snapshots);
+int hd_preview_read(hd_ctx* ctx, int n, const int32_t* slots, int snapshot, float* x0_out, int32_t* rows_out, void* stream);
+
 /* One scheduler update on its own: `scheduler.step(eps, t, x).prev_sample` (test_refiner.py:91) in
  * the coefficient form of hd_schedule (coef7 on the host); x updated in place.  noise/seed/step as in
  * hd_sample.  Needs no context. */
