@@ -24,8 +24,7 @@ struct ChainP {
     const uint4 *Wsca, *W3, *W4, *W5; // packed bf16 weights (K = C)
     const float *bsca, *b3, *b4, *b5, *beta, *gamma;
     const float* film;                // FiLM table; this block's [bias_ffn | gain_ffn] at film_bias_off / film_gain_off
-    int film_face_stride, film_step_stride, film_gain_off, film_bias_off;
-    const int* step_ptr;
+    int film_face_stride, film_gain_off, film_bias_off;
     float ln_eps;
     float* Xout;                      // [M][C] fp32
     unsigned short* Xout16;           // bf16 copy (next LayerNorm GEMM / down conv), or NULL
@@ -111,8 +110,7 @@ __global__ __launch_bounds__((ChainCfg<C, MT>::THREADS), (C == 128 && MT == 1 ? 
     chain_load_b<C>(p.W3, tile, lane, bw2);                        // conv3's right behind them (second register set)
     // ---- FiLM gain/bias of norm2 for this face/step into LDS ----
     {
-        const int step = p.step_ptr ? *p.step_ptr : 0;
-        const float* f = p.film + (size_t)step * p.film_step_stride + (size_t)(p.face0 + face) * p.film_face_stride;
+        const float* f = p.film + (size_t)(p.face0 + face) * p.film_face_stride;
         for (int k = tid; k < C; k += K::THREADS) { gb[k] = f[p.film_gain_off + k]; gb[C + k] = f[p.film_bias_off + k]; }
     }
     // per-column constants of all four GEMM epilogues: requested now.  Read at the top of each epilogue they were a dependent

@@ -171,6 +171,23 @@ struct SavedWs {
     float *cr_loc1 = nullptr, *cr_loc2 = nullptr, *cr_theta = nullptr;
 };
 
+// Which evaluation a launch of Chain::program is part of.  Every closure of the program derives what it needs from this one value:
+//   mode        set by                                   FiLM rows read from   face stride   step counter   ending also updates / stages
+//   EpsShared   hd_eps(n_t = 1)                          film_table            0             stays          no
+//   EpsFaces    hd_eps(n_t = B)                          film_table            film_total    stays          no
+//   LoopShared  hd_sample, hd_sample_multistep           Chain::film_cur       0             advances       yes, shared form
+//   LoopRows    hd_sample_rows*, _faces*, _spans         film_pf               film_total    advances       yes, per-face form
+// No other program reads it: the conditioning prologue, the FPG, CoarseRestoration and the VAE use static FiLM rows or none.
+enum class EvalMode { EpsShared, EpsFaces, LoopShared, LoopRows };
+constexpr bool mode_is_loop(EvalMode m) { return m == EvalMode::LoopShared || m == EvalMode::LoopRows; }      // the intro advances the step counter, the ending updates and stages
+constexpr bool mode_is_rows(EvalMode m) { return m == EvalMode::LoopRows; }                                   // the per-face instantiations of the stages and the ending
+constexpr bool mode_shared_row(EvalMode m) { return m == EvalMode::EpsShared || m == EvalMode::LoopShared; }  // one FiLM row for all faces (face stride 0)
+constexpr bool mode_allows_stages(EvalMode m) { return m != EvalMode::EpsFaces; }                             // persistent stages: a shared row, or their per-face instantiation
+static_assert(!mode_is_loop(EvalMode::EpsShared) && !mode_is_loop(EvalMode::EpsFaces) && mode_is_loop(EvalMode::LoopShared) && mode_is_loop(EvalMode::LoopRows), "EvalMode table");
+static_assert(!mode_is_rows(EvalMode::EpsShared) && !mode_is_rows(EvalMode::EpsFaces) && !mode_is_rows(EvalMode::LoopShared) && mode_is_rows(EvalMode::LoopRows), "EvalMode table");
+static_assert(mode_shared_row(EvalMode::EpsShared) && !mode_shared_row(EvalMode::EpsFaces) && mode_shared_row(EvalMode::LoopShared) && !mode_shared_row(EvalMode::LoopRows), "EvalMode table");
+static_assert(mode_allows_stages(EvalMode::EpsShared) && !mode_allows_stages(EvalMode::EpsFaces) && mode_allows_stages(EvalMode::LoopShared) && mode_allows_stages(EvalMode::LoopRows), "EvalMode table");
+
 struct hd_ctx {
     int L = 16, device = 0, S = 1;            // S = L/16
     bool conditional = true;                  // false: the unconditional Denoiser (models/denoiser/model.py:32-134): no priors, HCAs or IDC
@@ -224,18 +241,15 @@ struct hd_ctx {
     // FiLM / schedule
     float *t_dev = nullptr, *temb_a = nullptr, *temb_b = nullptr, *temb_c = nullptr, *film_table = nullptr;
     int film_rows_cap = 0;
-    int film_face_stride = 0, film_step_stride = 0;
-    bool film_from_cur = false;               // sampling loop: LayerNorm loaders read Chain::film_cur
+    EvalMode mode = EvalMode::EpsShared;      // which evaluation the next launches of Chain::program belong to (hd_eps / sample_impl set it)
     float* coef_dev = nullptr;
     int coef_cap = 0;
     float* c7_dev = nullptr;                  // [n] history coefficients of a multistep schedule (StepState::c7, not captured)
     int c7_cap = 0;
-    // per-face schedule positions (hd_sample_rows*): film_pf [B][film_total] holds every face's FiLM row of the current iteration (the
-    // LayerNorm loaders read it with film_face_stride = film_total while film_pf_mode is set, i.e. while the per-face graphs are captured).
-    // rows_gen: bumped wherever the captured graphs go stale (Chain::rows_gen).
+    // per-face schedule positions (hd_sample_rows*): film_pf [B][film_total] holds every face's FiLM row of the current iteration (what
+    // the LayerNorm loaders read in EvalMode::LoopRows).  rows_gen: bumped wherever the captured graphs go stale (Chain::rows_gen).
     float* film_pf = nullptr;
     size_t film_pf_cap = 0;
-    bool film_pf_mode = false;
     // the per-face arguments of a sampling call (FaceArgs): one device block for faces_cap faces, laid out per call for its batch and
     // uploaded with one copy.  Read through StepState and by the gather launch of the call: no graph holds a pointer into it.
     unsigned long long* faces_dev = nullptr;
@@ -268,7 +282,6 @@ struct hd_ctx {
     // "sample_face_stage_launches", "rows_stage_launches"); stage_count / face_stage_count count while a capture runs
     int stage_count = 0, face_stage_count = 0;
     int sample_stages = -1, sample_face_stages = -1, rows_stages = -1;
-    int advance = 0;
     hipEvent_t fork_ev = nullptr;
     // hd_sample never blocks on the caller's stream: the schedule is staged through two pinned buffers owned by the
     // context (the one written two calls ago is reused; its copy-done event is the only thing ever waited for), and the
@@ -344,10 +357,13 @@ struct hd_ctx {
     std::map<std::string, std::pair<void*, std::pair<size_t, int>>> dbg;   // name -> (ptr, (elems, is_bf16))
 };
 
-// The FiLM rows a denoiser LayerNorm of chain chp reads: per-face rows (hd_sample_rows*), the staged row of the sampling loop, or the table
-inline const float* film_src(const hd_ctx* c, const Chain* chp) {
-    return c->film_pf_mode ? c->film_pf : c->film_from_cur ? chp->film_cur : c->film_table;
+// The FiLM rows a denoiser LayerNorm of chain chp reads in the context's mode (the table above), and the one way a launch closure puts
+// them into its copy of a parameter block
+struct FilmRows { const float* base; int face_stride; };
+inline FilmRows film_rows(const hd_ctx* c, const Chain* chp) {
+    return {mode_is_rows(c->mode) ? c->film_pf : mode_is_loop(c->mode) ? chp->film_cur : c->film_table, mode_shared_row(c->mode) ? 0 : c->film_total};
 }
+template <class P> inline void set_film(P& p, const hd_ctx* c, const Chain* chp) { const FilmRows f = film_rows(c, chp); p.film = f.base; p.film_face_stride = f.face_stride; }
 
 #define HD_FAIL(ctx, code, ...)                                   \
     do {                                                          \
@@ -741,10 +757,7 @@ void add_gemm(hd_ctx* c, std::vector<Op>& prog, const std::string& name, GemmP p
     op.run = [c, chp, gp, lk, ek, t128, film](hipStream_t s) mutable -> hipError_t {
                         if (film && gp->film == nullptr) {        // denoiser FiLM rows live in the (re-allocatable) table
                             GemmP q = *gp;
-                            q.film = film_src(c, chp);
-                            q.film_face_stride = c->film_face_stride;
-                            q.film_step_stride = 0;
-                            q.step_ptr = nullptr;
+                            set_film(q, c, chp);
                             return dispatch_gemm(q, lk, ek, t128, s);
                         }
                         return dispatch_gemm(*gp, lk, ek, t128, s);
@@ -766,7 +779,6 @@ void add_naf_block(hd_ctx* c, std::vector<Op>& prog, const BlockW& bw, const Lev
         p.film = static_film;                           // nullptr -> patched from the table at launch
         p.film_bias_off = bw.film_off + (2 * half) * C;
         p.film_gain_off = bw.film_off + (2 * half + 1) * C;
-        p.film_face_stride = 0; p.film_step_stride = 0; p.step_ptr = nullptr;
     };
     bool strip_pool = false;
     static const bool no_fuse = hd_env("HD_NO_DWFUSE") != nullptr, no_chain = hd_env("HD_NO_CHAIN") != nullptr;
@@ -793,7 +805,7 @@ void add_naf_block(hd_ctx* c, std::vector<Op>& prog, const BlockW& bw, const Lev
         op.name = bw.name + ".conv2_gate_pool"; op.out = lv.G; op.out_elems = (size_t)M * C; op.out_bf16 = 1;
         op.run = [c, chp, q](hipStream_t s) mutable -> hipError_t {
             StripP r = q;
-            if (r.film == nullptr) { r.film = film_src(c, chp); r.film_face_stride = c->film_face_stride; }
+            if (r.film == nullptr) set_film(r, c, chp);
             return run_strip_dwgate(r, s);
         };
         prog.push_back(op);
@@ -846,10 +858,7 @@ void add_naf_block(hd_ctx* c, std::vector<Op>& prog, const BlockW& bw, const Lev
         op.name = bw.name + ".conv5"; op.out = lv.X; op.out_elems = (size_t)M * C; op.out_bf16 = 0;
         op.run = [c, chp, q, big, two](hipStream_t s) mutable -> hipError_t {
             ChainP r = q;
-            if (r.film == nullptr) {                      // denoiser: FiLM rows live in the (re-allocatable) table
-                r.film = film_src(c, chp); r.film_face_stride = c->film_face_stride; r.film_step_stride = 0;
-                r.step_ptr = nullptr;
-            }
+            if (r.film == nullptr) set_film(r, c, chp);   // denoiser: FiLM rows live in the (re-allocatable) table
             return big ? launch_chain<256, 1>(r, s) : two ? launch_chain<128, 2>(r, s) : launch_chain<128, 1>(r, s);
         };
         prog.push_back(op);

@@ -126,8 +126,8 @@ int build_denoiser_program(hd_ctx* c) {
         unsigned short* xb = c->ch->lv[0].Xb;
         const int M = c->ch->lv[0].M;
         intro_run = [=](hipStream_t s) -> hipError_t {
-            if (M >= kLongRunRows) hipLaunchKernelGGL(intro_conv_kernel<16>, dim3((M / 16 + 3) / 4), dim3(256), 0, s, lat, w, b, out, xb, sx, B, L, chp->step_state, c->advance);
-            else hipLaunchKernelGGL(intro_conv_kernel<kIntroPx>, dim3((M / kIntroPx + 3) / 4), dim3(256), 0, s, lat, w, b, out, xb, sx, B, L, chp->step_state, c->advance);
+            if (M >= kLongRunRows) hipLaunchKernelGGL(intro_conv_kernel<16>, dim3((M / 16 + 3) / 4), dim3(256), 0, s, lat, w, b, out, xb, sx, B, L, chp->step_state, mode_is_loop(c->mode));
+            else hipLaunchKernelGGL(intro_conv_kernel<kIntroPx>, dim3((M / kIntroPx + 3) / 4), dim3(256), 0, s, lat, w, b, out, xb, sx, B, L, chp->step_state, mode_is_loop(c->mode));
             return hipGetLastError();
         };
     }
@@ -173,9 +173,9 @@ int build_denoiser_program(hd_ctx* c) {
         Op op;
         op.name = c->den_blocks[first + nblk - 1].name + ".conv5"; op.out = lv.X; op.out_elems = (size_t)lv.M * lv.C; op.out_bf16 = 0;
         op.run = [c, chp, sp, sp2, have2, sub, l3, first](hipStream_t s) -> hipError_t {
-            if (have2 && c->xcd_ok && c->xcd_on && c->xcd2_on && c->chains.size() == 1 && c->film_face_stride == 0) {
+            if (have2 && c->xcd_ok && c->xcd_on && c->xcd2_on && c->chains.size() == 1 && mode_shared_row(c->mode)) {
                 X2StageP r = sp2;
-                r.film = film_src(c, chp);
+                r.film = film_rows(c, chp).base;
                 r.phase_limit = (c->stage_limit_first < 0 || c->stage_limit_first == first) ? c->xcd_phase_limit : 0;
                 r.force_global = c->xcd_force_global; r.test_abort = c->stage_test_abort;
                 const hipError_t e = run_xcd2_stage(l3 ? 1024 : 512, r, s);
@@ -184,13 +184,12 @@ int build_denoiser_program(hd_ctx* c) {
                 c->xcd2_on = false;
             }
             // (per-face rows of hd_sample_rows*: the K-split form's per-face instantiation; the autonomous-wave form above has none)
-            if (c->xcd_ok && c->xcd_on && c->chains.size() == 1 && (c->film_face_stride == 0 || c->film_pf_mode)) {
+            if (c->xcd_ok && c->xcd_on && c->chains.size() == 1 && mode_allows_stages(c->mode)) {
                 XStageP r = sp;
-                r.film = film_src(c, chp);
-                r.film_face_stride = c->film_pf_mode ? c->film_total : 0;
+                set_film(r, c, chp);
                 r.phase_limit = (c->stage_limit_first < 0 || c->stage_limit_first == first) ? c->xcd_phase_limit : 0;
                 r.force_global = c->xcd_force_global; r.test_abort = c->stage_test_abort;
-                const hipError_t e = c->film_pf_mode ? run_xcd_rows_stage(l3 ? 1024 : 512, r, s) : run_xcd_stage(l3 ? 1024 : 512, r, s);
+                const hipError_t e = mode_is_rows(c->mode) ? run_xcd_rows_stage(l3 ? 1024 : 512, r, s) : run_xcd_stage(l3 ? 1024 : 512, r, s);
                 if (e == hipSuccess) { ++c->stage_count; return e; }
                 (void)hipGetLastError();                      // as the face stages below: a refused launch is recoverable
                 c->xcd_on = false;
@@ -239,15 +238,14 @@ int build_denoiser_program(hd_ctx* c) {
         op.run = [c, chp, fp, sub, c128, first, intro_first](hipStream_t s) -> hipError_t {
             // (hd_eps's per-face timesteps and split batches run the per-GEMM form: every workgroup resident is what the stage needs; the
             // per-face rows of hd_sample_rows* have an instantiation of their own)
-            if (c->xcd_ok && c->face_on && c->chains.size() == 1 && (c->film_face_stride == 0 || c->film_pf_mode)) {
+            if (c->xcd_ok && c->face_on && c->chains.size() == 1 && mode_allows_stages(c->mode)) {
                 FStageP r = fp;
-                r.film = film_src(c, chp);
-                r.film_face_stride = c->film_pf_mode ? c->film_total : 0;
+                set_film(r, c, chp);
                 r.block_limit = (c->stage_limit_first < 0 || c->stage_limit_first == first) ? c->face_block_limit : 0;
                 r.test_abort = c->stage_test_abort;
-                r.intro_advance = c->advance;
-                const hipError_t e = c->film_pf_mode ? run_face_rows_stage(c128 ? 128 : 256, c128 ? 32 : c->face_l1_rows, r, s)
-                                                     : run_face_stage(c128 ? 128 : 256, c128 ? 32 : c->face_l1_rows, r, s);
+                r.intro_advance = mode_is_loop(c->mode);
+                const hipError_t e = mode_is_rows(c->mode) ? run_face_rows_stage(c128 ? 128 : 256, c128 ? 32 : c->face_l1_rows, r, s)
+                                                           : run_face_stage(c128 ? 128 : 256, c128 ? 32 : c->face_l1_rows, r, s);
                 if (e == hipSuccess) { ++c->stage_count; ++c->face_stage_count; return e; }
                 (void)hipGetLastError();                      // (the dynamic-LDS grant was refused: nothing was launched) -> the per-block launches
                 c->face_on = false;
@@ -317,20 +315,24 @@ int build_denoiser_program(hd_ctx* c) {
             ep.B = B; ep.Xg = c->ch->lv[0].Xg; ep.W = c->hca[4].fused.w; ep.bias = c->hca[4].fused.bias; ep.ewT = w; ep.eb = b; ep.eps = eps;
             hca4_run = hca4[0].run;
         }
+        // sampling loop: the ending launch also applies the scheduler update to this chain's latents and stages the next step's FiLM
+        // row -- per-face rows: every face of this chain stages its own (all zero outside the loop: nothing but the conv)
+        auto sched_args = [c, chp, L]() {
+            SchedArgs sa{};
+            if (!mode_is_loop(c->mode)) return sa;
+            const size_t per_face = (size_t)4 * L * L;
+            sa.lat = chp->lat; sa.coef = c->coef_dev; sa.st = chp->step_state;
+            sa.elem0 = (int)(chp->face0 * per_face); sa.n_total = (int)(c->B * per_face);
+            sa.film_table = c->film_table; sa.film_total = c->film_total;
+            sa.film_cur = mode_is_rows(c->mode) ? c->film_pf + (size_t)chp->face0 * c->film_total : chp->film_cur;
+            return sa;
+        };
         prog.push_back({"ending", [=](hipStream_t s) -> hipError_t {
-                            // sampling loop (film_from_cur): the launch also applies the scheduler update to this
-                            // chain's latents and stages the next step's FiLM row
-                            SchedArgs sa{};
+                            const bool rows = mode_is_rows(c->mode);
                             if (fuse_end && c->end_fused) {
                                 EndP q = ep;
-                                if (c->film_from_cur) {
-                                    const size_t per_face = (size_t)4 * L * L;
-                                    q.sa.lat = chp->lat; q.sa.coef = c->coef_dev; q.sa.st = chp->step_state;
-                                    q.sa.elem0 = (int)(chp->face0 * per_face); q.sa.n_total = (int)(c->B * per_face);
-                                    q.sa.film_table = c->film_table; q.sa.film_cur = chp->film_cur; q.sa.film_total = c->film_total;
-                                    if (c->film_pf_mode) q.sa.film_cur = c->film_pf + (size_t)chp->face0 * c->film_total;   // this chain's faces
-                                }
-                                const hipError_t e = launch_hca_ending(q, s, c->film_from_cur && c->film_pf_mode);
+                                q.sa = sched_args();
+                                const hipError_t e = launch_hca_ending(q, s, rows);
                                 if (e == hipSuccess) return e;
                                 (void)hipGetLastError();              // the dynamic-LDS grant was refused: nothing was launched -> the two launches
                                 c->end_fused = false;
@@ -338,20 +340,14 @@ int build_denoiser_program(hd_ctx* c) {
                             if (hca4_run) { const hipError_t e = hca4_run(s); if (e != hipSuccess) return e; }
                             const bool long_runs = M >= kLongRunRows;
                             unsigned nb = (unsigned)((M / (long_runs ? 16 : kEndingPx) + 3) / 4);
-                            if (c->film_from_cur) {
-                                const size_t per_face = (size_t)4 * L * L;
-                                sa.lat = chp->lat; sa.coef = c->coef_dev; sa.st = chp->step_state;
-                                sa.elem0 = (int)(chp->face0 * per_face); sa.n_total = (int)(c->B * per_face);
-                                sa.film_table = c->film_table; sa.film_cur = chp->film_cur; sa.film_total = c->film_total;
-                                if (c->film_pf_mode) {                // per-face rows: every face of this chain stages its own next row
-                                    sa.film_cur = c->film_pf + (size_t)chp->face0 * c->film_total;
-                                    nb += (unsigned)(B * film_stage_pieces(c->film_total));
-                                    if (long_runs) hipLaunchKernelGGL((ending_conv_kernel<16, true>), dim3(nb), dim3(256), 0, s, X, w, b, eps, B, L, sa);
-                                    else hipLaunchKernelGGL((ending_conv_kernel<kEndingPx, true>), dim3(nb), dim3(256), 0, s, X, w, b, eps, B, L, sa);
-                                    return hipGetLastError();
-                                }
-                                nb += (unsigned)((c->film_total / 4 + 255) / 256);
+                            const SchedArgs sa = sched_args();
+                            if (rows) {                               // the workgroups behind the conv's stage the next row(s)
+                                nb += (unsigned)(B * film_stage_pieces(c->film_total));
+                                if (long_runs) hipLaunchKernelGGL((ending_conv_kernel<16, true>), dim3(nb), dim3(256), 0, s, X, w, b, eps, B, L, sa);
+                                else hipLaunchKernelGGL((ending_conv_kernel<kEndingPx, true>), dim3(nb), dim3(256), 0, s, X, w, b, eps, B, L, sa);
+                                return hipGetLastError();
                             }
+                            if (mode_is_loop(c->mode)) nb += (unsigned)((c->film_total / 4 + 255) / 256);
                             if (long_runs) hipLaunchKernelGGL(ending_conv_kernel<16>, dim3(nb), dim3(256), 0, s, X, w, b, eps, B, L, sa);
                             else hipLaunchKernelGGL(ending_conv_kernel<kEndingPx>, dim3(nb), dim3(256), 0, s, X, w, b, eps, B, L, sa);
                             return hipGetLastError();
@@ -1124,10 +1120,7 @@ int hd_eps(hd_ctx* c, const float* x, const float* timesteps, int n_t, float* ep
     c->film_valid = false;                               // rows [0, n_t) are overwritten
     rc = compute_film(c, timesteps, n_t, s);
     if (rc) return rc;
-    c->film_step_stride = 0;
-    c->film_from_cur = false;
-    c->film_face_stride = (n_t == 1) ? 0 : c->film_total;
-    c->advance = 0;
+    c->mode = (n_t == 1) ? EvalMode::EpsShared : EvalMode::EpsFaces;
     for (auto& ch : c->chains) {
         rc = run_ops(c, ch.program, s, ch.index == 0 ? c->op_limit : -1);
         if (rc) return rc;
@@ -1301,10 +1294,6 @@ static int film_for_call(hd_ctx* c, const SampleCall& call, bool reuse, hipStrea
     } else {
         HIPCHECK(c, hipStreamWaitEvent(s, c->film_ev, 0));       // no-op on the stream that computed it
     }
-    c->film_step_stride = c->film_total;
-    c->film_face_stride = 0;
-    c->film_from_cur = true;
-    c->advance = 1;
     if (call.start_rows) {                                // every face's row r_f (clamped to its last row)
         const FaceArgs dev = face_args(c->faces_dev, c->B);
         hipLaunchKernelGGL(film_rows_gather_kernel, dim3(8, c->B), dim3(256), 0, s, c->film_pf, c->film_table, dev.rows,
@@ -1319,8 +1308,8 @@ static int film_for_call(hd_ctx* c, const SampleCall& call, bool reuse, hipStrea
 
 // One graph pair per chain: its launch program + its scheduler update, one step and kGraphSteps steps back to back (fewer graph
 // launches).  Faces never interact, so the chains are independent over the whole loop and each graph is replayed on the chain's own
-// stream.  pf: the per-face pair (Chain::graph_rows_*) -- the LayerNorm loaders read film_pf with a face stride while the program is
-// captured.  Nothing is captured while the pair asked for is current.
+// stream.  pf: the per-face pair (Chain::graph_rows_*), captured in EvalMode::LoopRows like every pair in the mode sample_impl set.
+// Nothing is captured while the pair asked for is current.
 static int capture_step_graphs(hd_ctx* c, bool pf) {
     bool stale = !c->graphs_valid || c->graph_film != c->film_table || c->graph_B != c->B;
     if (pf) {
@@ -1328,7 +1317,6 @@ static int capture_step_graphs(hd_ctx* c, bool pf) {
         for (auto& ch : c->chains) stale |= !ch.graph_rows_exec || ch.rows_gen != c->rows_gen || ch.rows_film != c->film_table;
     }
     if (!stale) return HD_OK;
-    if (pf) { c->film_pf_mode = true; c->film_face_stride = c->film_total; }
     c->stage_count = c->face_stage_count = 0;
     for (auto& ch : c->chains) {
         hipGraphExec_t& g1 = pf ? ch.graph_rows_exec : ch.graph_exec;
@@ -1347,7 +1335,7 @@ static int capture_step_graphs(hd_ctx* c, bool pf) {
             if (e == hipSuccess) e = hipGraphInstantiate(multi ? &gm : &g1, graph, nullptr, nullptr, 0);
             if (e == hipSuccess) ++c->graph_captures;
             if (graph) (void)hipGraphDestroy(graph);
-            if (e != hipSuccess) { c->film_pf_mode = false; c->film_face_stride = 0; HD_FAIL(c, HD_ERR_HIP, "graph capture/instantiate failed: %s", hipGetErrorString(e)); }
+            if (e != hipSuccess) HD_FAIL(c, HD_ERR_HIP, "graph capture/instantiate failed: %s", hipGetErrorString(e));
             if (multi == 0 && &ch == &c->chains[0]) {      // the one-step program of chain 0: what hd_get_option reports
                 (pf ? c->rows_stages : c->sample_stages) = c->stage_count;
                 if (!pf) c->sample_face_stages = c->face_stage_count;
@@ -1355,7 +1343,6 @@ static int capture_step_graphs(hd_ctx* c, bool pf) {
         }
         if (pf) { ch.rows_gen = c->rows_gen; ch.rows_film = c->film_table; }
     }
-    c->film_pf_mode = false; c->film_face_stride = 0;
     if (!pf) { c->graphs_valid = true; c->graph_film = c->film_table; c->graph_B = c->B; }
     return HD_OK;
 }
@@ -1406,6 +1393,7 @@ static int sample_impl(hd_ctx* c, float* x_inout, const SampleCall& call, void* 
     rc = stage_loop_state(c, call, !reuse_film, s);
     if (rc) return rc;
     HIPCHECK(c, hipMemcpyAsync(c->lat, x_inout, nlat * sizeof(float), hipMemcpyDeviceToDevice, s));
+    c->mode = pf ? EvalMode::LoopRows : EvalMode::LoopShared;
     rc = film_for_call(c, call, reuse_film, s);
     if (!rc) rc = capture_step_graphs(c, pf);
     if (!rc) rc = replay_step_graphs(c, pf, n_iters, s);

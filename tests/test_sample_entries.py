@@ -41,10 +41,12 @@ def _tables():
     return ddpm.coefficient_table(), sde.coefficient_table(), ScheduleSet({"ddpm": ddpm, "sde": sde})
 
 
-def _call(c, entry, x):
-    """One call of `entry` on the prepared batch of context c: staggered start rows (face 2 is past its last row: held), per-face keys."""
+def _call(c, entry, x, tab=None):
+    """One call of `entry` on the prepared batch of context c: staggered start rows (face 2 is past its last row: held), per-face keys.
+    tab: a 7-column table for the single-step entry points in place of the DDPM one."""
     B = x.shape[0]
     ddpm, sde, sset = _tables()
+    ddpm = tab or ddpm
     rows = [0, 1, 3, 2][:B]
     seeds = [11 + f for f in range(B)]
     if entry == "hd_sample_spans":
@@ -140,3 +142,48 @@ def test_entry_with_two_chains_equals_a_fresh_context(shared_two_chains, weights
     assert torch.equal(got[(4, entry)], want), entry
     assert not torch.equal(want[3], data[0][3])                        # a face of the second chain ran
     assert captures == 2 * fresh_captures                              # one plain and one per-face pair per chain, whatever the order
+
+
+# Which kind of evaluation a launch of the denoiser program belongs to is state of the context that every call sets for itself: one
+# timestep or one per face (hd_eps), the loop's shared staged row (hd_sample) or per-face rows (hd_sample_rows).  The order of the calls
+# on one context must not matter.
+MODE_SEQUENCE = ("eps_one", "eps_faces", "hd_sample_rows", "eps_one", "hd_sample", "eps_faces")
+
+
+def _mode_call(c, what, x):
+    if what.startswith("eps"):
+        t = 500 if what == "eps_one" else torch.tensor([500.0, 37.0])
+        out = c.e.eps(x.cuda(), t)
+        return c.done((0, out))
+    return _call(c, what, x, _sched("ddim", 3).coefficient_table())          # hd_sample_rows: start rows (0, 1)
+
+
+def _mode_ctx(weights, data, stages):
+    m = make_model(weights)
+    c = Ctx(m)
+    if not stages:                                                           # the per-GEMM form of the same closures
+        for key in (b"xcd", b"face"):
+            assert _L().hd_set_option(c.ctx, key, 0) == 0
+    c.prep(data[2][:2], data[1][:2])
+    return m, c
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("stages", (True, False), ids=("stages", "per_gemm"))
+def test_evaluation_modes_in_any_order_equal_a_fresh_context(gpu, weights16, data, stages):
+    x = data[0][:2]
+    with _env({}):
+        want = {}
+        for what in sorted(set(MODE_SEQUENCE)):
+            m, c = _mode_ctx(weights16, data, stages)
+            want[what] = _mode_call(c, what, x)
+            free(m)
+        m, c = _mode_ctx(weights16, data, stages)
+        got = [_mode_call(c, what, x) for what in MODE_SEQUENCE]
+        launches = c.opt(b"sample_stage_launches"), c.opt(b"rows_stage_launches")
+        free(m)
+    assert (min(launches) > 0) if stages else (launches == (0, 0)), launches
+    for i, what in enumerate(MODE_SEQUENCE):
+        assert bool(torch.isfinite(got[i]).all()) and not torch.equal(got[i], x), (i, what)
+        assert torch.equal(got[i], want[what]), (i, what)
+    assert not torch.equal(want["eps_one"][1], want["eps_faces"][1])         # face 1 has its own timestep
