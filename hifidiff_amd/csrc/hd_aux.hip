@@ -132,12 +132,21 @@ static int alloc_cr_new(hd_ctx* c, int B) {
         rc |= dev_alloc(c, &v.pooled16, (size_t)B * v.C);
         if (l > 0) rc |= dev_alloc(c, &c->cr_skip[l], mc);
         if (rc) return rc;
+        const std::string s = std::to_string(l);          // introspection (hd_debug_read), names as for the refiner's levels
+        c->dbg["X" + s] = {v.X, {mc, 0}}; c->dbg["Y" + s] = {v.Y, {mc, 0}}; c->dbg["T1_" + s] = {v.T1, {2 * mc, 0}};
+        c->dbg["G" + s] = {v.G, {mc, 1}}; c->dbg["pooled" + s] = {v.pooled, {(size_t)B * v.C, 0}}; c->dbg["S" + s] = {v.S, {(size_t)B * v.C, 0}};
+        c->dbg["Xb" + s] = {v.Xb, {mc, 1}}; c->dbg["Yb" + s] = {v.Yb, {mc, 1}};
+        c->dbg["pooled16_" + s] = {v.pooled16, {(size_t)B * v.C, 1}};
+        c->dbg["sx" + s] = {v.sx, {(size_t)v.M * (v.C / 32) * 2, 0}}; c->dbg["sy" + s] = {v.sy, {(size_t)v.M * (v.C / 32) * 2, 0}};
+        if (l > 0) c->dbg["skip" + s] = {c->cr_skip[l], {mc, 0}};
     }
     // STN temporaries sized for the largest stage (side 128: 8 x 60 x 60 and 10 x 27 x 27 per face)
     rc |= dev_alloc(c, &c->cr_loc1, (size_t)B * 8 * 60 * 60); rc |= dev_alloc(c, &c->cr_loc2, (size_t)B * 10 * 27 * 27);
     rc |= dev_alloc(c, &c->cr_theta, (size_t)B * 6);
     rc |= dev_alloc(c, &ch.step_state, 1);
     if (rc) return rc;
+    c->dbg["loc1"] = {c->cr_loc1, {(size_t)B * 8 * 60 * 60, 0}}; c->dbg["loc2"] = {c->cr_loc2, {(size_t)B * 10 * 27 * 27, 0}};   // a smaller stage fills the front
+    c->dbg["theta"] = {c->cr_theta, {(size_t)B * 6, 0}};
     HIPCHECK(c, hipMemset(ch.step_state, 0, sizeof(StepState)));
     c->B = B;
     c->ch = &ch;
@@ -187,6 +196,7 @@ static int build_cr_program(hd_ctx* c, const float* in, float* out) {
             add_gemm(c, prog, g.name, p, LK_CONV_BF16, EK_BIASF32);
             float* skip = c->cr_skip[g.level + 1]; const float* src = dst.X; const size_t bytes = (size_t)dst.M * dst.C * sizeof(float);
             prog.push_back({g.name + ".skip_copy", [=](hipStream_t s) -> hipError_t { return hipMemcpyAsync(skip, src, bytes, hipMemcpyDeviceToDevice, s); }});
+            prog.back().out = skip; prog.back().out_elems = (size_t)dst.M * dst.C;
             np = dst.C / 32; cnt = 32;
         } else if (g.samp == 2) {
             const Level& lo = ch.lv[g.level - 1];

@@ -122,9 +122,9 @@ static __global__ __launch_bounds__(256) void stn_fc_kernel(const float* __restr
     }
     __syncthreads();
     if (threadIdx.x < 6) {
-        float a = b2[threadIdx.x];
+        float a = 0.f;                                             // bias last: small products added onto a bias near 1 lose a rounding each
         for (int j = 0; j < n1; ++j) a += w2[threadIdx.x * n1 + j] * h[j];
-        theta[blockIdx.x * 6 + threadIdx.x] = a;
+        theta[blockIdx.x * 6 + threadIdx.x] = a + b2[threadIdx.x];
     }
 }
 
