@@ -67,7 +67,7 @@ static void add_stn(hd_ctx* c, std::vector<Op>& prog, const std::string& name, c
     const float *w3 = find_raw(c, name + ".localization.3.weight")->dev, *b3 = find_raw(c, name + ".localization.3.bias")->dev;
     const float *f0w = find_raw(c, name + ".fc_loc.0.weight")->dev, *f0b = find_raw(c, name + ".fc_loc.0.bias")->dev;
     const float *f2w = find_raw(c, name + ".fc_loc.2.weight")->dev, *f2b = find_raw(c, name + ".fc_loc.2.bias")->dev;
-    float *loc1 = c->cr_loc1, *loc2 = c->cr_loc2, *theta = c->cr_theta;
+    float *loc1 = c->ws->cr_loc1, *loc2 = c->ws->cr_loc2, *theta = c->ws->cr_theta;
     const float* X = lv.X; float* Y = lv.Y; unsigned short* Yb = lv.Yb;
     const int C = lv.C, H = lv.H;
     {   // localization[0..2]: conv k0 (valid) on the channels-last map -> maxpool 2 -> relu
@@ -105,59 +105,40 @@ static void add_stn(hd_ctx* c, std::vector<Op>& prog, const std::string& name, c
     prog.back().out = Y; prog.back().out_elems = (size_t)lv.M * C;
 }
 
-static int alloc_cr_new(hd_ctx* c, int B);
-static int alloc_cr(hd_ctx* c, int B) {
-    if (B == c->B) return HD_OK;
-    park_workspace(c);
-    if (unpark_workspace(c, B)) return HD_OK;
-    c->ws_scope = true;
-    const int rc = alloc_cr_new(c, B);
-    c->ws_scope = false;
-    if (rc) { c->B = B; park_workspace(c); auto it = c->ws_cache.find(B); if (it != c->ws_cache.end()) { destroy_saved(it->second); c->ws_cache.erase(it); } }
-    return rc;
-}
-static int alloc_cr_new(hd_ctx* c, int B) {
-    c->chains.resize(1);
-    Chain& ch = c->chains[0];
+static int alloc_cr_new(hd_ctx* c, Workspace& w, int B) {
+    w.chains.resize(1);
+    Chain& ch = w.chains[0];
     ch.index = 0; ch.B = B; ch.face0 = 0;
     int rc = 0;
     for (int l = 0; l < 5; ++l) {
         Level& v = ch.lv[l];
         v.C = 32 << l; v.H = 128 >> l; v.M = B * v.H * v.H;
         const size_t mc = (size_t)v.M * v.C;
-        rc |= dev_alloc(c, &v.X, mc); rc |= dev_alloc(c, &v.Y, mc); rc |= dev_alloc(c, &v.T1, 2 * mc + (size_t)B * ((v.H + 7) / 8) * v.C);
-        rc |= dev_alloc(c, &v.G, mc); rc |= dev_alloc(c, &v.pooled, (size_t)B * v.C); rc |= dev_alloc(c, &v.S, (size_t)B * v.C);
-        rc |= dev_alloc(c, &v.sx, (size_t)v.M * (v.C / 32)); rc |= dev_alloc(c, &v.sy, (size_t)v.M * (v.C / 32));
-        rc |= dev_alloc(c, &v.Xb, mc); rc |= dev_alloc(c, &v.Yb, mc); rc |= dev_alloc(c, &v.Xg, 64);
-        rc |= dev_alloc(c, &v.pooled16, (size_t)B * v.C);
-        if (l > 0) rc |= dev_alloc(c, &c->cr_skip[l], mc);
+        rc |= alloc_level(c, v, B, 64, true, l);          // names as for the refiner's levels; no HCA reads Xg here
+        if (l > 0) rc |= ws_alloc(c, &w.cr_skip[l], mc);
         if (rc) return rc;
-        const std::string s = std::to_string(l);          // introspection (hd_debug_read), names as for the refiner's levels
-        c->dbg["X" + s] = {v.X, {mc, 0}}; c->dbg["Y" + s] = {v.Y, {mc, 0}}; c->dbg["T1_" + s] = {v.T1, {2 * mc, 0}};
-        c->dbg["G" + s] = {v.G, {mc, 1}}; c->dbg["pooled" + s] = {v.pooled, {(size_t)B * v.C, 0}}; c->dbg["S" + s] = {v.S, {(size_t)B * v.C, 0}};
-        c->dbg["Xb" + s] = {v.Xb, {mc, 1}}; c->dbg["Yb" + s] = {v.Yb, {mc, 1}};
-        c->dbg["pooled16_" + s] = {v.pooled16, {(size_t)B * v.C, 1}};
-        c->dbg["sx" + s] = {v.sx, {(size_t)v.M * (v.C / 32) * 2, 0}}; c->dbg["sy" + s] = {v.sy, {(size_t)v.M * (v.C / 32) * 2, 0}};
-        if (l > 0) c->dbg["skip" + s] = {c->cr_skip[l], {mc, 0}};
+        if (l > 0) w.dbg["skip" + std::to_string(l)] = {w.cr_skip[l], {mc, 0}};
     }
     // STN temporaries sized for the largest stage (side 128: 8 x 60 x 60 and 10 x 27 x 27 per face)
-    rc |= dev_alloc(c, &c->cr_loc1, (size_t)B * 8 * 60 * 60); rc |= dev_alloc(c, &c->cr_loc2, (size_t)B * 10 * 27 * 27);
-    rc |= dev_alloc(c, &c->cr_theta, (size_t)B * 6);
-    rc |= dev_alloc(c, &ch.step_state, 1);
+    rc |= ws_alloc(c, &w.cr_loc1, (size_t)B * 8 * 60 * 60); rc |= ws_alloc(c, &w.cr_loc2, (size_t)B * 10 * 27 * 27);
+    rc |= ws_alloc(c, &w.cr_theta, (size_t)B * 6);
+    rc |= ws_alloc(c, &ch.step_state, 1);
     if (rc) return rc;
-    c->dbg["loc1"] = {c->cr_loc1, {(size_t)B * 8 * 60 * 60, 0}}; c->dbg["loc2"] = {c->cr_loc2, {(size_t)B * 10 * 27 * 27, 0}};   // a smaller stage fills the front
-    c->dbg["theta"] = {c->cr_theta, {(size_t)B * 6, 0}};
+    w.dbg["loc1"] = {w.cr_loc1, {(size_t)B * 8 * 60 * 60, 0}}; w.dbg["loc2"] = {w.cr_loc2, {(size_t)B * 10 * 27 * 27, 0}};   // a smaller stage fills the front
+    w.dbg["theta"] = {w.cr_theta, {(size_t)B * 6, 0}};
     HIPCHECK(c, hipMemset(ch.step_state, 0, sizeof(StepState)));
-    c->B = B;
-    c->ch = &ch;
+    w.B = B;
     return HD_OK;
+}
+static int alloc_cr(hd_ctx* c, int B) {
+    return switch_workspace(c, B, [&](Workspace& w) { return alloc_cr_new(c, w, B); });
 }
 
 // in / out: [B,3,128,128] fp32 NCHW device pointers of this call (captured by the first and last op)
 static int build_cr_program(hd_ctx* c, const float* in, float* out) {
-    std::vector<Op>& prog = c->cr_program;
+    std::vector<Op>& prog = c->ws->cr_program;
     prog.clear();
-    Chain& ch = c->chains[0];
+    Chain& ch = c->ws->chains[0];
     const int B = ch.B;
     {
         const float *w = find_raw(c, "intro.weight")->dev, *b = find_raw(c, "intro.bias")->dev;
@@ -176,7 +157,7 @@ static int build_cr_program(hd_ctx* c, const float* in, float* out) {
         if (si == 5) {
             // decoders.0 input: middle output (STN result in Y) + skip of level 4 (model.py:82-83); later decoder inputs
             // get their skip added by the preceding up-conv epilogue
-            const float *A = lv.Y, *S = c->cr_skip[4]; float* X = lv.X; unsigned short* Xb = lv.Xb; float2* sx = lv.sx;
+            const float *A = lv.Y, *S = c->ws->cr_skip[4]; float* X = lv.X; unsigned short* Xb = lv.Xb; float2* sx = lv.sx;
             const int M = lv.M, C = lv.C;
             prog.push_back({g.name + ".skip_add", [=](hipStream_t s) -> hipError_t {
                                 hipLaunchKernelGGL(add_rows_stats_kernel, dim3((M + 3) / 4), dim3(256), 0, s, A, S, X, Xb, sx, M, C);
@@ -194,13 +175,13 @@ static int build_cr_program(hd_ctx* c, const float* in, float* out) {
             p.Hout = dst.H; p.Wout = dst.H; p.ntaps = 4;
             p.out = dst.X; p.ldo = dst.C; p.stats_out = dst.sx; p.out16 = dst.Xb;
             add_gemm(c, prog, g.name, p, LK_CONV_BF16, EK_BIASF32);
-            float* skip = c->cr_skip[g.level + 1]; const float* src = dst.X; const size_t bytes = (size_t)dst.M * dst.C * sizeof(float);
+            float* skip = c->ws->cr_skip[g.level + 1]; const float* src = dst.X; const size_t bytes = (size_t)dst.M * dst.C * sizeof(float);
             prog.push_back({g.name + ".skip_copy", [=](hipStream_t s) -> hipError_t { return hipMemcpyAsync(skip, src, bytes, hipMemcpyDeviceToDevice, s); }});
             prog.back().out = skip; prog.back().out_elems = (size_t)dst.M * dst.C;
             np = dst.C / 32; cnt = 32;
         } else if (g.samp == 2) {
             const Level& lo = ch.lv[g.level - 1];
-            add_up(c, prog, g.name, c->cr_samp[si], lv.Yb, true, lv.M, lv.H, lv.C, lo.X, g.level - 1 >= 1 ? c->cr_skip[g.level - 1] : nullptr, 2, lo.Xb, lo.sx);
+            add_up(c, prog, g.name, c->cr_samp[si], lv.Yb, true, lv.M, lv.H, lv.C, lo.X, g.level - 1 >= 1 ? c->ws->cr_skip[g.level - 1] : nullptr, 2, lo.Xb, lo.sx);
             np = lo.C / 32; cnt = 32;
         } else {
             prog.back().name = g.name;                             // middle stage: its output is the STN result
@@ -215,7 +196,7 @@ static int build_cr_program(hd_ctx* c, const float* in, float* out) {
                         }});
         prog.back().out = out; prog.back().out_elems = M * 3;
     }
-    c->cr_in = in; c->cr_out = out;
+    c->ws->cr_in = in; c->ws->cr_out = out;
     return HD_OK;
 }
 
@@ -311,36 +292,29 @@ int finalize_vae(hd_ctx* c) {
     return HD_OK;
 }
 
-static int alloc_vae_new(hd_ctx* c, int B, int R) {
-    auto& v = c->vws;
+static int alloc_vae_new(hd_ctx* c, Workspace& w, int B, int R) {
+    auto& v = w.vws;
     const size_t px = (size_t)B * R * R, big = px * 256, lat = (size_t)B * (R / 8) * (R / 8);
     int rc = 0;
-    rc |= dev_alloc(c, &v.X, big); rc |= dev_alloc(c, &v.T, big); rc |= dev_alloc(c, &v.S, big);
-    rc |= dev_alloc(c, &v.H, big); rc |= dev_alloc(c, &v.H2, big); rc |= dev_alloc(c, &v.Xb, big); rc |= dev_alloc(c, &v.U, big);
-    rc |= dev_alloc(c, &v.in8, px); rc |= dev_alloc(c, &v.resz, px * 3); rc |= dev_alloc(c, &v.out3, px * 3);
-    rc |= dev_alloc(c, &v.mom, lat * 8); rc |= dev_alloc(c, &v.Q, lat * 512); rc |= dev_alloc(c, &v.K, lat * 512); rc |= dev_alloc(c, &v.V, lat * 512);
-    rc |= dev_alloc(c, &v.part, (size_t)B * ((size_t)R * R / 256 + 1) * GN_GROUPS * 2);
+    rc |= ws_alloc(c, &v.X, big); rc |= ws_alloc(c, &v.T, big); rc |= ws_alloc(c, &v.S, big);
+    rc |= ws_alloc(c, &v.H, big); rc |= ws_alloc(c, &v.H2, big); rc |= ws_alloc(c, &v.Xb, big); rc |= ws_alloc(c, &v.U, big);
+    rc |= ws_alloc(c, &v.in8, px); rc |= ws_alloc(c, &v.resz, px * 3); rc |= ws_alloc(c, &v.out3, px * 3);
+    rc |= ws_alloc(c, &v.mom, lat * 8); rc |= ws_alloc(c, &v.Q, lat * 512); rc |= ws_alloc(c, &v.K, lat * 512); rc |= ws_alloc(c, &v.V, lat * 512);
+    rc |= ws_alloc(c, &v.part, (size_t)B * ((size_t)R * R / 256 + 1) * GN_GROUPS * 2);
     v.B = B; v.R = R;
+    w.B = B;
     return rc;
 }
+// one workspace per (batch, resolution): encode at R and decode at latent R / 8 share it
 static int alloc_vae(hd_ctx* c, int B, int R) {
-    const int key = B + 8192 * (R / 8);
-    if (key == c->B) return HD_OK;
-    park_workspace(c);
-    if (unpark_workspace(c, key)) return HD_OK;
-    c->ws_scope = true;
-    const int rc = alloc_vae_new(c, B, R);
-    c->ws_scope = false;
-    c->B = key;
-    if (rc) { park_workspace(c); auto it = c->ws_cache.find(key); if (it != c->ws_cache.end()) { destroy_saved(it->second); c->ws_cache.erase(it); } }
-    return rc;
+    return switch_workspace(c, B + 8192 * (R / 8), [&](Workspace& w) { return alloc_vae_new(c, w, B, R); });
 }
 
 // ---- launch-program pieces (channels-last fp32 residual stream X [B*H*H][C]) ----
 static void vae_groupnorm(hd_ctx* c, std::vector<Op>& prog, const std::string& name, const float* x, const float* gw, const float* gb,
                           unsigned short* y, int B, int H, int C, bool silu) {
     const int HW = H * H, chunk = 256, nch = (HW + chunk - 1) / chunk;
-    double* part = c->vws.part;
+    double* part = c->ws->vws.part;
     prog.push_back({name, [=](hipStream_t s) -> hipError_t {
                         hipLaunchKernelGGL(groupnorm_partial_kernel, dim3(nch, B), dim3(256), 0, s, x, part, HW, C, chunk);
                         hipLaunchKernelGGL(groupnorm_apply_kernel, dim3(nch, B), dim3(256), 0, s, x, part, nch, gw, gb, y, HW, C, chunk, 1e-6f, silu ? 1 : 0);
@@ -360,7 +334,7 @@ static void vae_conv3(hd_ctx* c, std::vector<Op>& prog, const std::string& name,
     else add_gemm(c, prog, name, p, LK_CONV_BF16, EK_BIASF32);
 }
 static void vae_resnet(hd_ctx* c, std::vector<Op>& prog, const hd_ctx::VaeRes& r, int B, int H, unsigned short* out16) {
-    auto& v = c->vws;
+    auto& v = c->ws->vws;
     vae_groupnorm(c, prog, r.name + ".norm1", v.X, r.n1w, r.n1b, v.H, B, H, r.cin, true);
     vae_conv3(c, prog, r.name + ".conv1", r.c1, v.H, B, H, 1, v.T, nullptr, nullptr);
     vae_groupnorm(c, prog, r.name + ".norm2", v.T, r.n2w, r.n2b, v.H2, B, H, r.cout, true);
@@ -374,7 +348,7 @@ static void vae_resnet(hd_ctx* c, std::vector<Op>& prog, const hd_ctx::VaeRes& r
     vae_conv3(c, prog, r.name + ".conv2", r.c2, v.H2, B, H, 1, v.X, resid, out16);
 }
 static void vae_attention(hd_ctx* c, std::vector<Op>& prog, const hd_ctx::VaeAttn& a, int B, int H) {
-    auto& v = c->vws;
+    auto& v = c->ws->vws;
     const int T = H * H, M = B * T;
     vae_groupnorm(c, prog, a.name + ".group_norm", v.X, a.gw, a.gb, v.H, B, H, 512, false);
     const PackedW* ws[3] = {&a.q, &a.k, &a.v}; float* outs[3] = {v.Q, v.K, v.V}; const char* nm[3] = {".to_q", ".to_k", ".to_v"};
@@ -398,8 +372,8 @@ static void vae_attention(hd_ctx* c, std::vector<Op>& prog, const hd_ctx::VaeAtt
 
 static int build_vae_encode(hd_ctx* c, int B, int in_res, int R, const float* images, int vae_range, const float* noise, uint64_t seed,
                             float* moments_out, float* latents_out) {
-    auto& prog = c->vae_enc_prog; prog.clear();
-    auto& v = c->vws; auto& w = c->vw;
+    auto& prog = c->ws->vae_enc_prog; prog.clear();
+    auto& v = c->ws->vws; auto& w = c->vw;
     const float* src = images;
     if (in_res != R) {                                     // F.interpolate(x, R, mode="bicubic", align_corners=False) (test_refiner.py:80)
         float* dst = v.resz; const int planes = B * 3;
@@ -448,8 +422,8 @@ static int build_vae_encode(hd_ctx* c, int B, int in_res, int R, const float* im
 }
 
 static int build_vae_decode(hd_ctx* c, int B, int L, const float* latents, float* images_out) {
-    auto& prog = c->vae_dec_prog; prog.clear();
-    auto& v = c->vws; auto& w = c->vw;
+    auto& prog = c->ws->vae_dec_prog; prog.clear();
+    auto& v = c->ws->vws; auto& w = c->vw;
     int H = L;
     {
         uint4* in8 = v.in8; const float *pw = w.pq_w, *pb = w.pq_b; const int HW = H * H; const size_t npix = (size_t)B * HW;
@@ -507,11 +481,11 @@ int hd_cr_forward(hd_ctx* c, int batch, const float* ln_face, float* cr_face_out
     HIPCHECK(c, hipSetDevice(c->device));
     int rc = alloc_cr(c, batch);
     if (rc) return rc;
-    if (c->cr_program.empty() || c->cr_in != ln_face || c->cr_out != cr_face_out) {
+    if (c->ws->cr_program.empty() || c->ws->cr_in != ln_face || c->ws->cr_out != cr_face_out) {
         rc = build_cr_program(c, ln_face, cr_face_out);
         if (rc) return rc;
     }
-    return run_ops(c, c->cr_program, reinterpret_cast<hipStream_t>(stream), c->op_limit);
+    return run_ops(c, c->ws->cr_program, reinterpret_cast<hipStream_t>(stream), c->op_limit);
 }
 
 // AutoencoderKL boundary.  encode: images [B,3,in_res,in_res] fp32 NCHW -> bicubic to image_res (test_refiner.py:80)
@@ -535,13 +509,13 @@ int hd_vae_encode(hd_ctx* c, int batch, int in_res, int image_res, const float* 
     if (rc) return rc;
     const void* key[4] = {images, noise, moments_out, latents_out};
     const int flags = in_res * 4 + vae_range * 2;
-    if (c->vae_enc_prog.empty() || memcmp(key, c->vae_enc_key, sizeof(key)) != 0 || flags != c->vae_enc_flags || seed != c->vae_seed) {
+    if (c->ws->vae_enc_prog.empty() || memcmp(key, c->ws->vae_enc_key, sizeof(key)) != 0 || flags != c->ws->vae_enc_flags || seed != c->ws->vae_seed) {
         rc = build_vae_encode(c, batch, in_res, image_res, images, vae_range, noise, seed, moments_out, latents_out);
         if (rc) return rc;
-        memcpy(c->vae_enc_key, key, sizeof(key)); c->vae_enc_flags = flags;
+        memcpy(c->ws->vae_enc_key, key, sizeof(key)); c->ws->vae_enc_flags = flags;
     }
-    c->vae_seed = seed;
-    return run_ops(c, c->vae_enc_prog, reinterpret_cast<hipStream_t>(stream), c->op_limit);
+    c->ws->vae_seed = seed;
+    return run_ops(c, c->ws->vae_enc_prog, reinterpret_cast<hipStream_t>(stream), c->op_limit);
 }
 int hd_vae_decode(hd_ctx* c, int batch, int latent_res, const float* latents, float* images_out, void* stream) {
     if (!c) return HD_ERR_INVALID;
@@ -552,12 +526,12 @@ int hd_vae_decode(hd_ctx* c, int batch, int latent_res, const float* latents, fl
     int rc = alloc_vae(c, batch, latent_res * 8);
     if (rc) return rc;
     const void* key[2] = {latents, images_out};
-    if (c->vae_dec_prog.empty() || memcmp(key, c->vae_dec_key, sizeof(key)) != 0) {
+    if (c->ws->vae_dec_prog.empty() || memcmp(key, c->ws->vae_dec_key, sizeof(key)) != 0) {
         rc = build_vae_decode(c, batch, latent_res, latents, images_out);
         if (rc) return rc;
-        memcpy(c->vae_dec_key, key, sizeof(key));
+        memcpy(c->ws->vae_dec_key, key, sizeof(key));
     }
-    return run_ops(c, c->vae_dec_prog, reinterpret_cast<hipStream_t>(stream), c->op_limit);
+    return run_ops(c, c->ws->vae_dec_prog, reinterpret_cast<hipStream_t>(stream), c->op_limit);
 }
 
 }  // extern "C"

@@ -144,31 +144,46 @@ struct Chain {
 
 constexpr int kGraphSteps = 10;              // diffusion steps per captured graph in hd_sample (plus a one-step graph for the remainder)
 
-// Everything whose size depends on the batch: buffers, launch programs, captured graphs.  One context serves any batch
-// size (the reference's val loop has a ragged last batch: DataLoader without drop_last, test_refiner.py:160): the
-// workspace of the batch in use lives in hd_ctx itself, workspaces of other recent batch sizes are parked here
-// (packed weights are shared and never touched).
+// Everything whose lifetime is "this batch size": buffers, launch programs, captured graphs.  One context serves any batch
+// size (the reference's val loop has a ragged last batch: DataLoader without drop_last, test_refiner.py:160): hd_ctx::ws holds
+// the workspace of the batch in use, hd_ctx::ws_cache those of other recent batch sizes (packed weights are shared and never
+// touched).  A workspace is only ever moved by its pointer (switch_workspace), so every address inside it -- the Chain* a launch
+// closure holds -- stays valid while it is parked.
 struct VaeWs { float *X = nullptr, *T = nullptr, *S = nullptr, *mom = nullptr, *Q = nullptr, *K = nullptr, *V = nullptr, *resz = nullptr, *out3 = nullptr;
                unsigned short *H = nullptr, *H2 = nullptr, *Xb = nullptr, *U = nullptr; uint4* in8 = nullptr; double* part = nullptr; int B = 0, R = 0; };
 
-struct SavedWs {
-    VaeWs vws;
-    std::vector<Op> vae_enc_prog, vae_dec_prog;
-    int B = 0;
-    uint64_t stamp = 0;
+struct Workspace {
+    Workspace() = default;
+    Workspace(const Workspace&) = delete;
+    Workspace& operator=(const Workspace&) = delete;
+    int key = 0;                             // ws_cache key: B; the VAE: B + 8192 * (R / 8)
+    int B = 0;                               // the batch; 0: the empty workspace of a batch-less context
+    uint64_t stamp = 0;                      // hd_ctx::ws_clock when it was parked (the least recently used one is evicted)
     std::vector<Chain> chains;
-    float *lat = nullptr, *eps = nullptr, *x0_hist = nullptr;
-    Chain slot_stage; bool slot_stage_ok = false; int* slots_dev = nullptr;
-    std::vector<void*> allocs;
-    std::map<std::string, std::pair<void*, std::pair<size_t, int>>> dbg;
-    bool graphs_valid = false;
+    float *lat = nullptr, *eps = nullptr;    // [B,4,L,L] of the whole batch; chains own contiguous face ranges
+    float* x0_hist = nullptr;                // [B,4,L,L]: previous step's x0 of a multistep schedule (hd_sample_multistep)
+    // hd_prepare_slots: a private chain of capacity B (allocated on first use) on which the conditioning prologue runs at batch n,
+    // and the [B] device list of the slots it is scattered to
+    Chain slot_stage;
+    bool slot_stage_ok = false;
+    int* slots_dev = nullptr;
+    std::vector<void*> allocs;               // ws_alloc
+    std::map<std::string, std::pair<void*, std::pair<size_t, int>>> dbg;   // name -> (ptr, (elems, is_bf16)) of this workspace's buffers
+    // the plain step graphs (Chain::graph_exec / graph_multi) are current while these match hd_ctx::graphs_gen, film_table and B
+    unsigned graph_gen = 0;
     const float* graph_film = nullptr;
     int graph_B = 0;
-    // CoarseRestoration contexts
+    // CoarseRestoration: the launch program with the caller's pointers it captured
     std::vector<Op> cr_program;
     const float* cr_in = nullptr; float* cr_out = nullptr;
-    float* cr_skip[5] = {};
-    float *cr_loc1 = nullptr, *cr_loc2 = nullptr, *cr_theta = nullptr;
+    float* cr_skip[5] = {};                  // encoder-stage outputs kept for the decoder adds (levels 1..4)
+    float *cr_loc1 = nullptr, *cr_loc2 = nullptr, *cr_theta = nullptr;   // STN temporaries
+    // AutoencoderKL: the buffers, and each launch program with what validates it (the caller's pointers, flags and seed it captured)
+    VaeWs vws;
+    std::vector<Op> vae_enc_prog, vae_dec_prog;
+    const void *vae_enc_key[4] = {}, *vae_dec_key[2] = {};
+    int vae_enc_flags = -1;
+    uint64_t vae_seed = 0;
 };
 
 // Which evaluation a launch of Chain::program is part of.  Every closure of the program derives what it needs from this one value:
@@ -197,16 +212,11 @@ struct hd_ctx {
     std::vector<BlockW> cr_blocks;            // execution order
     PackedW cr_samp[9];                       // per stage: down (2x2 s2) or up (1x1 + PixelShuffle) conv
     float* cr_ln_pack = nullptr;
-    float* cr_skip[5] = {};                   // encoder-stage outputs kept for the decoder adds (levels 1..4)
-    float *cr_loc1 = nullptr, *cr_loc2 = nullptr, *cr_theta = nullptr;   // STN temporaries
-    std::vector<Op> cr_program;
-    const float* cr_in = nullptr; float* cr_out = nullptr;
     std::string err;
     std::unordered_map<std::string, RawTensor> raw;
-    std::vector<void*> allocs;
-    std::vector<void*> ws_allocs;             // allocations of the active batch workspace (dev_alloc while ws_scope)
-    bool ws_scope = false;
-    std::map<int, SavedWs> ws_cache;          // parked workspaces by batch size (at most kWsCached)
+    std::vector<void*> allocs;                // context lifetime (dev_alloc)
+    std::unique_ptr<Workspace> ws = std::make_unique<Workspace>();   // the active workspace; never null (batch-less: empty, B == 0)
+    std::map<int, std::unique_ptr<Workspace>> ws_cache;              // parked workspaces by Workspace::key (at most kWsCached)
     uint64_t ws_clock = 0;
     bool finalized = false;
 
@@ -225,18 +235,8 @@ struct hd_ctx {
     int64_t weight_bytes_per_step = 0;
     double flops_per_face_step = 0.0;
 
-    // batch-dependent workspace
-    int B = 0;
-    std::vector<Chain> chains;
-    Chain* ch = nullptr;                     // chain the builder functions currently work on
-    float *lat = nullptr, *eps = nullptr;    // [B,4,L,L] of the whole batch; chains own contiguous face ranges
-    float* x0_hist = nullptr;                // [B,4,L,L]: previous step's x0 of a multistep schedule (hd_sample_multistep)
-    bool prepared = false;
-    // hd_prepare_slots: a private chain of capacity B (allocated on first use, owned and parked with this workspace) on which the
-    // conditioning prologue runs at batch n, and the [B] device list of the slots it is scattered to
-    Chain slot_stage;
-    bool slot_stage_ok = false;
-    int* slots_dev = nullptr;
+    Chain* ch = nullptr;                     // chain the builder functions currently work on (ChainCursor; else chain 0 of the active workspace)
+    bool prepared = false;                   // cleared by every switch_workspace
 
     // FiLM / schedule
     float *t_dev = nullptr, *temb_a = nullptr, *temb_b = nullptr, *temb_c = nullptr, *film_table = nullptr;
@@ -254,7 +254,9 @@ struct hd_ctx {
     // uploaded with one copy.  Read through StepState and by the gather launch of the call: no graph holds a pointer into it.
     unsigned long long* faces_dev = nullptr;
     int faces_cap = 0;
-    unsigned rows_gen = 1;
+    // generations of the captured step graphs: invalidate_step_graphs bumps both; rows_gen (the per-face graphs, Chain::rows_gen) also
+    // moves when film_pf grows, graphs_gen (the plain graphs, Workspace::graph_gen) does not
+    unsigned rows_gen = 1, graphs_gen = 1;
     // the x0 history left by the last multistep call (hd_sample_rows_multistep resume = 1 continues it): valid for batch hist_B until
     // hd_prepare* or a single-step sampling call
     bool hist_valid = false;
@@ -303,11 +305,6 @@ struct hd_ctx {
         const float *enc_nw = nullptr, *enc_nb = nullptr, *dec_nw = nullptr, *dec_nb = nullptr;
         const float *quant_w = nullptr, *quant_b = nullptr, *pq_w = nullptr, *pq_b = nullptr, *ones = nullptr;
     } vw;
-    VaeWs vws;
-    std::vector<Op> vae_enc_prog, vae_dec_prog;
-    const void *vae_enc_key[4] = {}, *vae_dec_key[2] = {};
-    int vae_enc_flags = -1;
-    uint64_t vae_seed = 0;
 
     // XCD-local persistent stages (hd_xcd.hpp): latent 16, batch <= 64, one chain, one FiLM row for all faces
     struct XStage {
@@ -345,16 +342,13 @@ struct hd_ctx {
 
     // program
     int op_limit = -1, prep_limit = -1;
-    bool graphs_valid = false;
-    const float* graph_film = nullptr;
-    int graph_B = 0;
 
     // profiling
     bool profiling = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double last_loop_ms = 0.0;
     int last_steps = 0;
-    std::map<std::string, std::pair<void*, std::pair<size_t, int>>> dbg;   // name -> (ptr, (elems, is_bf16))
+    std::map<std::string, std::pair<void*, std::pair<size_t, int>>> dbg;   // context-lifetime names (film, temb); hd_debug_read looks in Workspace::dbg first
 };
 
 // The FiLM rows a denoiser LayerNorm of chain chp reads in the context's mode (the table above), and the one way a launch closure puts
@@ -381,20 +375,51 @@ template <class P> inline void set_film(P& p, const hd_ctx* c, const Chain* chp)
 namespace {
 
 template <class T>
-int dev_alloc(hd_ctx* c, T** out, size_t count) {
+int alloc_into(hd_ctx* c, std::vector<void*>& owner, T** out, size_t count) {
     void* p = nullptr;
     HIPCHECK(c, hipMalloc(&p, count * sizeof(T) + 256));
-    (c->ws_scope ? c->ws_allocs : c->allocs).push_back(p);
+    owner.push_back(p);
     *out = reinterpret_cast<T*>(p);
     return HD_OK;
 }
+// dev_alloc: freed with the context; ws_alloc: with the active workspace
+template <class T> int dev_alloc(hd_ctx* c, T** out, size_t count) { return alloc_into(c, c->allocs, out, count); }
+template <class T> int ws_alloc(hd_ctx* c, T** out, size_t count) { return alloc_into(c, c->ws->allocs, out, count); }
 void dev_free(hd_ctx* c, void* p) {
     if (!p) return;
     for (auto& a : c->allocs)
         if (a == p) { a = nullptr; break; }
-    for (auto& a : c->ws_allocs)
-        if (a == p) { a = nullptr; break; }
     (void)hipFree(p);
+}
+
+// Points hd_ctx::ch at the chain the builder functions are to work on; the previous one is back on every exit of the scope.
+struct ChainCursor {
+    hd_ctx* c; Chain* prev;
+    ChainCursor(hd_ctx* c_, Chain* ch) : c(c_), prev(c_->ch) { c->ch = ch; }
+    ~ChainCursor() { c->ch = prev; }
+    ChainCursor(const ChainCursor&) = delete;
+    ChainCursor& operator=(const ChainCursor&) = delete;
+};
+
+// The buffers of one level (C, H, M set by the caller) in the active workspace.  xg: elements of the pre-gated HCA conv input.
+// names: register them for hd_debug_read as <name><l>.
+int alloc_level(hd_ctx* c, Level& v, int B, size_t xg, bool names, int l) {
+    const size_t mc = (size_t)v.M * v.C;
+    int rc = 0;
+    rc |= ws_alloc(c, &v.X, mc); rc |= ws_alloc(c, &v.Y, mc); rc |= ws_alloc(c, &v.T1, 2 * mc + (size_t)B * ((v.H + 7) / 8) * v.C);   // + per-band pool sums of the unfused depthwise path
+    rc |= ws_alloc(c, &v.G, mc); rc |= ws_alloc(c, &v.pooled, (size_t)B * v.C); rc |= ws_alloc(c, &v.S, (size_t)B * v.C);
+    rc |= ws_alloc(c, &v.sx, (size_t)v.M * (v.C / 32)); rc |= ws_alloc(c, &v.sy, (size_t)v.M * (v.C / 32));
+    rc |= ws_alloc(c, &v.Xb, mc); rc |= ws_alloc(c, &v.Yb, mc); rc |= ws_alloc(c, &v.Xg, xg);
+    rc |= ws_alloc(c, &v.pooled16, (size_t)B * v.C);
+    if (rc || !names) return rc;
+    auto& dbg = c->ws->dbg;
+    const std::string s = std::to_string(l);
+    dbg["X" + s] = {v.X, {mc, 0}}; dbg["Y" + s] = {v.Y, {mc, 0}}; dbg["T1_" + s] = {v.T1, {2 * mc, 0}};
+    dbg["G" + s] = {v.G, {mc, 1}}; dbg["pooled" + s] = {v.pooled, {(size_t)B * v.C, 0}}; dbg["S" + s] = {v.S, {(size_t)B * v.C, 0}};
+    dbg["Xb" + s] = {v.Xb, {mc, 1}}; dbg["Yb" + s] = {v.Yb, {mc, 1}};
+    dbg["pooled16_" + s] = {v.pooled16, {(size_t)B * v.C, 1}};
+    dbg["sx" + s] = {v.sx, {(size_t)v.M * (v.C / 32) * 2, 0}}; dbg["sy" + s] = {v.sy, {(size_t)v.M * (v.C / 32) * 2, 0}};
+    return HD_OK;
 }
 
 constexpr size_t kWsCached = 3;
@@ -403,74 +428,51 @@ void destroy_chain_queue(Chain& ch) {
     if (ch.done) (void)hipEventDestroy(ch.done);
     ch.stream = nullptr; ch.done = nullptr;
 }
-void destroy_saved(SavedWs& w) {
+// Graphs, queues and device memory of a workspace (its launches must have finished).
+void destroy(Workspace& w) {
     if (w.slot_stage_ok) destroy_chain_queue(w.slot_stage);
     for (auto& ch : w.chains) {
-        if (ch.graph_exec) (void)hipGraphExecDestroy(ch.graph_exec);
-        if (ch.graph_multi) (void)hipGraphExecDestroy(ch.graph_multi);
-        if (ch.graph_rows_exec) (void)hipGraphExecDestroy(ch.graph_rows_exec);
-        if (ch.graph_rows_multi) (void)hipGraphExecDestroy(ch.graph_rows_multi);
-        if (ch.stream) (void)hipStreamDestroy(ch.stream);
-        if (ch.done) (void)hipEventDestroy(ch.done);
+        for (hipGraphExec_t g : {ch.graph_exec, ch.graph_multi, ch.graph_rows_exec, ch.graph_rows_multi}) if (g) (void)hipGraphExecDestroy(g);
+        destroy_chain_queue(ch);
     }
     for (void* p : w.allocs) if (p) (void)hipFree(p);
     w.chains.clear(); w.allocs.clear();
 }
-// Park the active workspace under its batch size and make the context batch-less (B = 0).
-void park_workspace(hd_ctx* c) {
-    if (c->B == 0) return;
-    SavedWs w;
-    w.B = c->B; w.stamp = ++c->ws_clock;
-    w.chains = std::move(c->chains); w.lat = c->lat; w.eps = c->eps; w.x0_hist = c->x0_hist;
-    w.slot_stage = c->slot_stage; w.slot_stage_ok = c->slot_stage_ok; w.slots_dev = c->slots_dev;
-    c->slot_stage = Chain(); c->slot_stage_ok = false; c->slots_dev = nullptr;
-    w.allocs = std::move(c->ws_allocs);
-    w.dbg = c->dbg;
-    w.graphs_valid = c->graphs_valid; w.graph_film = c->graph_film; w.graph_B = c->graph_B;
-    w.cr_program = std::move(c->cr_program); w.cr_in = c->cr_in; w.cr_out = c->cr_out;
-    w.vws = c->vws; c->vws = VaeWs();
-    w.vae_enc_prog = std::move(c->vae_enc_prog); w.vae_dec_prog = std::move(c->vae_dec_prog);
-    c->vae_enc_prog.clear(); c->vae_dec_prog.clear();
-    for (auto& k : c->vae_enc_key) k = nullptr;
-    for (auto& k : c->vae_dec_key) k = nullptr;
-    for (int i = 0; i < 5; ++i) { w.cr_skip[i] = c->cr_skip[i]; c->cr_skip[i] = nullptr; }
-    w.cr_loc1 = c->cr_loc1; w.cr_loc2 = c->cr_loc2; w.cr_theta = c->cr_theta;
-    c->cr_loc1 = c->cr_loc2 = c->cr_theta = nullptr; c->cr_in = nullptr; c->cr_out = nullptr;
-    c->chains.clear(); c->ws_allocs.clear(); c->cr_program.clear();
-    c->lat = c->eps = c->x0_hist = nullptr; c->ch = nullptr;
-    for (auto it = c->dbg.begin(); it != c->dbg.end();) it = (it->first == "film" || it->first == "temb") ? std::next(it) : c->dbg.erase(it);
-    c->graphs_valid = false; c->prepared = false;
-    const int B = c->B;
-    c->B = 0;
-    c->ws_cache[B] = std::move(w);
-    while (c->ws_cache.size() > kWsCached) {                // evict the least recently used (its launches may still be in flight)
-        auto old = c->ws_cache.begin();
-        for (auto it = c->ws_cache.begin(); it != c->ws_cache.end(); ++it) if (it->second.stamp < old->second.stamp) old = it;
-        (void)hipDeviceSynchronize();
-        destroy_saved(old->second);
-        c->ws_cache.erase(old);
+// Make the workspace of `key` the active one: the one in use already, a parked one, or a new one that make(Workspace&) fills (it is
+// hd_ctx::ws while make runs, so ws_alloc and the debug names reach it).  The active one is parked first, and the least recently used
+// beyond kWsCached destroyed.  The conditioning a parked workspace holds belongs to an older batch, so the context is "not prepared"
+// after every switch.  If make fails, what it allocated is freed and the context is batch-less.
+template <class Make>
+int switch_workspace(hd_ctx* c, int key, Make make) {
+    if (key == c->ws->key) return HD_OK;
+    c->prepared = false; c->ch = nullptr;
+    if (c->ws->B != 0) {
+        c->ws->stamp = ++c->ws_clock;
+        const int old_key = c->ws->key;
+        c->ws_cache[old_key] = std::move(c->ws);
+        while (c->ws_cache.size() > kWsCached) {                // evict the least recently used (its launches may still be in flight)
+            auto old = c->ws_cache.begin();
+            for (auto it = c->ws_cache.begin(); it != c->ws_cache.end(); ++it) if (it->second->stamp < old->second->stamp) old = it;
+            (void)hipDeviceSynchronize();
+            destroy(*old->second);
+            c->ws_cache.erase(old);
+        }
     }
+    auto it = c->ws_cache.find(key);
+    if (it != c->ws_cache.end()) {
+        c->ws = std::move(it->second);
+        c->ws_cache.erase(it);
+    } else {
+        c->ws = std::make_unique<Workspace>();
+        c->ws->key = key;
+        if (const int rc = make(*c->ws)) { destroy(*c->ws); c->ws = std::make_unique<Workspace>(); return rc; }
+    }
+    c->ch = c->ws->chains.empty() ? nullptr : &c->ws->chains[0];
+    return HD_OK;
 }
-// Make the parked workspace of batch B active again; false if there is none.  The conditioning it holds belongs to an
-// older batch, so the context is "not prepared" afterwards.
-bool unpark_workspace(hd_ctx* c, int B) {
-    auto it = c->ws_cache.find(B);
-    if (it == c->ws_cache.end()) return false;
-    SavedWs& w = it->second;
-    c->chains = std::move(w.chains); c->lat = w.lat; c->eps = w.eps; c->x0_hist = w.x0_hist;
-    c->slot_stage = w.slot_stage; c->slot_stage_ok = w.slot_stage_ok; c->slots_dev = w.slots_dev;
-    c->ws_allocs = std::move(w.allocs);
-    for (auto& kv : w.dbg) if (kv.first != "film" && kv.first != "temb") c->dbg[kv.first] = kv.second;
-    c->graphs_valid = w.graphs_valid; c->graph_film = w.graph_film; c->graph_B = w.graph_B;
-    c->cr_program = std::move(w.cr_program); c->cr_in = w.cr_in; c->cr_out = w.cr_out;
-    c->vws = w.vws;                                       // the VAE launch programs are rebuilt (they capture the caller's pointers)
-    for (int i = 0; i < 5; ++i) c->cr_skip[i] = w.cr_skip[i];
-    c->cr_loc1 = w.cr_loc1; c->cr_loc2 = w.cr_loc2; c->cr_theta = w.cr_theta;
-    c->B = B; c->ch = c->chains.empty() ? nullptr : &c->chains[0];
-    c->prepared = false;
-    c->ws_cache.erase(it);
-    return true;
-}
+// Every captured step graph of the context is stale (a switch, a moved buffer or a reset stage they captured): the active workspace and
+// the parked ones recapture on their next use.
+void invalidate_step_graphs(hd_ctx* c) { ++c->graphs_gen; ++c->rows_gen; }
 
 const RawTensor* find_raw(hd_ctx* c, const std::string& n) {
     auto it = c->raw.find(n);

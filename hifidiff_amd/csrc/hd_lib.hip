@@ -10,44 +10,36 @@ namespace {
 // --------------------------------------------------------------------------------------- workspace
 int alloc_chain(hd_ctx* c, Chain& ch) {
     const int L = c->L, B = ch.B;
-    const bool dbg = (ch.index == 0);                    // introspection reads chain 0
+    const bool names = (ch.index == 0);                  // introspection reads chain 0
+    auto& dbg = c->ws->dbg;
     int rc = 0;
     for (int l = 0; l < 5; ++l) {
         Level& v = ch.lv[l];
         v.C = WIDTH << l; v.H = L >> l; v.M = B * v.H * v.H;
         const size_t mc = (size_t)v.M * v.C;
-        rc |= dev_alloc(c, &v.X, mc); rc |= dev_alloc(c, &v.Y, mc); rc |= dev_alloc(c, &v.T1, 2 * mc + (size_t)B * ((v.H + 7) / 8) * v.C);   // + per-band pool sums of the unfused depthwise path
-        rc |= dev_alloc(c, &v.G, mc); rc |= dev_alloc(c, &v.pooled, (size_t)B * v.C); rc |= dev_alloc(c, &v.S, (size_t)B * v.C);
-        rc |= dev_alloc(c, &v.sx, (size_t)v.M * (v.C / 32)); rc |= dev_alloc(c, &v.sy, (size_t)v.M * (v.C / 32));
-        rc |= dev_alloc(c, &v.Xb, mc); rc |= dev_alloc(c, &v.Yb, mc); rc |= dev_alloc(c, &v.Xg, mc);
-        rc |= dev_alloc(c, &v.pooled16, (size_t)B * v.C);
+        rc |= alloc_level(c, v, B, mc, names, l);
         const int pi = 4 - l;                            // prior index: coarsest first
-        rc |= dev_alloc(c, &ch.prior[pi], mc); rc |= dev_alloc(c, &ch.gate_c[pi], (size_t)B * v.C);
-        rc |= dev_alloc(c, &ch.gate_s[pi], (size_t)v.M);
+        rc |= ws_alloc(c, &ch.prior[pi], mc); rc |= ws_alloc(c, &ch.gate_c[pi], (size_t)B * v.C);
+        rc |= ws_alloc(c, &ch.gate_s[pi], (size_t)v.M);
         if (rc) return rc;
-        if (dbg) {
-            const std::string s = std::to_string(l);
-            c->dbg["X" + s] = {v.X, {mc, 0}}; c->dbg["Y" + s] = {v.Y, {mc, 0}}; c->dbg["T1_" + s] = {v.T1, {2 * mc, 0}};
-            c->dbg["G" + s] = {v.G, {mc, 1}}; c->dbg["pooled" + s] = {v.pooled, {(size_t)B * v.C, 0}}; c->dbg["S" + s] = {v.S, {(size_t)B * v.C, 0}};
-            c->dbg["Xb" + s] = {v.Xb, {mc, 1}}; c->dbg["Yb" + s] = {v.Yb, {mc, 1}}; c->dbg["Xg" + s] = {v.Xg, {mc, 1}};
-            c->dbg["pooled16_" + s] = {v.pooled16, {(size_t)B * v.C, 1}};
-            c->dbg["sx" + s] = {v.sx, {(size_t)v.M * (v.C / 32) * 2, 0}}; c->dbg["sy" + s] = {v.sy, {(size_t)v.M * (v.C / 32) * 2, 0}};
+        if (names) {
             const std::string ps = std::to_string(pi);
-            c->dbg["prior" + ps] = {ch.prior[pi], {mc, 0}}; c->dbg["wc" + ps] = {ch.gate_c[pi], {(size_t)B * v.C, 0}};
-            c->dbg["ws" + ps] = {ch.gate_s[pi], {(size_t)v.M, 0}};
+            dbg["Xg" + std::to_string(l)] = {v.Xg, {mc, 1}};
+            dbg["prior" + ps] = {ch.prior[pi], {mc, 0}}; dbg["wc" + ps] = {ch.gate_c[pi], {(size_t)B * v.C, 0}};
+            dbg["ws" + ps] = {ch.gate_s[pi], {(size_t)v.M, 0}};
         }
     }
-    rc |= dev_alloc(c, &ch.idc_term, (size_t)B * 2048 * c->S * c->S); rc |= dev_alloc(c, &ch.id_emb, (size_t)B * 2048);
-    rc |= dev_alloc(c, &ch.pool_tmp, (size_t)B * 2048); rc |= dev_alloc(c, &ch.mlp_tmp, (size_t)B * 2048);
-    rc |= dev_alloc(c, &ch.sp_tmp, (size_t)ch.lv[0].M * 1024);       // >= max over levels of M_l * C_l / 2
+    rc |= ws_alloc(c, &ch.idc_term, (size_t)B * 2048 * c->S * c->S); rc |= ws_alloc(c, &ch.id_emb, (size_t)B * 2048);
+    rc |= ws_alloc(c, &ch.pool_tmp, (size_t)B * 2048); rc |= ws_alloc(c, &ch.mlp_tmp, (size_t)B * 2048);
+    rc |= ws_alloc(c, &ch.sp_tmp, (size_t)ch.lv[0].M * 1024);       // >= max over levels of M_l * C_l / 2
     if (rc) return rc;
-    if (dbg) { c->dbg["idc"] = {ch.idc_term, {(size_t)B * 2048 * c->S * c->S, 0}}; c->dbg["id_emb"] = {ch.id_emb, {(size_t)B * 2048, 0}}; }
+    if (names) { dbg["idc"] = {ch.idc_term, {(size_t)B * 2048 * c->S * c->S, 0}}; dbg["id_emb"] = {ch.id_emb, {(size_t)B * 2048, 0}}; }
     // ResNet activations (channels-last bf16); largest is conv1 output B x 64x64 x 64 == layer1 B x 32x32 x 256
     const size_t rmax = (size_t)B * 64 * 64 * 64;
-    for (int i = 0; i < 4; ++i) rc |= dev_alloc(c, &ch.res_buf[i], rmax);
-    rc |= dev_alloc(c, &ch.face8, (size_t)B * 128 * 128);
-    rc |= dev_alloc(c, &ch.step_state, 1);
-    rc |= dev_alloc(c, &ch.film_cur, (size_t)c->film_total);
+    for (int i = 0; i < 4; ++i) rc |= ws_alloc(c, &ch.res_buf[i], rmax);
+    rc |= ws_alloc(c, &ch.face8, (size_t)B * 128 * 128);
+    rc |= ws_alloc(c, &ch.step_state, 1);
+    rc |= ws_alloc(c, &ch.film_cur, (size_t)c->film_total);
     if (rc) return rc;
     HIPCHECK(c, hipMemset(ch.step_state, 0, sizeof(StepState)));
     HIPCHECK(c, hipStreamCreateWithFlags(&ch.stream, hipStreamNonBlocking));
@@ -66,18 +58,7 @@ int setup_xcd(hd_ctx* c);
 
 // Cut the batch into chains (HD_CHAINS, default 1).  Two streams of these kernels do overlap (1.6x in
 // tools/gemm_bench), but halving M does not make a kernel cheaper, so splitting the batch is not a win.
-int alloc_workspace_new(hd_ctx* c, int B);
-int alloc_workspace(hd_ctx* c, int B) {
-    if (B == c->B) return HD_OK;
-    park_workspace(c);                                     // another batch size: keep its buffers, programs and graphs for later
-    if (unpark_workspace(c, B)) return HD_OK;
-    c->ws_scope = true;
-    const int rc = alloc_workspace_new(c, B);
-    c->ws_scope = false;
-    if (rc) { c->B = B; park_workspace(c); auto it = c->ws_cache.find(B); if (it != c->ws_cache.end()) { destroy_saved(it->second); c->ws_cache.erase(it); } }
-    return rc;
-}
-int alloc_workspace_new(hd_ctx* c, int B) {
+int alloc_workspace_new(hd_ctx* c, Workspace& w, int B) {
     int n = 1;                                            // measured: per-kernel cost barely depends on M, so more chains only add launches
     if (const char* e = hd_env("HD_CHAINS")) n = atoi(e);         // experiment switch (needs HD_EXPERIMENTS=1): measured slower at 2 and 4
     if (n < 1) n = 1;
@@ -85,28 +66,31 @@ int alloc_workspace_new(hd_ctx* c, int B) {
     while (n > 1 && B % n != 0) --n;
     const size_t per_face = (size_t)4 * c->L * c->L;
     int rc = 0;
-    rc |= dev_alloc(c, &c->lat, (size_t)B * per_face); rc |= dev_alloc(c, &c->eps, (size_t)B * per_face);
-    rc |= dev_alloc(c, &c->x0_hist, (size_t)B * per_face);
+    rc |= ws_alloc(c, &w.lat, (size_t)B * per_face); rc |= ws_alloc(c, &w.eps, (size_t)B * per_face);
+    rc |= ws_alloc(c, &w.x0_hist, (size_t)B * per_face);
     if (rc) return rc;
-    c->dbg["lat"] = {c->lat, {(size_t)B * per_face, 0}}; c->dbg["eps"] = {c->eps, {(size_t)B * per_face, 0}};
-    c->dbg["x0_hist"] = {c->x0_hist, {(size_t)B * per_face, 0}};
-    c->chains.resize(n);
+    w.dbg["lat"] = {w.lat, {(size_t)B * per_face, 0}}; w.dbg["eps"] = {w.eps, {(size_t)B * per_face, 0}};
+    w.dbg["x0_hist"] = {w.x0_hist, {(size_t)B * per_face, 0}};
+    w.chains.resize(n);
     for (int i = 0; i < n; ++i) {
-        Chain& ch = c->chains[i];
+        Chain& ch = w.chains[i];
         ch.index = i; ch.B = B / n; ch.face0 = i * (B / n);
-        ch.lat = c->lat + (size_t)ch.face0 * per_face; ch.eps = c->eps + (size_t)ch.face0 * per_face;
-        ch.x0_hist = c->x0_hist + (size_t)ch.face0 * per_face;
+        ch.lat = w.lat + (size_t)ch.face0 * per_face; ch.eps = w.eps + (size_t)ch.face0 * per_face;
+        ch.x0_hist = w.x0_hist + (size_t)ch.face0 * per_face;
         rc = alloc_chain(c, ch);
         if (rc) return rc;
     }
-    c->B = B;
-    for (auto& ch : c->chains) {
-        c->ch = &ch;
+    w.B = B;
+    for (auto& ch : w.chains) {
+        ChainCursor on(c, &ch);
         rc = build_denoiser_program(c);
         if (rc) return rc;
     }
-    c->ch = &c->chains[0];
     return HD_OK;
+}
+// another batch size: the buffers, programs and graphs of the one in use are kept for later
+int alloc_workspace(hd_ctx* c, int B) {
+    return switch_workspace(c, B, [&](Workspace& w) { return alloc_workspace_new(c, w, B); });
 }
 
 // ----------------------------------------------------------------------------- program construction
@@ -173,7 +157,7 @@ int build_denoiser_program(hd_ctx* c) {
         Op op;
         op.name = c->den_blocks[first + nblk - 1].name + ".conv5"; op.out = lv.X; op.out_elems = (size_t)lv.M * lv.C; op.out_bf16 = 0;
         op.run = [c, chp, sp, sp2, have2, sub, l3, first](hipStream_t s) -> hipError_t {
-            if (have2 && c->xcd_ok && c->xcd_on && c->xcd2_on && c->chains.size() == 1 && mode_shared_row(c->mode)) {
+            if (have2 && c->xcd_ok && c->xcd_on && c->xcd2_on && c->ws->chains.size() == 1 && mode_shared_row(c->mode)) {
                 X2StageP r = sp2;
                 r.film = film_rows(c, chp).base;
                 r.phase_limit = (c->stage_limit_first < 0 || c->stage_limit_first == first) ? c->xcd_phase_limit : 0;
@@ -184,7 +168,7 @@ int build_denoiser_program(hd_ctx* c) {
                 c->xcd2_on = false;
             }
             // (per-face rows of hd_sample_rows*: the K-split form's per-face instantiation; the autonomous-wave form above has none)
-            if (c->xcd_ok && c->xcd_on && c->chains.size() == 1 && mode_allows_stages(c->mode)) {
+            if (c->xcd_ok && c->xcd_on && c->ws->chains.size() == 1 && mode_allows_stages(c->mode)) {
                 XStageP r = sp;
                 set_film(r, c, chp);
                 r.phase_limit = (c->stage_limit_first < 0 || c->stage_limit_first == first) ? c->xcd_phase_limit : 0;
@@ -214,11 +198,8 @@ int build_denoiser_program(hd_ctx* c) {
         if (stage_rc) return;
         hd_ctx::FStage& fs = c->fstages[first];
         if (!fs.sync) {
-            const bool ws = c->ws_scope;
-            c->ws_scope = false;
             int rc = dev_alloc(c, &fs.sync, (size_t)2 * 64 * 16);
             rc |= dev_alloc(c, &fs.pool_part, (size_t)64 * 8 * 256);
-            c->ws_scope = ws;
             if (rc || hipMemset(fs.sync, 0, (size_t)2 * 64 * 16 * sizeof(unsigned)) != hipSuccess) { stage_rc = HD_ERR_HIP; return; }
         }
         FStageP fp{};
@@ -238,7 +219,7 @@ int build_denoiser_program(hd_ctx* c) {
         op.run = [c, chp, fp, sub, c128, first, intro_first](hipStream_t s) -> hipError_t {
             // (hd_eps's per-face timesteps and split batches run the per-GEMM form: every workgroup resident is what the stage needs; the
             // per-face rows of hd_sample_rows* have an instantiation of their own)
-            if (c->xcd_ok && c->face_on && c->chains.size() == 1 && mode_allows_stages(c->mode)) {
+            if (c->xcd_ok && c->face_on && c->ws->chains.size() == 1 && mode_allows_stages(c->mode)) {
                 FStageP r = fp;
                 set_film(r, c, chp);
                 r.block_limit = (c->stage_limit_first < 0 || c->stage_limit_first == first) ? c->face_block_limit : 0;
@@ -322,7 +303,7 @@ int build_denoiser_program(hd_ctx* c) {
             if (!mode_is_loop(c->mode)) return sa;
             const size_t per_face = (size_t)4 * L * L;
             sa.lat = chp->lat; sa.coef = c->coef_dev; sa.st = chp->step_state;
-            sa.elem0 = (int)(chp->face0 * per_face); sa.n_total = (int)(c->B * per_face);
+            sa.elem0 = (int)(chp->face0 * per_face); sa.n_total = (int)(c->ws->B * per_face);
             sa.film_table = c->film_table; sa.film_total = c->film_total;
             sa.film_cur = mode_is_rows(c->mode) ? c->film_pf + (size_t)chp->face0 * c->film_total : chp->film_cur;
             return sa;
@@ -557,28 +538,24 @@ int get_xstage(hd_ctx* c, int first_block, int nblocks, hd_ctx::XStage** out) {
         x.b1 = bw.conv1.bias; x.bsca = bw.sca.bias; x.b3 = bw.conv3.bias; x.b4 = bw.conv4.bias; x.b5 = bw.conv5.bias;
         x.beta = bw.beta; x.gamma = bw.gamma; x.dw_w = bw.dw_wT; x.dw_b = bw.dw_b; x.film_off = bw.film_off; x.pad_ = 0;
     }
-    const bool ws = c->ws_scope;
-    c->ws_scope = false;                                  // context-lifetime allocations
     int rc = dev_alloc(c, &st.blocks_dev, (size_t)nblocks);
     rc |= dev_alloc(c, &st.sync, (size_t)3 * 256);
-    c->ws_scope = ws;
     if (rc) return rc;
     HIPCHECK(c, hipMemcpy(st.blocks_dev, host.data(), host.size() * sizeof(XBlockW), hipMemcpyHostToDevice));
     HIPCHECK(c, hipMemset(st.sync, 0, (size_t)3 * 256 * sizeof(unsigned)));
     const int C = c->den_blocks[first_block].C, HW = (C == 1024) ? 4 : 16;
     if (c->xcd2_mask & (C == 1024 ? 2 : 1)) {
         // the five 1x1 convs of every block once more, in the A-operand order of the 16x16x32 MFMA (hd_xcd2.hpp)
-        c->ws_scope = false;
         for (int j = 0; j < nblocks; ++j) {
             const BlockW& bw = c->den_blocks[first_block + j];
             const char* conv[5] = {".conv1", ".sca.1", ".conv3", ".conv4", ".conv5"};
             const uint4** dst[5] = {&host[j].w1, &host[j].wsca, &host[j].w3, &host[j].w4, &host[j].w5};
             for (int k = 0; k < 5; ++k) {
                 const RawTensor* w = find_raw(c, bw.name + conv[k] + ".weight");
-                if (!w || (int)w->shape[1] != C) { c->ws_scope = ws; HD_FAIL(c, HD_ERR_WEIGHTS, "missing %s%s.weight", bw.name.c_str(), conv[k]); }
+                if (!w || (int)w->shape[1] != C) HD_FAIL(c, HD_ERR_WEIGHTS, "missing %s%s.weight", bw.name.c_str(), conv[k]);
                 const int N = (int)w->shape[0];
                 uint4* d = nullptr;
-                if (int r2 = dev_alloc(c, &d, (size_t)N * C / 8)) { c->ws_scope = ws; return r2; }
+                if (int r2 = dev_alloc(c, &d, (size_t)N * C / 8)) return r2;
                 hipLaunchKernelGGL(pack_weight16_kernel, dim3(1024), dim3(256), 0, 0, w->dev, d, N, C);
                 *dst[k] = d;
             }
@@ -588,7 +565,6 @@ int get_xstage(hd_ctx* c, int first_block, int nblocks, hd_ctx::XStage** out) {
         const size_t hn = (size_t)64 * HW * C / 8;
         r2 |= dev_alloc(c, &st.hX, hn); r2 |= dev_alloc(c, &st.hG, hn); r2 |= dev_alloc(c, &st.hY, hn);
         r2 |= dev_alloc(c, &st.hsx, (size_t)64 * HW * (C / 16)); r2 |= dev_alloc(c, &st.hsy, (size_t)64 * HW * (C / 16));
-        c->ws_scope = ws;
         if (r2) return r2;
         HIPCHECK(c, hipGetLastError());
         HIPCHECK(c, hipMemcpy(st.blocks2_dev, host.data(), host.size() * sizeof(XBlockW), hipMemcpyHostToDevice));
@@ -610,9 +586,8 @@ static int check_xcd(hd_ctx* c) {
         (void)hipDeviceSynchronize();                      // the failed call's remaining launches still read the words reset below
         c->xcd_tmo_host[0] = 0;
         if (c->abort_dev) (void)hipMemset(c->abort_dev, 0, 64 * sizeof(unsigned));
-        c->xcd_on = false; c->graphs_valid = false;
-        for (auto& kv : c->ws_cache) kv.second.graphs_valid = false;
-        ++c->rows_gen;
+        c->xcd_on = false;
+        invalidate_step_graphs(c);
         for (auto& kv : c->xstages) {
             (void)hipMemset(kv.second.sync, 0, (size_t)3 * 256 * sizeof(unsigned));
             if (kv.second.sync2) (void)hipMemset(kv.second.sync2, 0, (size_t)2048 * sizeof(unsigned));
@@ -677,25 +652,16 @@ void hd_destroy(hd_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    for (auto& ch : c->chains) {
-        if (ch.graph_exec) (void)hipGraphExecDestroy(ch.graph_exec);
-        if (ch.graph_multi) (void)hipGraphExecDestroy(ch.graph_multi);
-        if (ch.graph_rows_exec) (void)hipGraphExecDestroy(ch.graph_rows_exec);
-        if (ch.graph_rows_multi) (void)hipGraphExecDestroy(ch.graph_rows_multi);
-        if (ch.stream) (void)hipStreamDestroy(ch.stream);
-        if (ch.done) (void)hipEventDestroy(ch.done);
-    }
-    if (c->slot_stage_ok) destroy_chain_queue(c->slot_stage);
+    destroy(*c->ws);
+    for (auto& kv : c->ws_cache) destroy(*kv.second);
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
     if (c->film_ev) (void)hipEventDestroy(c->film_ev);
     for (auto& sg : c->stage) { if (sg.ev) (void)hipEventDestroy(sg.ev); if (sg.host) (void)hipHostFree(sg.host); }
     if (c->xcd_tmo_host) (void)hipHostFree(c->xcd_tmo_host);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
-    for (auto& kv : c->ws_cache) destroy_saved(kv.second);
     for (auto& kv : c->raw) if (kv.second.dev) (void)hipFree(kv.second.dev);
     for (void* p : c->allocs) if (p) (void)hipFree(p);
-    for (void* p : c->ws_allocs) if (p) (void)hipFree(p);
     delete c;
 }
 
@@ -935,28 +901,38 @@ static void free_previews(hd_ctx* c) {
 // every face: no estimate (rows -1, zeroed planes); the planes are (re)allocated when the batch or the snapshot count has changed
 static int reset_previews(hd_ctx* c, hipStream_t s) {
     if (!c->pv_on) return HD_OK;
-    const size_t B = (size_t)c->B, per_face = (size_t)4 * c->L * c->L, planes = (size_t)c->pv_snaps;
-    if (c->pv_B != c->B || c->pv_planes != c->pv_snaps) {
+    const size_t B = (size_t)c->ws->B, per_face = (size_t)4 * c->L * c->L, planes = (size_t)c->pv_snaps;
+    if (c->pv_B != c->ws->B || c->pv_planes != c->pv_snaps) {
         free_previews(c);
         int rc = dev_alloc(c, &c->pv_x0_dev, B * per_face);
         if (!rc) rc = dev_alloc(c, &c->pv_snap_dev, (planes ? planes : 1) * B * per_face);
         if (!rc) rc = dev_alloc(c, &c->pv_row_dev, (1 + planes) * B);
         if (!rc) rc = dev_alloc(c, &c->pv_slots_dev, B);
         if (rc) { free_previews(c); return rc; }
-        c->pv_B = c->B; c->pv_planes = c->pv_snaps;
+        c->pv_B = c->ws->B; c->pv_planes = c->pv_snaps;
     }
     HIPCHECK(c, hipMemsetAsync(c->pv_x0_dev, 0, B * per_face * sizeof(float), s));
     if (planes) HIPCHECK(c, hipMemsetAsync(c->pv_snap_dev, 0, planes * B * per_face * sizeof(float), s));
     HIPCHECK(c, hipMemsetAsync(c->pv_row_dev, 0xff, (1 + planes) * B * sizeof(int), s));      // -1
     return HD_OK;
 }
-static bool previews_ready(const hd_ctx* c) { return c->pv_on && c->pv_x0_dev && c->pv_B == c->B && c->pv_planes == c->pv_snaps; }
+static bool previews_ready(const hd_ctx* c) { return c->pv_on && c->pv_x0_dev && c->pv_B == c->ws->B && c->pv_planes == c->pv_snaps; }
 
 // every hd_prepare*: the new batch has no masks and no previews
 static int clear_masks(hd_ctx* c, hipStream_t s) {
     if (masked_faces(c) > 0) HIPCHECK(c, hipMemsetAsync(c->mask_on_dev, 0, (size_t)c->mask_cap * sizeof(int), s));
     c->mask_face.clear();
     return reset_previews(c, s);
+}
+
+// the common end of every hd_prepare*
+static int finish_prepare(hd_ctx* c, hipStream_t s) {
+    const int rc = clear_masks(c, s);
+    if (rc) return rc;
+    c->prepared = true;
+    c->hist_valid = false;                               // a new batch: no multistep history to resume
+    c->hist_face.clear();
+    return HD_OK;
 }
 
 #define HD_NEED_CONDITIONAL(c, what) \
@@ -968,12 +944,7 @@ int hd_prepare_unconditional(hd_ctx* c, int batch, void* stream) {
     if (c && c->conditional) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_unconditional: this context holds the conditional FusedDenoiser");
     int rc = prepare_common(c, batch);
     if (rc) return rc;
-    rc = clear_masks(c, reinterpret_cast<hipStream_t>(stream));
-    if (rc) return rc;
-    c->prepared = true;
-    c->hist_valid = false;                               // a new batch: no multistep history to resume
-    c->hist_face.clear();
-    return HD_OK;
+    return finish_prepare(c, reinterpret_cast<hipStream_t>(stream));
 }
 
 int hd_prepare(hd_ctx* c, int batch, const float* cr_latent, const float* cr_face, const float* id_emb, void* stream) {
@@ -983,8 +954,8 @@ int hd_prepare(hd_ctx* c, int batch, const float* cr_latent, const float* cr_fac
     if (!cr_latent || (!cr_face == !id_emb)) HD_FAIL(c, HD_ERR_INVALID, "need cr_latent and exactly one of cr_face / id_emb");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const size_t lat_face = (size_t)4 * c->L * c->L;
-    for (auto& ch : c->chains) {
-        c->ch = &ch;
+    for (auto& ch : c->ws->chains) {
+        ChainCursor on(c, &ch);
         std::vector<Op> prog;
         add_fpg(c, prog, cr_latent + ch.face0 * lat_face);
         if (cr_face) add_resnet(c, prog, cr_face + (size_t)ch.face0 * 3 * 128 * 128);
@@ -993,16 +964,9 @@ int hd_prepare(hd_ctx* c, int batch, const float* cr_latent, const float* cr_fac
         add_idc_term(c, prog);
         rc = run_ops(c, prog, s, ch.index == 0 ? c->prep_limit : -1);
         ch.prep_program.swap(prog);
-        if (rc) break;
+        if (rc) return rc;
     }
-    c->ch = &c->chains[0];
-    if (rc) return rc;
-    rc = clear_masks(c, s);
-    if (rc) return rc;
-    c->prepared = true;
-    c->hist_valid = false;                               // a new batch: no multistep history to resume
-    c->hist_face.clear();
-    return HD_OK;
+    return finish_prepare(c, s);
 }
 
 int hd_prepare_from_priors(hd_ctx* c, int batch, const float* const priors[5], const float* id_emb, void* stream) {
@@ -1012,8 +976,8 @@ int hd_prepare_from_priors(hd_ctx* c, int batch, const float* const priors[5], c
     if (!priors || !id_emb) HD_FAIL(c, HD_ERR_INVALID, "priors and id_emb are required");
     for (int i = 0; i < 5; ++i) if (!priors[i]) HD_FAIL(c, HD_ERR_INVALID, "prior %d is NULL", i);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    for (auto& ch : c->chains) {
-        c->ch = &ch;
+    for (auto& ch : c->ws->chains) {
+        ChainCursor on(c, &ch);
         for (int i = 0; i < 5; ++i) {
             const Level& lv = ch.lv[4 - i];
             const size_t total = (size_t)lv.M * lv.C;          // per chain; faces are contiguous in NCHW too
@@ -1026,16 +990,9 @@ int hd_prepare_from_priors(hd_ctx* c, int batch, const float* const priors[5], c
         for (int i = 0; i < 5; ++i) add_gates(c, prog, i);
         add_idc_term(c, prog);
         rc = run_ops(c, prog, s);
-        if (rc) break;
+        if (rc) return rc;
     }
-    c->ch = &c->chains[0];
-    if (rc) return rc;
-    rc = clear_masks(c, s);
-    if (rc) return rc;
-    c->prepared = true;
-    c->hist_valid = false;                               // a new batch: no multistep history to resume
-    c->hist_face.clear();
-    return HD_OK;
+    return finish_prepare(c, s);
 }
 
 int hd_fpg(hd_ctx* c, int batch, const float* cr_latent, float* const priors_out[5], void* stream) {
@@ -1045,12 +1002,12 @@ int hd_fpg(hd_ctx* c, int batch, const float* cr_latent, float* const priors_out
     if (!cr_latent || !priors_out) HD_FAIL(c, HD_ERR_INVALID, "hd_fpg: bad arguments");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const size_t lat_face = (size_t)4 * c->L * c->L;
-    for (auto& ch : c->chains) {
-        c->ch = &ch;
+    for (auto& ch : c->ws->chains) {
+        ChainCursor on(c, &ch);
         std::vector<Op> prog;
         add_fpg(c, prog, cr_latent + ch.face0 * lat_face);
         rc = run_ops(c, prog, s);
-        if (rc) break;
+        if (rc) return rc;
         for (int i = 0; i < 5; ++i) {
             if (!priors_out[i]) continue;
             const Level& lv = ch.lv[4 - i];
@@ -1059,8 +1016,6 @@ int hd_fpg(hd_ctx* c, int batch, const float* cr_latent, float* const priors_out
                                priors_out[i] + (size_t)ch.face0 * lv.C * lv.H * lv.H, lv.C, lv.H * lv.H, total);
         }
     }
-    c->ch = &c->chains[0];
-    if (rc) return rc;
     HIPCHECK(c, hipGetLastError());
     return HD_OK;
 }
@@ -1071,16 +1026,15 @@ int hd_idc(hd_ctx* c, int batch, const float* cr_face, float* id_emb_out, void* 
     if (rc) return rc;
     if (!cr_face || !id_emb_out) HD_FAIL(c, HD_ERR_INVALID, "hd_idc: bad arguments");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    for (auto& ch : c->chains) {
-        c->ch = &ch;
+    for (auto& ch : c->ws->chains) {
+        ChainCursor on(c, &ch);
         std::vector<Op> prog;
         add_resnet(c, prog, cr_face + (size_t)ch.face0 * 3 * 128 * 128);
         rc = run_ops(c, prog, s);
-        if (rc) break;
+        if (rc) return rc;
         HIPCHECK(c, hipMemcpyAsync(id_emb_out + (size_t)ch.face0 * 2048, ch.id_emb, (size_t)ch.B * 2048 * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
-    c->ch = &c->chains[0];
-    return rc;
+    return HD_OK;
 }
 
 int hd_scheduler_step(float* x_inout, const float* eps, const float* coef7, const float* noise, uint64_t seed, int step,
@@ -1109,25 +1063,25 @@ int hd_eps(hd_ctx* c, const float* x, const float* timesteps, int n_t, float* ep
     if (rc) return rc;
     rc = check_xcd(c);
     if (rc) return rc;
-    if (!x || !timesteps || !eps_out || (n_t != 1 && n_t != c->B)) HD_FAIL(c, HD_ERR_INVALID, "hd_eps: bad arguments (n_t must be 1 or batch)");
+    if (!x || !timesteps || !eps_out || (n_t != 1 && n_t != c->ws->B)) HD_FAIL(c, HD_ERR_INVALID, "hd_eps: bad arguments (n_t must be 1 or batch)");
     HIPCHECK(c, hipSetDevice(c->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     rc = ensure_film_rows(c, n_t);
     if (rc) return rc;
-    const size_t nlat = (size_t)c->B * 4 * c->L * c->L;
-    HIPCHECK(c, hipMemcpyAsync(c->lat, x, nlat * sizeof(float), hipMemcpyDeviceToDevice, s));
-    for (auto& ch : c->chains) HIPCHECK(c, hipMemsetAsync(ch.step_state, 0, sizeof(StepState), s));
+    const size_t nlat = (size_t)c->ws->B * 4 * c->L * c->L;
+    HIPCHECK(c, hipMemcpyAsync(c->ws->lat, x, nlat * sizeof(float), hipMemcpyDeviceToDevice, s));
+    for (auto& ch : c->ws->chains) HIPCHECK(c, hipMemsetAsync(ch.step_state, 0, sizeof(StepState), s));
     c->film_valid = false;                               // rows [0, n_t) are overwritten
     rc = compute_film(c, timesteps, n_t, s);
     if (rc) return rc;
     c->mode = (n_t == 1) ? EvalMode::EpsShared : EvalMode::EpsFaces;
-    for (auto& ch : c->chains) {
+    for (auto& ch : c->ws->chains) {
         rc = run_ops(c, ch.program, s, ch.index == 0 ? c->op_limit : -1);
         if (rc) return rc;
     }
-    rc = poison_on_abort(c, c->eps, nlat, s);
+    rc = poison_on_abort(c, c->ws->eps, nlat, s);
     if (rc) return rc;
-    HIPCHECK(c, hipMemcpyAsync(eps_out, c->eps, nlat * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHECK(c, hipMemcpyAsync(eps_out, c->ws->eps, nlat * sizeof(float), hipMemcpyDeviceToDevice, s));
     return HD_OK;
 }
 
@@ -1172,7 +1126,7 @@ static int stage_slots(hd_ctx* c, int* dev, const int32_t* slots, int n, hipStre
     return stage_submit(c, sg, s);
 }
 
-static bool any_mask(const hd_ctx* c) { return c->mask_face.size() == (size_t)c->B && masked_faces(c) > 0; }   // hd_mask_faces
+static bool any_mask(const hd_ctx* c) { return c->mask_face.size() == (size_t)c->ws->B && masked_faces(c) > 0; }   // hd_mask_faces
 
 static int grow_loop_buffers(hd_ctx* c, const SampleCall& call) {
     const int n = call.n;
@@ -1183,24 +1137,21 @@ static int grow_loop_buffers(hd_ctx* c, const SampleCall& call) {
         rc = dev_alloc(c, &c->coef_dev, (size_t)n * 7);
         if (rc) return rc;
         c->coef_cap = n;
-        c->graphs_valid = false;
-        // parked workspaces captured the old coefficient buffer into their ending launch as well (SchedArgs::coef)
-        for (auto& kv : c->ws_cache) kv.second.graphs_valid = false;
-        ++c->rows_gen;
+        invalidate_step_graphs(c);                        // every workspace's ending launch captured the old buffer (SchedArgs::coef)
     }
-    if (call.start_rows && (size_t)c->B * c->film_total > c->film_pf_cap) {   // the per-face graphs hold this pointer
+    if (call.start_rows && (size_t)c->ws->B * c->film_total > c->film_pf_cap) {   // the per-face graphs hold this pointer
         dev_free(c, c->film_pf);
-        rc = dev_alloc(c, &c->film_pf, (size_t)c->B * c->film_total);
+        rc = dev_alloc(c, &c->film_pf, (size_t)c->ws->B * c->film_total);
         if (rc) return rc;
-        c->film_pf_cap = (size_t)c->B * c->film_total;
+        c->film_pf_cap = (size_t)c->ws->B * c->film_total;
         ++c->rows_gen;
     }
-    if (call.start_rows && c->B > c->faces_cap) {         // read through StepState and by the gather launch: no graph holds this pointer
+    if (call.start_rows && c->ws->B > c->faces_cap) {         // read through StepState and by the gather launch: no graph holds this pointer
         dev_free(c, c->faces_dev);
         c->faces_dev = nullptr; c->faces_cap = 0;
-        rc = dev_alloc(c, &c->faces_dev, (size_t)c->B * kFaceArgBytes / sizeof(*c->faces_dev));
+        rc = dev_alloc(c, &c->faces_dev, (size_t)c->ws->B * kFaceArgBytes / sizeof(*c->faces_dev));
         if (rc) return rc;
-        c->faces_cap = c->B;
+        c->faces_cap = c->ws->B;
     }
     if (call.ncoef == 8 && n > c->c7_cap) {               // read through StepState: no graph holds this pointer
         dev_free(c, c->c7_dev);
@@ -1218,11 +1169,11 @@ static int stage_loop_state(hd_ctx* c, const SampleCall& call, bool upload_times
     const int n = call.n;
     const bool ms = call.ncoef == 8, pf = call.start_rows != nullptr;
     const bool mk = any_mask(c), pv = previews_ready(c);
-    const size_t nst = (ms || pf || mk || pv) ? c->chains.size() : 1;
+    const size_t nst = (ms || pf || mk || pv) ? c->ws->chains.size() : 1;
     StageCursor cur;
     const size_t coef0 = cur.take((size_t)n * 7 * sizeof(float)), ts0 = cur.take((size_t)n * sizeof(float));
     const size_t c70 = cur.take(ms ? (size_t)n * sizeof(float) : 0), st0 = cur.take(nst * sizeof(StepState));
-    const size_t faces0 = cur.take(pf ? (size_t)c->B * kFaceArgBytes : 0);
+    const size_t faces0 = cur.take(pf ? (size_t)c->ws->B * kFaceArgBytes : 0);
     hd_ctx::Stage* sg;
     int rc = stage_acquire(c, cur.at, &sg);
     if (rc) return rc;
@@ -1243,10 +1194,10 @@ static int stage_loop_state(hd_ctx* c, const SampleCall& call, bool upload_times
     }
     memcpy(host + ts0, call.timesteps, (size_t)n * sizeof(float));
     if (pf) st.hist_first = call.resume ? 0 : 1;
-    const FaceArgs dev = face_args(c->faces_dev, c->B);    // only the arrays the call gave are handed on
+    const FaceArgs dev = face_args(c->faces_dev, c->ws->B);    // only the arrays the call gave are handed on
     for (size_t k = 0; k < nst; ++k) {
-        const size_t f0 = (size_t)c->chains[k].face0;
-        if (ms) st.x0_hist = c->chains[k].x0_hist;
+        const size_t f0 = (size_t)c->ws->chains[k].face0;
+        if (ms) st.x0_hist = c->ws->chains[k].x0_hist;
         if (pf) st.start_rows = dev.rows + f0;
         if (call.face_seeds) st.face_seeds = dev.seeds + f0;
         if (call.first) st.face_first = dev.first + f0;
@@ -1259,13 +1210,13 @@ static int stage_loop_state(hd_ctx* c, const SampleCall& call, bool upload_times
         if (pv) {
             const size_t per_face = (size_t)4 * c->L * c->L;
             st.pv_x0 = c->pv_x0_dev + f0 * per_face; st.pv_snap = c->pv_snap_dev + f0 * per_face; st.pv_row = c->pv_row_dev + f0;
-            st.pv_every = c->pv_every; st.pv_snaps = c->pv_snaps; st.pv_batch = c->B;
+            st.pv_every = c->pv_every; st.pv_snaps = c->pv_snaps; st.pv_batch = c->ws->B;
         }
         memcpy(host + st0 + k * sizeof(StepState), &st, sizeof(st));
     }
     if (pf) {                                             // one upload; an array the call did not give is zero and nothing reads it
-        const FaceArgs h = face_args(host + faces0, c->B);
-        const size_t B = (size_t)c->B;
+        const FaceArgs h = face_args(host + faces0, c->ws->B);
+        const size_t B = (size_t)c->ws->B;
         memset(host + faces0, 0, B * kFaceArgBytes);
         memcpy(h.rows, call.start_rows, B * sizeof(int32_t));
         if (call.face_seeds) memcpy(h.seeds, call.face_seeds, B * sizeof(uint64_t));
@@ -1274,8 +1225,8 @@ static int stage_loop_state(hd_ctx* c, const SampleCall& call, bool upload_times
         HIPCHECK(c, hipMemcpyAsync(c->faces_dev, host + faces0, B * kFaceArgBytes, hipMemcpyHostToDevice, s));
     }
     HIPCHECK(c, hipMemcpyAsync(c->coef_dev, hcoef, (size_t)n * 7 * sizeof(float), hipMemcpyHostToDevice, s));
-    for (size_t k = 0; k < c->chains.size(); ++k)
-        HIPCHECK(c, hipMemcpyAsync(c->chains[k].step_state, host + st0 + (nst > 1 ? k : 0) * sizeof(StepState), sizeof(st), hipMemcpyHostToDevice, s));
+    for (size_t k = 0; k < c->ws->chains.size(); ++k)
+        HIPCHECK(c, hipMemcpyAsync(c->ws->chains[k].step_state, host + st0 + (nst > 1 ? k : 0) * sizeof(StepState), sizeof(st), hipMemcpyHostToDevice, s));
     if (upload_timesteps) HIPCHECK(c, hipMemcpyAsync(c->t_dev, host + ts0, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
     return stage_submit(c, sg, s);
 }
@@ -1295,12 +1246,12 @@ static int film_for_call(hd_ctx* c, const SampleCall& call, bool reuse, hipStrea
         HIPCHECK(c, hipStreamWaitEvent(s, c->film_ev, 0));       // no-op on the stream that computed it
     }
     if (call.start_rows) {                                // every face's row r_f (clamped to its last row)
-        const FaceArgs dev = face_args(c->faces_dev, c->B);
-        hipLaunchKernelGGL(film_rows_gather_kernel, dim3(8, c->B), dim3(256), 0, s, c->film_pf, c->film_table, dev.rows,
+        const FaceArgs dev = face_args(c->faces_dev, c->ws->B);
+        hipLaunchKernelGGL(film_rows_gather_kernel, dim3(8, c->ws->B), dim3(256), 0, s, c->film_pf, c->film_table, dev.rows,
                            call.end_rows ? dev.ends : nullptr, call.n, c->film_total);
         HIPCHECK(c, hipGetLastError());
     } else {
-        for (auto& ch : c->chains)                      // row 0
+        for (auto& ch : c->ws->chains)                      // row 0
             HIPCHECK(c, hipMemcpyAsync(ch.film_cur, c->film_table, (size_t)c->film_total * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
     return HD_OK;
@@ -1311,14 +1262,14 @@ static int film_for_call(hd_ctx* c, const SampleCall& call, bool reuse, hipStrea
 // stream.  pf: the per-face pair (Chain::graph_rows_*), captured in EvalMode::LoopRows like every pair in the mode sample_impl set.
 // Nothing is captured while the pair asked for is current.
 static int capture_step_graphs(hd_ctx* c, bool pf) {
-    bool stale = !c->graphs_valid || c->graph_film != c->film_table || c->graph_B != c->B;
+    bool stale = c->ws->graph_gen != c->graphs_gen || c->ws->graph_film != c->film_table || c->ws->graph_B != c->ws->B;
     if (pf) {
         stale = false;
-        for (auto& ch : c->chains) stale |= !ch.graph_rows_exec || ch.rows_gen != c->rows_gen || ch.rows_film != c->film_table;
+        for (auto& ch : c->ws->chains) stale |= !ch.graph_rows_exec || ch.rows_gen != c->rows_gen || ch.rows_film != c->film_table;
     }
     if (!stale) return HD_OK;
     c->stage_count = c->face_stage_count = 0;
-    for (auto& ch : c->chains) {
+    for (auto& ch : c->ws->chains) {
         hipGraphExec_t& g1 = pf ? ch.graph_rows_exec : ch.graph_exec;
         hipGraphExec_t& gm = pf ? ch.graph_rows_multi : ch.graph_multi;
         if (g1) { (void)hipGraphExecDestroy(g1); g1 = nullptr; }
@@ -1336,27 +1287,27 @@ static int capture_step_graphs(hd_ctx* c, bool pf) {
             if (e == hipSuccess) ++c->graph_captures;
             if (graph) (void)hipGraphDestroy(graph);
             if (e != hipSuccess) HD_FAIL(c, HD_ERR_HIP, "graph capture/instantiate failed: %s", hipGetErrorString(e));
-            if (multi == 0 && &ch == &c->chains[0]) {      // the one-step program of chain 0: what hd_get_option reports
+            if (multi == 0 && &ch == &c->ws->chains[0]) {      // the one-step program of chain 0: what hd_get_option reports
                 (pf ? c->rows_stages : c->sample_stages) = c->stage_count;
                 if (!pf) c->sample_face_stages = c->face_stage_count;
             }
         }
         if (pf) { ch.rows_gen = c->rows_gen; ch.rows_film = c->film_table; }
     }
-    if (!pf) { c->graphs_valid = true; c->graph_film = c->film_table; c->graph_B = c->B; }
+    if (!pf) { c->ws->graph_gen = c->graphs_gen; c->ws->graph_film = c->film_table; c->ws->graph_B = c->ws->B; }
     return HD_OK;
 }
 
 static int replay_step_graphs(hd_ctx* c, bool pf, int n_iters, hipStream_t s) {
     if (c->profiling) HIPCHECK(c, hipEventRecord(c->ev0, s));
     HIPCHECK(c, hipEventRecord(c->fork_ev, s));
-    for (auto& ch : c->chains) HIPCHECK(c, hipStreamWaitEvent(ch.stream, c->fork_ev, 0));
+    for (auto& ch : c->ws->chains) HIPCHECK(c, hipStreamWaitEvent(ch.stream, c->fork_ev, 0));
     int i = 0;
     for (; i + graph_steps() <= n_iters; i += graph_steps())
-        for (auto& ch : c->chains) HIPCHECK(c, hipGraphLaunch(pf ? ch.graph_rows_multi : ch.graph_multi, ch.stream));
+        for (auto& ch : c->ws->chains) HIPCHECK(c, hipGraphLaunch(pf ? ch.graph_rows_multi : ch.graph_multi, ch.stream));
     for (; i < n_iters; ++i)
-        for (auto& ch : c->chains) HIPCHECK(c, hipGraphLaunch(pf ? ch.graph_rows_exec : ch.graph_exec, ch.stream));
-    for (auto& ch : c->chains) {
+        for (auto& ch : c->ws->chains) HIPCHECK(c, hipGraphLaunch(pf ? ch.graph_rows_exec : ch.graph_exec, ch.stream));
+    for (auto& ch : c->ws->chains) {
         HIPCHECK(c, hipEventRecord(ch.done, ch.stream));
         HIPCHECK(c, hipStreamWaitEvent(s, ch.done, 0));
     }
@@ -1370,13 +1321,13 @@ static int replay_step_graphs(hd_ctx* c, bool pf, int n_iters, hipStream_t s) {
 // (faces / spans) only when every face has a history.
 static void record_history(hd_ctx* c, const SampleCall& call) {
     const bool ms = call.ncoef == 8;
-    if (c->hist_B != c->B || c->hist_face.size() != (size_t)c->B) c->hist_face.assign((size_t)c->B, 0);
+    if (c->hist_B != c->ws->B || c->hist_face.size() != (size_t)c->ws->B) c->hist_face.assign((size_t)c->ws->B, 0);
     if (ms && call.start_rows) {
-        for (int f = 0; f < c->B; ++f) if (call.start_rows[f] < (call.end_rows ? call.end_rows[f] : call.n)) c->hist_face[f] = 1;
+        for (int f = 0; f < c->ws->B; ++f) if (call.start_rows[f] < (call.end_rows ? call.end_rows[f] : call.n)) c->hist_face[f] = 1;
     } else {
-        c->hist_face.assign((size_t)c->B, ms ? 1 : 0);
+        c->hist_face.assign((size_t)c->ws->B, ms ? 1 : 0);
     }
-    c->hist_valid = ms; c->hist_B = c->B;
+    c->hist_valid = ms; c->hist_B = c->ws->B;
     if (ms && call.first) for (char h : c->hist_face) c->hist_valid = c->hist_valid && h;
 }
 
@@ -1385,23 +1336,23 @@ static int sample_impl(hd_ctx* c, float* x_inout, const SampleCall& call, void* 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool pf = call.start_rows != nullptr;
     const int n_iters = pf ? call.n_iters : call.n;
-    const size_t nlat = (size_t)c->B * 4 * c->L * c->L;
+    const size_t nlat = (size_t)c->ws->B * 4 * c->L * c->L;
     int rc = grow_loop_buffers(c, call);
     if (rc) return rc;
     const bool reuse_film = c->film_valid && c->film_sched.size() == (size_t)call.n &&
                             memcmp(c->film_sched.data(), call.timesteps, (size_t)call.n * sizeof(float)) == 0;
     rc = stage_loop_state(c, call, !reuse_film, s);
     if (rc) return rc;
-    HIPCHECK(c, hipMemcpyAsync(c->lat, x_inout, nlat * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHECK(c, hipMemcpyAsync(c->ws->lat, x_inout, nlat * sizeof(float), hipMemcpyDeviceToDevice, s));
     c->mode = pf ? EvalMode::LoopRows : EvalMode::LoopShared;
     rc = film_for_call(c, call, reuse_film, s);
     if (!rc) rc = capture_step_graphs(c, pf);
     if (!rc) rc = replay_step_graphs(c, pf, n_iters, s);
     if (rc) return rc;
     record_history(c, call);
-    rc = poison_on_abort(c, c->lat, nlat, s);
+    rc = poison_on_abort(c, c->ws->lat, nlat, s);
     if (rc) return rc;
-    HIPCHECK(c, hipMemcpyAsync(x_inout, c->lat, nlat * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHECK(c, hipMemcpyAsync(x_inout, c->ws->lat, nlat * sizeof(float), hipMemcpyDeviceToDevice, s));
     return HD_OK;
 }
 
@@ -1429,7 +1380,7 @@ static_assert(sizeof(hd_schedule) == sizeof(hd_schedule_ms), "the two schedule s
 static int check_rows(hd_ctx* c, SampleCall& call, const int32_t* rows, int n_iters) {
     const int n = call.n;
     int rmin = n;
-    for (int f = 0; f < c->B; ++f) {
+    for (int f = 0; f < c->ws->B; ++f) {
         if (rows[f] < 0 || rows[f] > n) HD_FAIL(c, HD_ERR_INVALID, "%s: start_rows[%d] = %d outside [0, %d]", call.fn, f, rows[f], n);
         if (rows[f] < rmin) rmin = rows[f];
     }
@@ -1441,7 +1392,7 @@ static int check_rows(hd_ctx* c, SampleCall& call, const int32_t* rows, int n_it
 // resume[f] of hd_sample_faces_multistep / hd_sample_spans: 0 or 1, and 1 only for a face that has a history; first_f = !resume_f
 static int check_face_resume(hd_ctx* c, const char* fn, int f, int32_t resume_f, int32_t* first_f) {
     if (resume_f != 0 && resume_f != 1) HD_FAIL(c, HD_ERR_INVALID, "%s: resume[%d] = %d is not 0 or 1", fn, f, resume_f);
-    const bool have = c->hist_B == c->B && c->hist_face.size() == (size_t)c->B;
+    const bool have = c->hist_B == c->ws->B && c->hist_face.size() == (size_t)c->ws->B;
     if (resume_f && !(have && c->hist_face[f]))
         HD_FAIL(c, HD_ERR_INVALID, "%s: resume[%d] = 1 but face %d has no multistep history (no multistep row since "
                                    "hd_prepare*, hd_prepare_slots refilled it, or a single-step call in between)", fn, f, f);
@@ -1479,7 +1430,7 @@ int hd_sample_rows_multistep(hd_ctx* c, float* x_inout, const hd_schedule_ms* sc
     int rc = sample_enter(c, "hd_sample_rows_multistep", x_inout, as_rows_of_8(sched), 8, start_rows && (resume == 0 || resume == 1), noise, seed, call);
     if (!rc) rc = check_rows(c, call, start_rows, n_iters);
     if (rc) return rc;
-    if (resume && !(c->hist_valid && c->hist_B == c->B))
+    if (resume && !(c->hist_valid && c->hist_B == c->ws->B))
         HD_FAIL(c, HD_ERR_INVALID, "hd_sample_rows_multistep: resume = 1 but no multistep history of this batch (no earlier multistep call, "
                                    "hd_prepare since, another batch size or a single-step call in between)");
     call.resume = resume;
@@ -1502,8 +1453,8 @@ int hd_sample_faces_multistep(hd_ctx* c, float* x_inout, const hd_schedule_ms* s
     int rc = sample_enter(c, "hd_sample_faces_multistep", x_inout, as_rows_of_8(sched), 8, start_rows && resume, noise, seed, call);
     if (!rc) rc = check_rows(c, call, start_rows, n_iters);
     if (rc) return rc;
-    std::vector<int32_t> first((size_t)c->B);
-    for (int f = 0; f < c->B; ++f) {
+    std::vector<int32_t> first((size_t)c->ws->B);
+    for (int f = 0; f < c->ws->B; ++f) {
         rc = check_face_resume(c, call.fn, f, resume[f], &first[f]);
         if (rc) return rc;
     }
@@ -1520,9 +1471,9 @@ int hd_sample_spans(hd_ctx* c, float* x_inout, const hd_schedule_ms* table, cons
     int rc = sample_enter(c, "hd_sample_spans", x_inout, as_rows_of_8(table), 8, begin_rows && end_rows && start_rows && resume, noise, seed, call);
     if (rc) return rc;
     const int n = call.n;
-    std::vector<int32_t> first((size_t)c->B);
+    std::vector<int32_t> first((size_t)c->ws->B);
     int longest = 0;
-    for (int f = 0; f < c->B; ++f) {
+    for (int f = 0; f < c->ws->B; ++f) {
         const int b = begin_rows[f], e = end_rows[f], r = start_rows[f];
         if (!(0 <= b && b <= r && r <= e && e <= n))
             HD_FAIL(c, HD_ERR_INVALID, "hd_sample_spans: face %d: need 0 <= begin (%d) <= start (%d) <= end (%d) <= n_steps (%d)", f, b, r, e, n);
@@ -1551,46 +1502,44 @@ int hd_prepare_slots(hd_ctx* c, int n, const int32_t* slots, const float* cr_lat
         HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: this context holds the unconditional Denoiser, CoarseRestoration or the VAE (no conditioning)");
     int rc = check_ready(c, true);
     if (rc) return rc;
-    if (n < 1 || n > c->B) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: n = %d outside [1, %d]", n, c->B);
+    if (n < 1 || n > c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: n = %d outside [1, %d]", n, c->ws->B);
     if (!slots || !cr_latent || (!cr_face == !id_emb))
         HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: need slots, cr_latent and exactly one of cr_face / id_emb");
     {
-        std::vector<char> seen((size_t)c->B, 0);
+        std::vector<char> seen((size_t)c->ws->B, 0);
         for (int j = 0; j < n; ++j) {
-            if (slots[j] < 0 || slots[j] >= c->B) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: slots[%d] = %d outside [0, %d)", j, slots[j], c->B);
+            if (slots[j] < 0 || slots[j] >= c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: slots[%d] = %d outside [0, %d)", j, slots[j], c->ws->B);
             if (seen[slots[j]]) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: slot %d given twice", slots[j]);
             seen[slots[j]] = 1;
         }
     }
-    if (c->chains.size() > (size_t)kSlotChains) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: more than %d chains", kSlotChains);
+    if (c->ws->chains.size() > (size_t)kSlotChains) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: more than %d chains", kSlotChains);
     HIPCHECK(c, hipSetDevice(c->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    Chain& sc = c->slot_stage;
-    if (!c->slot_stage_ok) {                               // first refill of this workspace: its buffers join the workspace's allocations
+    Chain& sc = c->ws->slot_stage;
+    if (!c->ws->slot_stage_ok) {                               // first refill of this workspace: its buffers join the workspace's allocations
         sc = Chain();
-        sc.index = -1; sc.B = c->B; sc.face0 = 0;          // index -1: no introspection names (those stay on chain 0)
-        c->ws_scope = true;
+        sc.index = -1; sc.B = c->ws->B; sc.face0 = 0;          // index -1: no introspection names (those stay on chain 0)
         rc = alloc_chain(c, sc);
-        if (!rc) rc = dev_alloc(c, &c->slots_dev, (size_t)c->B);
-        c->ws_scope = false;
+        if (!rc) rc = ws_alloc(c, &c->ws->slots_dev, (size_t)c->ws->B);
         if (rc) { destroy_chain_queue(sc); return rc; }
-        c->slot_stage_ok = true;
+        c->ws->slot_stage_ok = true;
     }
     // the staging chain at batch n: the level geometry of a batch of n faces (its buffers hold B)
     sc.B = n;
     for (int l = 0; l < 5; ++l) sc.lv[l].M = n * sc.lv[l].H * sc.lv[l].H;
-    Chain* prev = c->ch;
-    c->ch = &sc;
     std::vector<Op> prog;
-    add_fpg(c, prog, cr_latent);
-    if (cr_face) add_resnet(c, prog, cr_face);
-    for (int i = 0; i < 5; ++i) add_gates(c, prog, i);
-    add_idc_term(c, prog);
-    c->ch = prev;
+    {
+        ChainCursor on(c, &sc);
+        add_fpg(c, prog, cr_latent);
+        if (cr_face) add_resnet(c, prog, cr_face);
+        for (int i = 0; i < 5; ++i) add_gates(c, prog, i);
+        add_idc_term(c, prog);
+    }
     if (!cr_face) HIPCHECK(c, hipMemcpyAsync(sc.id_emb, id_emb, (size_t)n * 2048 * sizeof(float), hipMemcpyDeviceToDevice, s));
     rc = run_ops(c, prog, s);
     if (rc) return rc;
-    rc = stage_slots(c, c->slots_dev, slots, n, s);
+    rc = stage_slots(c, c->ws->slots_dev, slots, n, s);
     if (rc) return rc;
     SlotScatterP p{};
     int b = 0;
@@ -1600,37 +1549,37 @@ int hd_prepare_slots(hd_ctx* c, int n, const int32_t* slots, const float* cr_lat
         float* const srcs[3] = {sc.prior[i], sc.gate_c[i], sc.gate_s[i]};
         for (int q = 0; q < 3; ++q, ++b) {
             p.src[b] = srcs[q]; p.sz[b] = sz[q];
-            for (size_t k = 0; k < c->chains.size(); ++k) p.dst[k][b] = q == 0 ? c->chains[k].prior[i] : q == 1 ? c->chains[k].gate_c[i] : c->chains[k].gate_s[i];
+            for (size_t k = 0; k < c->ws->chains.size(); ++k) p.dst[k][b] = q == 0 ? c->ws->chains[k].prior[i] : q == 1 ? c->ws->chains[k].gate_c[i] : c->ws->chains[k].gate_s[i];
         }
     }
     p.src[b] = sc.idc_term; p.sz[b] = 2048 * c->S * c->S;
-    for (size_t k = 0; k < c->chains.size(); ++k) p.dst[k][b] = c->chains[k].idc_term;
+    for (size_t k = 0; k < c->ws->chains.size(); ++k) p.dst[k][b] = c->ws->chains[k].idc_term;
     ++b;
     p.src[b] = sc.id_emb; p.sz[b] = 2048;
-    for (size_t k = 0; k < c->chains.size(); ++k) p.dst[k][b] = c->chains[k].id_emb;
-    p.slots = c->slots_dev; p.faces_per_chain = c->chains[0].B;
+    for (size_t k = 0; k < c->ws->chains.size(); ++k) p.dst[k][b] = c->ws->chains[k].id_emb;
+    p.slots = c->ws->slots_dev; p.faces_per_chain = c->ws->chains[0].B;
     hipLaunchKernelGGL(slot_scatter_kernel, dim3(32, n, kSlotBufs), dim3(256), 0, s, p);
     HIPCHECK(c, hipGetLastError());
     // the refilled faces carry no mask (their flags are cleared in stream order; the slot list is on the device already)
-    if (c->mask_face.size() == (size_t)c->B) {
+    if (c->mask_face.size() == (size_t)c->ws->B) {
         bool any = false;
         for (int j = 0; j < n; ++j) { any |= c->mask_face[slots[j]] != 0; c->mask_face[slots[j]] = 0; }
         if (any) {
             MaskScatterP mp{};
-            mp.on = c->mask_on_dev; mp.slots = c->slots_dev; mp.ll = c->L * c->L;
+            mp.on = c->mask_on_dev; mp.slots = c->ws->slots_dev; mp.ll = c->L * c->L;
             hipLaunchKernelGGL(mask_scatter_kernel, dim3(1, n), dim3(64), 0, s, mp);
             HIPCHECK(c, hipGetLastError());
         }
     }
     if (previews_ready(c)) {                               // ... and no preview: row -1, zeroed planes
         PreviewP pp{};
-        pp.x0 = c->pv_x0_dev; pp.snap = c->pv_snap_dev; pp.rows = c->pv_row_dev; pp.slots = c->slots_dev;
-        pp.B = c->B; pp.snaps = c->pv_snaps; pp.ll4 = 4 * c->L * c->L;
+        pp.x0 = c->pv_x0_dev; pp.snap = c->pv_snap_dev; pp.rows = c->pv_row_dev; pp.slots = c->ws->slots_dev;
+        pp.B = c->ws->B; pp.snaps = c->pv_snaps; pp.ll4 = 4 * c->L * c->L;
         hipLaunchKernelGGL(preview_reset_kernel, dim3(4, n), dim3(256), 0, s, pp);
         HIPCHECK(c, hipGetLastError());
     }
     // the refilled faces have no multistep history; hd_sample_rows_multistep(resume = 1) no longer continues the whole batch
-    if (c->hist_B == c->B && c->hist_face.size() == (size_t)c->B)
+    if (c->hist_B == c->ws->B && c->hist_face.size() == (size_t)c->ws->B)
         for (int j = 0; j < n; ++j) c->hist_face[slots[j]] = 0;
     c->hist_valid = false;
     return HD_OK;
@@ -1644,38 +1593,38 @@ int hd_mask_faces(hd_ctx* c, int n, const int32_t* slots, const float* mask, con
     if (c->cr || c->vae) HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: this context holds CoarseRestoration or the VAE (no sampling loop)");
     int rc = check_ready(c, true);
     if (rc) return rc;
-    if (n < 1 || n > c->B) HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: n = %d outside [1, %d]", n, c->B);
-    if (!slots && n != c->B) HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: slots == NULL needs n == batch (%d), got %d", c->B, n);
+    if (n < 1 || n > c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: n = %d outside [1, %d]", n, c->ws->B);
+    if (!slots && n != c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: slots == NULL needs n == batch (%d), got %d", c->ws->B, n);
     if ((!mask != !known) || (!mask != !known_noise))
         HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: give mask, known and known_noise together, or none of them (clear)");
     if (slots) {
-        std::vector<char> seen((size_t)c->B, 0);
+        std::vector<char> seen((size_t)c->ws->B, 0);
         for (int j = 0; j < n; ++j) {
-            if (slots[j] < 0 || slots[j] >= c->B) HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: slots[%d] = %d outside [0, %d)", j, slots[j], c->B);
+            if (slots[j] < 0 || slots[j] >= c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: slots[%d] = %d outside [0, %d)", j, slots[j], c->ws->B);
             if (seen[slots[j]]) HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: slot %d given twice", slots[j]);
             seen[slots[j]] = 1;
         }
     }
-    if (c->mask_face.size() != (size_t)c->B) c->mask_face.assign((size_t)c->B, 0);
+    if (c->mask_face.size() != (size_t)c->ws->B) c->mask_face.assign((size_t)c->ws->B, 0);
     if (!mask && masked_faces(c) == 0) return HD_OK;       // nothing to clear
     HIPCHECK(c, hipSetDevice(c->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const size_t ll = (size_t)c->L * c->L;
-    if (c->B > c->mask_cap) {                              // a larger batch than ever masked: hd_prepare* has cleared every mask since
+    if (c->ws->B > c->mask_cap) {                              // a larger batch than ever masked: hd_prepare* has cleared every mask since
         dev_free(c, c->mask_dev); dev_free(c, c->mask_known_dev); dev_free(c, c->mask_noise_dev);
         dev_free(c, c->mask_on_dev); dev_free(c, c->mask_slots_dev);
         c->mask_dev = c->mask_known_dev = c->mask_noise_dev = nullptr; c->mask_on_dev = c->mask_slots_dev = nullptr; c->mask_cap = 0;
-        rc = dev_alloc(c, &c->mask_dev, (size_t)c->B * ll);
-        if (!rc) rc = dev_alloc(c, &c->mask_known_dev, (size_t)c->B * 4 * ll);
-        if (!rc) rc = dev_alloc(c, &c->mask_noise_dev, (size_t)c->B * 4 * ll);
-        if (!rc) rc = dev_alloc(c, &c->mask_on_dev, (size_t)c->B);
-        if (!rc) rc = dev_alloc(c, &c->mask_slots_dev, (size_t)c->B);
+        rc = dev_alloc(c, &c->mask_dev, (size_t)c->ws->B * ll);
+        if (!rc) rc = dev_alloc(c, &c->mask_known_dev, (size_t)c->ws->B * 4 * ll);
+        if (!rc) rc = dev_alloc(c, &c->mask_noise_dev, (size_t)c->ws->B * 4 * ll);
+        if (!rc) rc = dev_alloc(c, &c->mask_on_dev, (size_t)c->ws->B);
+        if (!rc) rc = dev_alloc(c, &c->mask_slots_dev, (size_t)c->ws->B);
         if (rc) return rc;
-        c->mask_cap = c->B;
-        HIPCHECK(c, hipMemsetAsync(c->mask_dev, 0, (size_t)c->B * ll * sizeof(float), s));
-        HIPCHECK(c, hipMemsetAsync(c->mask_known_dev, 0, (size_t)c->B * 4 * ll * sizeof(float), s));
-        HIPCHECK(c, hipMemsetAsync(c->mask_noise_dev, 0, (size_t)c->B * 4 * ll * sizeof(float), s));
-        HIPCHECK(c, hipMemsetAsync(c->mask_on_dev, 0, (size_t)c->B * sizeof(int), s));
+        c->mask_cap = c->ws->B;
+        HIPCHECK(c, hipMemsetAsync(c->mask_dev, 0, (size_t)c->ws->B * ll * sizeof(float), s));
+        HIPCHECK(c, hipMemsetAsync(c->mask_known_dev, 0, (size_t)c->ws->B * 4 * ll * sizeof(float), s));
+        HIPCHECK(c, hipMemsetAsync(c->mask_noise_dev, 0, (size_t)c->ws->B * 4 * ll * sizeof(float), s));
+        HIPCHECK(c, hipMemsetAsync(c->mask_on_dev, 0, (size_t)c->ws->B * sizeof(int), s));
     }
     if (slots) {
         rc = stage_slots(c, c->mask_slots_dev, slots, n, s);
@@ -1721,14 +1670,14 @@ int hd_preview_read(hd_ctx* c, int n, const int32_t* slots, int snapshot, float*
     if (rc) return rc;
     if (!previews_ready(c)) HD_FAIL(c, HD_ERR_NOT_READY, "hd_preview_read: previews are off (hd_preview_config)");
     if (!x0_out) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: x0_out is NULL");
-    if (n < 1 || n > c->B) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: n = %d outside [1, %d]", n, c->B);
-    if (!slots && n != c->B) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: slots == NULL needs n == batch (%d), got %d", c->B, n);
+    if (n < 1 || n > c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: n = %d outside [1, %d]", n, c->ws->B);
+    if (!slots && n != c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: slots == NULL needs n == batch (%d), got %d", c->ws->B, n);
     if (snapshot < -1 || snapshot >= c->pv_snaps)
         HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: snapshot = %d outside [-1, %d)", snapshot, c->pv_snaps);
     if (slots) {
-        std::vector<char> seen((size_t)c->B, 0);
+        std::vector<char> seen((size_t)c->ws->B, 0);
         for (int j = 0; j < n; ++j) {
-            if (slots[j] < 0 || slots[j] >= c->B) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: slots[%d] = %d outside [0, %d)", j, slots[j], c->B);
+            if (slots[j] < 0 || slots[j] >= c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: slots[%d] = %d outside [0, %d)", j, slots[j], c->ws->B);
             if (seen[slots[j]]) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: slot %d given twice", slots[j]);
             seen[slots[j]] = 1;
         }
@@ -1741,8 +1690,8 @@ int hd_preview_read(hd_ctx* c, int n, const int32_t* slots, int snapshot, float*
     }
     const size_t per_face = (size_t)4 * c->L * c->L;
     PreviewReadP p{};
-    p.plane = snapshot < 0 ? c->pv_x0_dev : c->pv_snap_dev + (size_t)snapshot * c->B * per_face;
-    p.rows = c->pv_row_dev + (size_t)(1 + snapshot) * c->B;
+    p.plane = snapshot < 0 ? c->pv_x0_dev : c->pv_snap_dev + (size_t)snapshot * c->ws->B * per_face;
+    p.rows = c->pv_row_dev + (size_t)(1 + snapshot) * c->ws->B;
     p.slots = slots ? c->pv_slots_dev : nullptr; p.out = x0_out; p.rows_out = rows_out; p.ll4 = (int)per_face;
     hipLaunchKernelGGL(preview_gather_kernel, dim3(4, n), dim3(256), 0, s, p);
     HIPCHECK(c, hipGetLastError());
@@ -1751,13 +1700,13 @@ int hd_preview_read(hd_ctx* c, int n, const int32_t* slots, int snapshot, float*
 
 static std::vector<Op>* which_program(hd_ctx* c, int which) {
     static std::vector<Op> empty;
-    if (c->cr) return &c->cr_program;
-    if (c->vae) return which == 0 ? &c->vae_enc_prog : &c->vae_dec_prog;
-    if (c->chains.empty()) return &empty;
-    return which == 0 ? &c->chains[0].program : &c->chains[0].prep_program;
+    if (c->cr) return &c->ws->cr_program;
+    if (c->vae) return which == 0 ? &c->ws->vae_enc_prog : &c->ws->vae_dec_prog;
+    if (c->ws->chains.empty()) return &empty;
+    return which == 0 ? &c->ws->chains[0].program : &c->ws->chains[0].prep_program;
 }
 int hd_num_ops(hd_ctx* c, int which) { return c ? (int)which_program(c, which)->size() : 0; }
-int hd_num_chains(hd_ctx* c) { return c ? (int)c->chains.size() : 0; }
+int hd_num_chains(hd_ctx* c) { return c ? (int)c->ws->chains.size() : 0; }
 int hd_debug_limit_ops(hd_ctx* c, int which, int n) {
     if (!c) return HD_ERR_INVALID;
     (which == 0 ? c->op_limit : c->prep_limit) = n;
@@ -1789,15 +1738,24 @@ int64_t hd_debug_read_op(hd_ctx* c, int which, int i, float* host_out, int64_t m
     return read_to_host(c, (*p)[i].out, (*p)[i].out_elems, (*p)[i].out_bf16, host_out, max_elems);
 }
 
+// a named buffer of the active workspace, else one of the context's own
+static const std::pair<void*, std::pair<size_t, int>>* find_debug(hd_ctx* c, const char* name) {
+    for (const auto* m : {&c->ws->dbg, &c->dbg}) {
+        const auto it = m->find(name);
+        if (it != m->end()) return &it->second;
+    }
+    return nullptr;
+}
+
 int64_t hd_debug_read(hd_ctx* c, const char* name, float* host_out, int64_t max_elems) {
     if (!c || !name) return HD_ERR_INVALID;
     {                                                      // the mask buffers belong to the context, not to a workspace: sized by the batch in use
         const std::string k = name;
         const bool m = k == "mask", mkn = k == "mask_known", mnz = k == "mask_noise";
         if (m || mkn || mnz) {
-            if (!c->mask_dev || c->B < 1 || c->B > c->mask_cap) HD_FAIL(c, HD_ERR_INVALID, "debug buffer %s: no mask has been set for this batch", name);
+            if (!c->mask_dev || c->ws->B < 1 || c->ws->B > c->mask_cap) HD_FAIL(c, HD_ERR_INVALID, "debug buffer %s: no mask has been set for this batch", name);
             const size_t ll = (size_t)c->L * c->L;
-            return read_to_host(c, m ? c->mask_dev : mkn ? c->mask_known_dev : c->mask_noise_dev, (size_t)c->B * (m ? ll : 4 * ll), 0, host_out, max_elems);
+            return read_to_host(c, m ? c->mask_dev : mkn ? c->mask_known_dev : c->mask_noise_dev, (size_t)c->ws->B * (m ? ll : 4 * ll), 0, host_out, max_elems);
         }
     }
     {                                                      // the preview planes too (preview_rows: the int32 rows as they are, 4 bytes each)
@@ -1805,35 +1763,35 @@ int64_t hd_debug_read(hd_ctx* c, const char* name, float* host_out, int64_t max_
         const bool px = k == "x0_preview", pr = k == "preview_rows", ps = k == "preview_snaps";
         if (px || pr || ps) {
             if (!previews_ready(c)) HD_FAIL(c, HD_ERR_INVALID, "debug buffer %s: previews are off or no batch has been prepared since", name);
-            const size_t n = (size_t)c->B * 4 * c->L * c->L;
+            const size_t n = (size_t)c->ws->B * 4 * c->L * c->L;
             if (ps && c->pv_snaps == 0) return 0;
             return read_to_host(c, px ? (const void*)c->pv_x0_dev : pr ? (const void*)c->pv_row_dev : (const void*)c->pv_snap_dev,
-                                px ? n : pr ? (size_t)c->B : (size_t)c->pv_snaps * n, 0, host_out, max_elems);
+                                px ? n : pr ? (size_t)c->ws->B : (size_t)c->pv_snaps * n, 0, host_out, max_elems);
         }
     }
-    auto it = c->dbg.find(name);
-    if (it == c->dbg.end()) HD_FAIL(c, HD_ERR_INVALID, "unknown debug buffer %s", name);
-    return read_to_host(c, it->second.first, it->second.second.first, it->second.second.second, host_out, max_elems);
+    const auto* e = find_debug(c, name);
+    if (!e) HD_FAIL(c, HD_ERR_INVALID, "unknown debug buffer %s", name);
+    return read_to_host(c, e->first, e->second.first, e->second.second, host_out, max_elems);
 }
 
 int hd_debug_write(hd_ctx* c, const char* name, const float* host_in, int64_t n_elems) {
     if (!c || !name || !host_in) return HD_ERR_INVALID;
-    auto it = c->dbg.find(name);
-    if (it == c->dbg.end()) HD_FAIL(c, HD_ERR_INVALID, "unknown debug buffer %s", name);
-    const size_t n = it->second.second.first;
+    const auto* e = find_debug(c, name);
+    if (!e) HD_FAIL(c, HD_ERR_INVALID, "unknown debug buffer %s", name);
+    const size_t n = e->second.first;
     if ((int64_t)n != n_elems) HD_FAIL(c, HD_ERR_INVALID, "debug write of %s needs %zu elements", name, n);
     HIPCHECK(c, hipSetDevice(c->device));
     HIPCHECK(c, hipDeviceSynchronize());
-    if (it->second.second.second) {                        // bf16 buffer: round to nearest even, as the kernels do
+    if (e->second.second) {                        // bf16 buffer: round to nearest even, as the kernels do
         std::vector<unsigned short> tmp(n);
         for (size_t i = 0; i < n; ++i) {
             unsigned u; memcpy(&u, &host_in[i], 4);
             if ((u & 0x7fffffffu) > 0x7f800000u) { tmp[i] = (unsigned short)((u >> 16) | 0x40u); continue; }   // NaN stays NaN
             tmp[i] = (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
         }
-        HIPCHECK(c, hipMemcpy(it->second.first, tmp.data(), n * 2, hipMemcpyHostToDevice));
+        HIPCHECK(c, hipMemcpy(e->first, tmp.data(), n * 2, hipMemcpyHostToDevice));
     } else {
-        HIPCHECK(c, hipMemcpy(it->second.first, host_in, n * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHECK(c, hipMemcpy(e->first, host_in, n * sizeof(float), hipMemcpyHostToDevice));
     }
     return HD_OK;
 }
@@ -1850,9 +1808,7 @@ int hd_set_option(hd_ctx* c, const char* key, int value) {
     else if (k == "stage_limit_first") c->stage_limit_first = value;
     else if (k == "stage_test_abort") c->stage_test_abort = value;   // fault injection: 1..: XCD stages, group 0 gives up its wait for phase value - 1; 1000 + b: face stages, face 0, block b; 2000 + p: a loader wave of hd_xcd2.hpp, phase p
     else HD_FAIL(c, HD_ERR_INVALID, "unknown option %s", key);
-    c->graphs_valid = false;                               // captured graphs hold the old choice
-    for (auto& kv : c->ws_cache) kv.second.graphs_valid = false;
-    ++c->rows_gen;
+    invalidate_step_graphs(c);                             // captured graphs hold the old choice
     return HD_OK;
 }
 int hd_get_option(hd_ctx* c, const char* key) {
@@ -1868,13 +1824,13 @@ int hd_get_option(hd_ctx* c, const char* key) {
     if (k == "sample_stage_launches") return c->sample_stages;
     if (k == "sample_face_stage_launches") return c->sample_face_stages;
     if (k == "rows_stage_launches") return c->rows_stages;
-    if (k == "masked_faces") return c->mask_face.size() == (size_t)c->B ? masked_faces(c) : 0;   // faces that carry a mask (hd_mask_faces)
+    if (k == "masked_faces") return c->mask_face.size() == (size_t)c->ws->B ? masked_faces(c) : 0;   // faces that carry a mask (hd_mask_faces)
     if (k == "preview") return c->pv_on ? 1 : 0;                 // hd_preview_config
     if (k == "graph_captures") return c->graph_captures;         // step graphs instantiated by this context (hd_prepare_slots adds none)
     // the folds of the program built for the batch in use (0 before the first call): the decisions build_denoiser_program made, and
     // whether the launch that carries them still runs -- the face-stage entries need the face stages on and a single chain
-    const Chain* ch = c->chains.empty() ? nullptr : &c->chains[0];
-    const bool face_runs = c->xcd_ok && c->face_on && c->chains.size() == 1;
+    const Chain* ch = c->ws->chains.empty() ? nullptr : &c->ws->chains[0];
+    const bool face_runs = c->xcd_ok && c->face_on && c->ws->chains.size() == 1;
     if (k == "intro_fold") return (ch && ch->fold_intro && face_runs) ? 1 : 0;
     if (k == "down_fold") return (ch && ch->fold_down0 && face_runs) ? 1 : 0;
     if (k == "up_fold") return (ch && ch->fold_up && face_runs) ? 1 : 0;
