@@ -14,6 +14,8 @@
     python examples/pipeline.py --stream 200 --preview-every 1      # one progress line per step() of the serving loop
     python examples/pipeline.py --mask-box 32,40,96,72 --mask-box 48,84,80,108 [--strength 0.8]   # inpainting: resample the boxes (pixels of
                                                           # the 128 x 128 face), keep the coarse restoration everywhere else
+    python examples/pipeline.py --fidelity 0.5 [--fidelity-scale 4] [--fidelity-rows 0,30]   # low-pass guidance towards the coarse restoration:
+                                                          # its structure and colour stay, the diffusion adds the detail
 """
 import argparse
 import os
@@ -50,9 +52,18 @@ def main():
     ap.add_argument("--preview-every", type=int, default=None, metavar="N",
                     help="progress previews: decode the denoised estimate of every N-th row through the VAE and print its mean absolute "
                          "difference to the final image; with --stream: one progress line per step()")
+    ap.add_argument("--fidelity", type=float, default=None, metavar="W",
+                    help="low-pass guidance towards cr_latent with weight W in (0, 1]: x0 <- x0 + W (LP_N(cr_latent) - LP_N(x0)) on every "
+                         "guided row (composes with --strength, --mask-box, --scheduler and --stream)")
+    ap.add_argument("--fidelity-scale", type=int, default=4, metavar="N",
+                    help="--fidelity: block size N of the low-pass filter, a divisor of 16 (1: every element, 16: only each channel's mean)")
+    ap.add_argument("--fidelity-rows", default=None, metavar="A,B", help="--fidelity: guide rows A <= j < B of each face's own schedule (default: all)")
     a = ap.parse_args()
     if a.preview_every is not None and a.preview_every < 1:
         ap.error("--preview-every must be >= 1")
+    if a.fidelity is None and (a.fidelity_rows is not None or a.fidelity_scale != 4):
+        ap.error("--fidelity-scale / --fidelity-rows need --fidelity")
+    a.fid_rows = None if a.fidelity_rows is None else tuple(int(v) for v in a.fidelity_rows.split(","))
     a.mask = None
     if a.mask_box:
         a.mask = sampling.region_mask([tuple(int(v) for v in b.split(",")) for b in a.mask_box], 16)
@@ -92,6 +103,8 @@ def main():
     torch.cuda.synchronize(); t2 = time.time()
     sch.set_timesteps(steps)
     pv = {} if a.preview_every is None else {"previews": a.preview_every}
+    if a.fidelity is not None:                                         # the coarse restoration's low frequencies stay (set_guidance checks the values)
+        pv.update(guide=cr_latent, guide_weight=a.fidelity, guide_scale=a.fidelity_scale, guide_rows=a.fid_rows)
     if a.mask is not None:                                             # inpainting: the boxes are resampled, the rest stays cr_latent
         latent, start, nz = sampling.inpaint_start(sch, cr_latent, 1.0 if a.strength is None else a.strength, noise=latent)
         out = sampling.sample(model, latent, cr_face, cr_latent, sch, start_steps=start, mask=a.mask[None].expand(B, 16, 16),
@@ -102,8 +115,11 @@ def main():
         latent, start = sampling.img2img_start(sch, cr_latent, a.strength, noise=latent)
         out = sampling.sample(model, latent, cr_face, cr_latent, sch, start_steps=start, **pv)
     snaps = None
-    if pv:
+    if a.preview_every is not None:
         out, snaps, snap_rows = out
+    if a.fidelity is not None:
+        lp = lambda t: sampling.low_pass(t, a.fidelity_scale)         # noqa: E731
+        print(f"fidelity {a.fidelity} at N = {a.fidelity_scale}: mean |LP(latent) - LP(cr_latent)| {float((lp(out) - lp(cr_latent)).abs().mean()):.4f}")
     torch.cuda.synchronize(); t3 = time.time()
     images = vae.decode(out / 0.18215).sample                          # the reference's call form; decode_scaled(out) is the fused one
     torch.cuda.synchronize(); t4 = time.time()
@@ -144,7 +160,8 @@ def stream(a, cr, vae, model, sch, steps, dev):
         pick = [counts[i % len(counts)] for i in range(N)]
     cs = sampling.ContinuousSampler(model, sch, batch=a.batch, refill_every=a.refill_every, previews=a.preview_every is not None)
     torch.cuda.synchronize(); t1 = time.time()
-    ids = [cs.submit(f, l, seed=1000 + i, strength=strength[i], mask=a.mask, **({"schedule": pick[i]} if a.steps_mix else {}))
+    fid = {} if a.fidelity is None else dict(fidelity=a.fidelity, fidelity_scale=a.fidelity_scale, fidelity_rows=a.fid_rows)
+    ids = [cs.submit(f, l, seed=1000 + i, strength=strength[i], mask=a.mask, **fid, **({"schedule": pick[i]} if a.steps_mix else {}))
            for i, (f, l) in enumerate(reqs)]
     out = {}
     while cs.busy():

@@ -224,10 +224,10 @@ static __global__ __launch_bounds__(EndCfg::THREADS) void hca_ending_conv_kernel
         const int step = p.sa.st->step;
         if constexpr (PF) {
             const int r = st_row(p.sa.st, face), k = r + step;       // workgroup-uniform: one face
-            if (k < st_end(p.sa.st, face))
+            if (k < st_end(p.sa.st, face) && !st_guided(p.sa.st, face, k - st_begin(p.sa.st, face)))
                 p.sa.lat[o] = sched_update<true>(p.sa.lat[o], e, p.sa.coef + (size_t)k * 7, p.sa.st, k, (size_t)p.sa.elem0 + o, p.sa.n_total, o,
                                                  st_first(p.sa.st, face, k, r), face, (unsigned)(o - (size_t)face * 4 * S * S), S * S);
-        } else {
+        } else if (!st_guided(p.sa.st, face, step)) {
             p.sa.lat[o] = sched_update(p.sa.lat[o], e, p.sa.coef + (size_t)step * 7, p.sa.st, step, (size_t)p.sa.elem0 + o, p.sa.n_total, o, false,
                                        face, (unsigned)(o - (size_t)face * 4 * S * S), S * S);
         }

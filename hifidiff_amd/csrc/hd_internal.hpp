@@ -279,6 +279,16 @@ struct hd_ctx {
     int pv_every = 1, pv_snaps = 0, pv_B = 0, pv_planes = 0;
     float *pv_x0_dev = nullptr, *pv_snap_dev = nullptr;
     int *pv_row_dev = nullptr, *pv_slots_dev = nullptr;
+    // low-pass fidelity guidance (hd_guide_config / hd_guide_faces): the switch -- while it is on the step ends with guided_update_kernel,
+    // so flipping it makes the captured step graphs stale -- and, sized by the batch like the mask buffers and read through StepState, the
+    // stored LP_N(g) [B,4,L,L], the weights [B] (0: not guided), block sizes [B] and row windows [2][guide_cap], and the staged [n] arrays
+    // of a call (slots | weight | scale | row_from | row_to).  guide_face: the host's copy of "is guided" ([B], empty: none).  Lifetime as
+    // for the masks: every hd_prepare* clears all faces, hd_prepare_slots those it refills.
+    bool guide_on = false;
+    float *guide_lp_dev = nullptr, *guide_w_dev = nullptr;
+    int *guide_n_dev = nullptr, *guide_rows_dev = nullptr, *guide_args_dev = nullptr;
+    int guide_cap = 0;
+    std::vector<char> guide_face;
     int graph_captures = 0;                   // step-graph instantiations of this context (hd_get_option "graph_captures")
     // persistent-stage launches recorded by the last one-step capture of each form (hd_get_option "sample_stage_launches",
     // "sample_face_stage_launches", "rows_stage_launches"); stage_count / face_stage_count count while a capture runs

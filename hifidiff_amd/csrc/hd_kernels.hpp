@@ -46,6 +46,14 @@ struct StepState {
     int* pv_row;
     float* pv_snap;
     int pv_every, pv_snaps, pv_batch;
+    // low-pass fidelity guidance (hd_guide_faces; all NULL while guidance is off or no face of the batch is guided): this chain's
+    // [B_chain,4,L,L] stored LP_N(g_f) and, per face, the weight w_f (0: not guided), the block size N_f and the window [j0_f, j1_f) of rows
+    // of the face's own schedule (j = k - begin_f) on which it is guided.  A guided row's latent update is left to guided_update_kernel.
+    const float* gd_lp;
+    const float* gd_w;
+    const int* gd_n;
+    const int* gd_j0;
+    const int* gd_j1;
 };
 
 // ----------------------------------------------------------------------------------- weight packing
@@ -215,11 +223,23 @@ __device__ __forceinline__ bool st_first(const StepState* st, int f, int k, int 
 // span, step - begin_f -- a request's z does not depend on where its schedule sits in the table; an explicit noise tensor keeps the absolute row.
 // Previews (st->pv_x0 != NULL, hd_preview_config): the estimate p -- x0, blended with the known latent of a masked face in the order of the
 // blend above, so m == 1 gives x0 and m == 0 gives known exactly -- is stored as one more output (StepState::pv_*).  NULL: nothing is read or written.
-template <bool PF = false>
-__device__ __forceinline__ float sched_update(float xv, float e, const float* c, const StepState* st, int step, size_t gi, int n_total,
-                                             size_t li, bool first, int f, unsigned ef, int ll) {
+// is face f guided on row j of its own schedule (hd_guide_faces): uniform over a run, a workgroup of the fused ending launch and a plane
+__device__ __forceinline__ bool st_guided(const StepState* st, int f, int j) {
+    if (!st->gd_w) return false;
+    if (((const __attribute__((address_space(1))) float*)st->gd_w)[f] == 0.f) return false;
+    return j >= ((const __attribute__((address_space(1))) int*)st->gd_j0)[f] && j < ((const __attribute__((address_space(1))) int*)st->gd_j1)[f];
+}
+// The update in two halves.  sched_x0: the denoised estimate of the element.  sched_from_x0: everything after it -- the new latent from an
+// x0 (the row's own, or the guided x0g of guided_update_kernel), the history, the mask blend and the preview store.  sched_update is the
+// two in a row: what the ending kernels run for every face that is not guided on this row.
+__device__ __forceinline__ float sched_x0(float xv, float e, const float* c) {
     float x0 = (xv - c[0] * e) / c[1];
     x0 = fminf(fmaxf(x0, -c[2]), c[2]);
+    return x0;
+}
+template <bool PF = false>
+__device__ __forceinline__ float sched_from_x0(float x0, float xv, float e, const float* c, const StepState* st, int step, size_t gi, int n_total,
+                                              size_t li, bool first, int f, unsigned ef, int ll) {
     float c3 = c[3];
     // a face's first row of a multistep call has no history: the row is taken first-order, h := x0 -- the x0 coefficient becomes c3 + c7
     // (c3 = g (1 + k'), c7 = -g k' in a second-order row: their sum is the first-order g)
@@ -265,6 +285,93 @@ __device__ __forceinline__ float sched_update(float xv, float e, const float* c,
         }
     }
     return r;
+}
+template <bool PF = false>
+__device__ __forceinline__ float sched_update(float xv, float e, const float* c, const StepState* st, int step, size_t gi, int n_total,
+                                             size_t li, bool first, int f, unsigned ef, int ll) {
+    return sched_from_x0<PF>(sched_x0(xv, e, c), xv, e, c, st, step, gi, n_total, li, first, f, ef, ll);
+}
+
+// Low-pass fidelity guidance (hd_guide_faces).  LP_N of one L x L plane: the mean over each of the P x P blocks of N x N elements (P = L/N),
+// upsampled bilinearly back to L x L with align_corners = False -- for output index i in either axis s = max((i + 0.5)/N - 0.5, 0),
+// i0 = floor(s), i1 = min(i0 + 1, P - 1), frac = s - i0.  N = 1 returns the plane bit for bit (frac = 0), N = L its mean everywhere.
+// lp_block_means: the plane sits in LDS (pl); rs [L][P] takes the sums of the N-runs of every row, bm [P][P] the block means (a block's
+// N row sums in row order).  Called by the whole workgroup; bm is complete when it returns.
+__device__ __forceinline__ void lp_block_means(const float* pl, float* rs, float* bm, int L, int N) {
+    const int P = L / N;
+    for (int i = threadIdx.x; i < L * P; i += blockDim.x) {
+        const int y = i / P, bx = i - y * P;
+        float s = 0.f;
+        for (int k = 0; k < N; ++k) s += pl[y * L + bx * N + k];
+        rs[i] = s;
+    }
+    __syncthreads();
+    const float inv = 1.f / (float)(N * N);
+    for (int i = threadIdx.x; i < P * P; i += blockDim.x) {
+        const int by = i / P, bx = i - by * P;
+        float s = 0.f;
+        for (int k = 0; k < N; ++k) s += rs[(by * N + k) * P + bx];
+        bm[i] = s * inv;
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ float lp_bilinear(const float* bm, int P, int N, int y, int x) {
+    const float sy = fmaxf(((float)y + 0.5f) / (float)N - 0.5f, 0.f), sx = fmaxf(((float)x + 0.5f) / (float)N - 0.5f, 0.f);
+    const int y0 = (int)sy, x0 = (int)sx, y1 = min(y0 + 1, P - 1), x1 = min(x0 + 1, P - 1);
+    const float fy = sy - (float)y0, fx = sx - (float)x0;
+    const float top = (1.f - fx) * bm[y0 * P + x0] + fx * bm[y0 * P + x1];
+    const float bot = (1.f - fx) * bm[y1 * P + x0] + fx * bm[y1 * P + x1];
+    return (1.f - fy) * top + fy * bot;
+}
+constexpr int kGuideMaxL = 64;                            // a plane of 64 x 64 fp32 is 16 KB: plane + row sums + block means = 48 KB of LDS
+inline size_t guide_lds_bytes(int L) { return (size_t)3 * L * L * sizeof(float); }
+
+// The guided half of a step, launched right after the ending launch while guidance is switched on (hd_guide_config): one workgroup per
+// (chain-local face, channel) plane.  The ending launch has stored eps and left the latents of a face that is guided on this row alone;
+// here x0 of the plane goes to LDS, is low-passed, pulled towards the stored LP_N(g) by w -- x0g = x0 + w (LP_N(g) - LP_N(x0)) -- and the
+// "from x0" half of the update runs on x0g with the element indices of the ending kernels (gi, li, ef, the Philox counters).  eps is
+// re-derived from x0g (e' = (x - c1 x0g)/c0) where the row uses it (c5 != 0).  A workgroup whose face is not guided on this row, or is
+// held, exits at once; a plane belongs to one workgroup, so nothing is synchronised across workgroups.  The step counter has been advanced
+// by the intro.  PF: the per-face form (hd_sample_rows* / _faces* / _spans).
+struct GuideArgs {
+    float* lat; const float* eps;     // chain-local [B_chain,4,L,L]
+    const float* coef;                // [n_steps][7]
+    const StepState* st;
+    int elem0, n_total, L;
+};
+template <bool PF>
+__global__ __launch_bounds__(256) void guided_update_kernel(const GuideArgs g) {
+    extern __shared__ float guide_lds[];
+    const StepState* st = g.st;
+    if (!st->gd_w) return;
+    const int f = blockIdx.x >> 2, L = g.L, ll = L * L;
+    const int step = st->step;
+    int k = step, r = 0, j = step;
+    if (PF) {
+        r = st_row(st, f); k = r + step;
+        if (k >= st_end(st, f)) return;                   // held
+        j = k - st_begin(st, f);
+    }
+    if (!st_guided(st, f, j)) return;
+    const float w = ((const __attribute__((address_space(1))) float*)st->gd_w)[f];
+    const int N = ((const __attribute__((address_space(1))) int*)st->gd_n)[f], P = L / N;
+    const __attribute__((address_space(1))) float* lpg = (const __attribute__((address_space(1))) float*)st->gd_lp;
+    const float* c = g.coef + (size_t)k * 7;
+    float *pl = guide_lds, *rs = pl + ll, *bm = rs + ll;
+    const size_t o0 = (size_t)blockIdx.x * ll;            // (f * 4 + channel) * L * L: NCHW
+    for (int i = threadIdx.x; i < ll; i += blockDim.x) pl[i] = sched_x0(g.lat[o0 + i], g.eps[o0 + i], c);
+    __syncthreads();
+    lp_block_means(pl, rs, bm, L, N);
+    const bool first = PF ? st_first(st, f, k, r) : false;
+    for (int i = threadIdx.x; i < ll; i += blockDim.x) {
+        const size_t o = o0 + i;
+        const int y = i / L, x = i - y * L;
+        const float xv = g.lat[o];
+        float e = g.eps[o];
+        const float x0g = pl[i] + w * (lpg[o] - lp_bilinear(bm, P, N, y, x));
+        if (c[5] != 0.f) e = (xv - c[1] * x0g) / c[0];
+        g.lat[o] = sched_from_x0<PF>(x0g, xv, e, c, st, k, (size_t)g.elem0 + o, g.n_total, o, first, f, (unsigned)(o - (size_t)f * 4 * ll), ll);
+    }
 }
 static __global__ void ending_weight_layout_kernel(const float* __restrict__ w, float* __restrict__ wT) {   // w[co][ci][tap] -> wT[tap][co][ci]
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -371,10 +478,10 @@ __global__ __launch_bounds__(256) void ending_conv_kernel(const float* __restric
         const int step = sa.st->step;
         if constexpr (PF) {
             const int r = st_row(sa.st, bb), k = r + step;          // the wave's run lies in one face: k is wave-uniform
-            if (k < st_end(sa.st, bb))
+            if (k < st_end(sa.st, bb) && !st_guided(sa.st, bb, k - st_begin(sa.st, bb)))
                 sa.lat[o] = sched_update<true>(sa.lat[o], e, sa.coef + (size_t)k * 7, sa.st, k, (size_t)sa.elem0 + o, sa.n_total, o,
                                                st_first(sa.st, bb, k, r), bb, (unsigned)(o - (size_t)bb * 4 * L * L), L * L);
-        } else {
+        } else if (!st_guided(sa.st, bb, step)) {
             sa.lat[o] = sched_update(sa.lat[o], e, sa.coef + (size_t)step * 7, sa.st, step, (size_t)sa.elem0 + o, sa.n_total, o, false, bb,
                                      (unsigned)(o - (size_t)bb * 4 * L * L), L * L);
         }
@@ -410,6 +517,35 @@ static __global__ void mask_scatter_kernel(const MaskScatterP p) {
         p.dknown[(size_t)slot * 4 * p.ll + i] = p.known[(size_t)j * 4 * p.ll + i];
         p.dnoise[(size_t)slot * 4 * p.ll + i] = p.noise[(size_t)j * 4 * p.ll + i];
     }
+}
+
+// hd_guide_faces: plane (j, channel) of target [n,4,L,L] (grid (4, n)) is low-passed with N = scale[j] and stored for slot slots[j]
+// (slots == NULL: j), and the slot's weight, block size and row window are set from the call's staged arrays; target == NULL sets the
+// slot's weight to 0 (not guided) and leaves the rest.
+struct GuideScatterP {
+    const float* target;
+    float *lp, *w;
+    int *n, *j0, *j1;
+    const int* slots;
+    const float* weight; const int *scale, *row_from, *row_to;   // the call's [n] arrays, on the device
+    int L;
+};
+static __global__ __launch_bounds__(256) void guide_scatter_kernel(const GuideScatterP p) {
+    extern __shared__ float guide_lds[];
+    const int j = blockIdx.y, ch = blockIdx.x, slot = p.slots ? p.slots[j] : j;
+    if (ch == 0 && threadIdx.x == 0) {
+        p.w[slot] = p.target ? p.weight[j] : 0.f;
+        if (p.target) { p.n[slot] = p.scale[j]; p.j0[slot] = p.row_from[j]; p.j1[slot] = p.row_to[j]; }
+    }
+    if (!p.target) return;
+    const int L = p.L, ll = L * L, N = p.scale[j], P = L / N;
+    float *pl = guide_lds, *rs = pl + ll, *bm = rs + ll;
+    const float* src = p.target + ((size_t)j * 4 + ch) * ll;
+    float* dst = p.lp + ((size_t)slot * 4 + ch) * ll;
+    for (int i = threadIdx.x; i < ll; i += blockDim.x) pl[i] = src[i];
+    __syncthreads();
+    lp_block_means(pl, rs, bm, L, N);
+    for (int i = threadIdx.x; i < ll; i += blockDim.x) dst[i] = lp_bilinear(bm, P, N, i / L, i - (i / L) * L);
 }
 
 // Progress previews (hd_preview_config).  ll4 = 4*L*L.  preview_reset_kernel (hd_prepare_slots): slot slots[j] (j < n = gridDim.y) has no

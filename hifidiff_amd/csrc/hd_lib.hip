@@ -308,7 +308,8 @@ int build_denoiser_program(hd_ctx* c) {
             sa.film_cur = mode_is_rows(c->mode) ? c->film_pf + (size_t)chp->face0 * c->film_total : chp->film_cur;
             return sa;
         };
-        prog.push_back({"ending", [=](hipStream_t s) -> hipError_t {
+        // the ending launch; while guidance is switched on (hd_guide_config) the loop's step ends with guided_update_kernel behind it
+        auto ending_run = [=](hipStream_t s) -> hipError_t {
                             const bool rows = mode_is_rows(c->mode);
                             if (fuse_end && c->end_fused) {
                                 EndP q = ep;
@@ -331,6 +332,16 @@ int build_denoiser_program(hd_ctx* c) {
                             if (mode_is_loop(c->mode)) nb += (unsigned)((c->film_total / 4 + 255) / 256);
                             if (long_runs) hipLaunchKernelGGL(ending_conv_kernel<16>, dim3(nb), dim3(256), 0, s, X, w, b, eps, B, L, sa);
                             else hipLaunchKernelGGL(ending_conv_kernel<kEndingPx>, dim3(nb), dim3(256), 0, s, X, w, b, eps, B, L, sa);
+                            return hipGetLastError();
+                        };
+        prog.push_back({"ending", [=](hipStream_t s) -> hipError_t {
+                            const hipError_t e = ending_run(s);
+                            if (e != hipSuccess || !c->guide_on || !mode_is_loop(c->mode)) return e;
+                            const SchedArgs sa = sched_args();
+                            GuideArgs g{};
+                            g.lat = sa.lat; g.eps = eps; g.coef = sa.coef; g.st = sa.st; g.elem0 = sa.elem0; g.n_total = sa.n_total; g.L = L;
+                            if (mode_is_rows(c->mode)) hipLaunchKernelGGL(guided_update_kernel<true>, dim3(B * 4), dim3(256), guide_lds_bytes(L), s, g);
+                            else hipLaunchKernelGGL(guided_update_kernel<false>, dim3(B * 4), dim3(256), guide_lds_bytes(L), s, g);
                             return hipGetLastError();
                         }});
         prog.back().out = eps; prog.back().out_elems = (size_t)B * 4 * L * L;
@@ -918,10 +929,23 @@ static int reset_previews(hd_ctx* c, hipStream_t s) {
 }
 static bool previews_ready(const hd_ctx* c) { return c->pv_on && c->pv_x0_dev && c->pv_B == c->ws->B && c->pv_planes == c->pv_snaps; }
 
-// every hd_prepare*: the new batch has no masks and no previews
+static int guided_faces(const hd_ctx* c) {
+    int n = 0;
+    for (char g : c->guide_face) n += g != 0;
+    return n;
+}
+// no face is guided any more (weight 0)
+static int clear_guidance(hd_ctx* c, hipStream_t s) {
+    if (guided_faces(c) > 0) HIPCHECK(c, hipMemsetAsync(c->guide_w_dev, 0, (size_t)c->guide_cap * sizeof(float), s));
+    c->guide_face.clear();
+    return HD_OK;
+}
+
+// every hd_prepare*: the new batch has no masks, no guidance and no previews
 static int clear_masks(hd_ctx* c, hipStream_t s) {
     if (masked_faces(c) > 0) HIPCHECK(c, hipMemsetAsync(c->mask_on_dev, 0, (size_t)c->mask_cap * sizeof(int), s));
     c->mask_face.clear();
+    { const int rc = clear_guidance(c, s); if (rc) return rc; }
     return reset_previews(c, s);
 }
 
@@ -1126,6 +1150,7 @@ static int stage_slots(hd_ctx* c, int* dev, const int32_t* slots, int n, hipStre
     return stage_submit(c, sg, s);
 }
 
+static bool any_guided(const hd_ctx* c) { return c->guide_on && c->guide_face.size() == (size_t)c->ws->B && guided_faces(c) > 0; }   // hd_guide_faces
 static bool any_mask(const hd_ctx* c) { return c->mask_face.size() == (size_t)c->ws->B && masked_faces(c) > 0; }   // hd_mask_faces
 
 static int grow_loop_buffers(hd_ctx* c, const SampleCall& call) {
@@ -1164,12 +1189,12 @@ static int grow_loop_buffers(hd_ctx* c, const SampleCall& call) {
 
 // Schedule and loop state (step = -1: each chain's intro kernel pre-increments) go through the pinned staging buffer, so the caller's
 // host arrays are free on return and nothing here waits for the stream.  Regions, in order: coef [n][7] | timesteps [n] | c7 [n]
-// (multistep) | one StepState (single-step, whole batch, no masks, no previews) or one per chain | the per-face argument block (per-face calls).
+// (multistep) | one StepState (single-step, whole batch, no masks, no guidance, no previews) or one per chain | the per-face argument block (per-face calls).
 static int stage_loop_state(hd_ctx* c, const SampleCall& call, bool upload_timesteps, hipStream_t s) {
     const int n = call.n;
     const bool ms = call.ncoef == 8, pf = call.start_rows != nullptr;
-    const bool mk = any_mask(c), pv = previews_ready(c);
-    const size_t nst = (ms || pf || mk || pv) ? c->ws->chains.size() : 1;
+    const bool mk = any_mask(c), pv = previews_ready(c), gd = any_guided(c);
+    const size_t nst = (ms || pf || mk || pv || gd) ? c->ws->chains.size() : 1;
     StageCursor cur;
     const size_t coef0 = cur.take((size_t)n * 7 * sizeof(float)), ts0 = cur.take((size_t)n * sizeof(float));
     const size_t c70 = cur.take(ms ? (size_t)n * sizeof(float) : 0), st0 = cur.take(nst * sizeof(StepState));
@@ -1211,6 +1236,10 @@ static int stage_loop_state(hd_ctx* c, const SampleCall& call, bool upload_times
             const size_t per_face = (size_t)4 * c->L * c->L;
             st.pv_x0 = c->pv_x0_dev + f0 * per_face; st.pv_snap = c->pv_snap_dev + f0 * per_face; st.pv_row = c->pv_row_dev + f0;
             st.pv_every = c->pv_every; st.pv_snaps = c->pv_snaps; st.pv_batch = c->ws->B;
+        }
+        if (gd) {
+            st.gd_lp = c->guide_lp_dev + f0 * 4 * c->L * c->L; st.gd_w = c->guide_w_dev + f0; st.gd_n = c->guide_n_dev + f0;
+            st.gd_j0 = c->guide_rows_dev + f0; st.gd_j1 = c->guide_rows_dev + c->guide_cap + f0;
         }
         memcpy(host + st0 + k * sizeof(StepState), &st, sizeof(st));
     }
@@ -1571,6 +1600,16 @@ int hd_prepare_slots(hd_ctx* c, int n, const int32_t* slots, const float* cr_lat
             HIPCHECK(c, hipGetLastError());
         }
     }
+    if (c->guide_face.size() == (size_t)c->ws->B) {         // ... no guidance (weight 0)
+        bool any = false;
+        for (int j = 0; j < n; ++j) { any |= c->guide_face[slots[j]] != 0; c->guide_face[slots[j]] = 0; }
+        if (any) {
+            GuideScatterP gp{};
+            gp.w = c->guide_w_dev; gp.slots = c->ws->slots_dev;
+            hipLaunchKernelGGL(guide_scatter_kernel, dim3(1, n), dim3(64), 0, s, gp);
+            HIPCHECK(c, hipGetLastError());
+        }
+    }
     if (previews_ready(c)) {                               // ... and no preview: row -1, zeroed planes
         PreviewP pp{};
         pp.x0 = c->pv_x0_dev; pp.snap = c->pv_snap_dev; pp.rows = c->pv_row_dev; pp.slots = c->ws->slots_dev;
@@ -1637,6 +1676,107 @@ int hd_mask_faces(hd_ctx* c, int n, const int32_t* slots, const float* mask, con
     hipLaunchKernelGGL(mask_scatter_kernel, dim3(mask ? 4 : 1, n), dim3(256), 0, s, p);
     HIPCHECK(c, hipGetLastError());
     for (int j = 0; j < n; ++j) c->mask_face[slots ? slots[j] : j] = mask ? 1 : 0;
+    return HD_OK;
+}
+
+// Low-pass fidelity guidance.  The switch decides whether the captured step ends with guided_update_kernel: flipping it makes the step
+// graphs stale (one recapture at the next loop), and with it off no launch, graph or bit differs from a context that never had it on.
+int hd_guide_config(hd_ctx* c, int on) {
+    if (!c) return HD_ERR_INVALID;
+    if (c->cr || c->vae) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_config: this context holds CoarseRestoration or the VAE (no sampling loop)");
+    if (on != 0 && on != 1) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_config: on = %d is not 0 or 1", on);
+    if (c->guide_on == (on != 0)) return HD_OK;
+    if (!on && guided_faces(c) > 0) {                      // switching off clears every face (the weights in stream order of the null stream)
+        HIPCHECK(c, hipSetDevice(c->device));
+        HIPCHECK(c, hipDeviceSynchronize());               // a loop in flight may still read them
+        const int rc = clear_guidance(c, nullptr);
+        if (rc) return rc;
+        HIPCHECK(c, hipStreamSynchronize(nullptr));
+    }
+    c->guide_face.clear();
+    c->guide_on = on != 0;
+    invalidate_step_graphs(c);                             // the ending op launches one kernel more, or one fewer
+    return HD_OK;
+}
+
+// Guide n faces of the prepared batch towards LP_N of a target (or stop guiding them: target NULL).  LP_N(target) is computed here, once,
+// in stream order, into a buffer of the context that the step kernels reach through StepState, with the faces' weights, block sizes and
+// row windows: no launch program is rebuilt and no graph recaptured by setting, changing or clearing faces.
+int hd_guide_faces(hd_ctx* c, int n, const int32_t* slots, const float* target, const float* weight, const int32_t* scale,
+                   const int32_t* row_from, const int32_t* row_to, void* stream) {
+    if (!c) return HD_ERR_INVALID;
+    if (c->cr || c->vae) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: this context holds CoarseRestoration or the VAE (no sampling loop)");
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    if (n < 1 || n > c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: n = %d outside [1, %d]", n, c->ws->B);
+    if (!slots && n != c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: slots == NULL needs n == batch (%d), got %d", c->ws->B, n);
+    if (slots) {
+        std::vector<char> seen((size_t)c->ws->B, 0);
+        for (int j = 0; j < n; ++j) {
+            if (slots[j] < 0 || slots[j] >= c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: slots[%d] = %d outside [0, %d)", j, slots[j], c->ws->B);
+            if (seen[slots[j]]) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: slot %d given twice", slots[j]);
+            seen[slots[j]] = 1;
+        }
+    }
+    if (target) {
+        if (!c->guide_on) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: guidance is switched off (hd_guide_config(ctx, 1) first)");
+        if (!weight || !scale) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: a target needs weight and scale");
+        if (!row_from != !row_to) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: give row_from and row_to together, or neither (all rows)");
+        if (c->L > kGuideMaxL) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: latent %d is larger than %d", c->L, kGuideMaxL);
+        for (int j = 0; j < n; ++j) {
+            if (!(weight[j] > 0.f && weight[j] <= 1.f)) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: weight[%d] = %g outside (0, 1]", j, (double)weight[j]);
+            if (scale[j] < 1 || scale[j] > c->L || c->L % scale[j] != 0)
+                HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: scale[%d] = %d does not divide the latent size %d", j, scale[j], c->L);
+            if (row_from && !(0 <= row_from[j] && row_from[j] < row_to[j]))
+                HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: rows [%d, %d) of face %d: need 0 <= row_from < row_to", row_from[j], row_to[j], j);
+        }
+    }
+    if (c->guide_face.size() != (size_t)c->ws->B) c->guide_face.assign((size_t)c->ws->B, 0);
+    if (!target && guided_faces(c) == 0) return HD_OK;     // nothing to clear
+    HIPCHECK(c, hipSetDevice(c->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const size_t B = (size_t)c->ws->B, ll = (size_t)c->L * c->L;
+    if (c->ws->B > c->guide_cap) {                         // a larger batch than ever guided: hd_prepare* has cleared every face since
+        dev_free(c, c->guide_lp_dev); dev_free(c, c->guide_w_dev); dev_free(c, c->guide_n_dev); dev_free(c, c->guide_rows_dev); dev_free(c, c->guide_args_dev);
+        c->guide_lp_dev = c->guide_w_dev = nullptr; c->guide_n_dev = c->guide_rows_dev = c->guide_args_dev = nullptr; c->guide_cap = 0;
+        rc = dev_alloc(c, &c->guide_lp_dev, B * 4 * ll);
+        if (!rc) rc = dev_alloc(c, &c->guide_w_dev, B);
+        if (!rc) rc = dev_alloc(c, &c->guide_n_dev, B);
+        if (!rc) rc = dev_alloc(c, &c->guide_rows_dev, 2 * B);
+        if (!rc) rc = dev_alloc(c, &c->guide_args_dev, 5 * B);
+        if (rc) return rc;
+        c->guide_cap = c->ws->B;
+        HIPCHECK(c, hipMemsetAsync(c->guide_lp_dev, 0, B * 4 * ll * sizeof(float), s));
+        HIPCHECK(c, hipMemsetAsync(c->guide_w_dev, 0, B * sizeof(float), s));
+        HIPCHECK(c, hipMemsetAsync(c->guide_n_dev, 0, B * sizeof(int), s));
+        HIPCHECK(c, hipMemsetAsync(c->guide_rows_dev, 0, 2 * B * sizeof(int), s));
+    }
+    // the call's host arrays through the pinned staging buffer: slots | weight | scale | row_from | row_to, [n] each
+    {
+        hd_ctx::Stage* sg;
+        rc = stage_acquire(c, (size_t)5 * n * sizeof(int32_t), &sg);
+        if (rc) return rc;
+        int32_t* h = reinterpret_cast<int32_t*>(sg->host);
+        for (int j = 0; j < n; ++j) {
+            h[j] = slots ? slots[j] : j;
+            const float w = target ? weight[j] : 0.f;
+            memcpy(&h[n + j], &w, sizeof(float));
+            h[2 * n + j] = target ? scale[j] : 1;
+            h[3 * n + j] = (target && row_from) ? row_from[j] : 0;
+            h[4 * n + j] = (target && row_from) ? row_to[j] : 0x7fffffff;
+        }
+        HIPCHECK(c, hipMemcpyAsync(c->guide_args_dev, h, (size_t)5 * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        rc = stage_submit(c, sg, s);
+        if (rc) return rc;
+    }
+    GuideScatterP p{};
+    p.target = target; p.lp = c->guide_lp_dev; p.w = c->guide_w_dev; p.n = c->guide_n_dev;
+    p.j0 = c->guide_rows_dev; p.j1 = c->guide_rows_dev + c->guide_cap;
+    p.slots = c->guide_args_dev; p.weight = reinterpret_cast<const float*>(c->guide_args_dev + n);
+    p.scale = c->guide_args_dev + 2 * n; p.row_from = c->guide_args_dev + 3 * n; p.row_to = c->guide_args_dev + 4 * n; p.L = c->L;
+    hipLaunchKernelGGL(guide_scatter_kernel, dim3(target ? 4 : 1, n), dim3(256), target ? guide_lds_bytes(c->L) : 0, s, p);
+    HIPCHECK(c, hipGetLastError());
+    for (int j = 0; j < n; ++j) c->guide_face[slots ? slots[j] : j] = target ? 1 : 0;
     return HD_OK;
 }
 
@@ -1758,6 +1898,15 @@ int64_t hd_debug_read(hd_ctx* c, const char* name, float* host_out, int64_t max_
             return read_to_host(c, m ? c->mask_dev : mkn ? c->mask_known_dev : c->mask_noise_dev, (size_t)c->ws->B * (m ? ll : 4 * ll), 0, host_out, max_elems);
         }
     }
+    {                                                      // the guidance buffers too (guide_scale: the int32 block sizes as they are, 4 bytes each)
+        const std::string k = name;
+        const bool gl = k == "guide_lp", gw = k == "guide_weight", gs = k == "guide_scale";
+        if (gl || gw || gs) {
+            if (!c->guide_lp_dev || c->ws->B < 1 || c->ws->B > c->guide_cap) HD_FAIL(c, HD_ERR_INVALID, "debug buffer %s: no guidance has been set for this batch", name);
+            return read_to_host(c, gl ? (const void*)c->guide_lp_dev : gw ? (const void*)c->guide_w_dev : (const void*)c->guide_n_dev,
+                                gl ? (size_t)c->ws->B * 4 * c->L * c->L : (size_t)c->ws->B, 0, host_out, max_elems);
+        }
+    }
     {                                                      // the preview planes too (preview_rows: the int32 rows as they are, 4 bytes each)
         const std::string k = name;
         const bool px = k == "x0_preview", pr = k == "preview_rows", ps = k == "preview_snaps";
@@ -1826,6 +1975,8 @@ int hd_get_option(hd_ctx* c, const char* key) {
     if (k == "rows_stage_launches") return c->rows_stages;
     if (k == "masked_faces") return c->mask_face.size() == (size_t)c->ws->B ? masked_faces(c) : 0;   // faces that carry a mask (hd_mask_faces)
     if (k == "preview") return c->pv_on ? 1 : 0;                 // hd_preview_config
+    if (k == "guide") return c->guide_on ? 1 : 0;                // hd_guide_config
+    if (k == "guided_faces") return c->guide_face.size() == (size_t)c->ws->B ? guided_faces(c) : 0;   // faces that are guided (hd_guide_faces)
     if (k == "graph_captures") return c->graph_captures;         // step graphs instantiated by this context (hd_prepare_slots adds none)
     // the folds of the program built for the batch in use (0 before the first call): the decisions build_denoiser_program made, and
     // whether the launch that carries them still runs -- the face-stage entries need the face stages on and a single chain

@@ -97,6 +97,51 @@ def mask_args(mask, known, noise, n, L):
     return mask, known.to(torch.float32), noise.to(torch.float32)
 
 
+def guidance_args(target, weight, scale, rows, n, L):
+    """Argument checks of set_guidance, before any device work: target [n,4,L,L]; weight a float or [n] values, finite and in (0, 1];
+    scale an int or [n] ints, each a divisor N of L; rows None (all rows), a pair (j0, j1) or [n,2] ints with 0 <= j0 < j1, relative to
+    each face's own schedule.  Returns (target fp32 on the device it came from, weight fp32 [n], scale int32 [n], rows int32 [n,2] or
+    None), the last three on the CPU; ValueError otherwise."""
+    if target is None:
+        raise ValueError("guidance needs a target (clear_guidance() stops guiding)")
+    target = torch.as_tensor(target)
+    if tuple(target.shape) != (n, 4, L, L):
+        raise ValueError("target must be (%d,4,%d,%d), got %s" % (n, L, L, tuple(target.shape)))
+    w = torch.as_tensor(weight)
+    if w.dtype == torch.bool or w.dtype.is_complex:
+        raise ValueError("weight must be a float or a [%d] tensor of floats" % n)
+    w = w.detach().to(device="cpu", dtype=torch.float32).flatten()
+    if w.numel() == 1:
+        w = w.expand(n)
+    if w.numel() != n:
+        raise ValueError(f"weight must be a float or a [{n}] tensor, got {w.numel()} values")
+    if not bool(torch.isfinite(w).all()) or bool(((w <= 0) | (w > 1)).any()):
+        raise ValueError("weight must be finite and lie in (0, 1] (clear_guidance() stops guiding a face)")
+    N = torch.as_tensor(scale)
+    if N.dtype.is_floating_point or N.dtype == torch.bool or N.dtype.is_complex:
+        raise ValueError("scale must be an int or a [%d] tensor of ints" % n)
+    N = N.detach().to(device="cpu", dtype=torch.int64).flatten()
+    if N.numel() == 1:
+        N = N.expand(n)
+    if N.numel() != n:
+        raise ValueError(f"scale must be an int or a [{n}] tensor, got {N.numel()} values")
+    if bool(((N < 1) | (N > L)).any()) or bool((L % N.clamp(min=1) != 0).any()):
+        raise ValueError(f"scale must divide the latent size {L}")
+    if rows is not None:
+        r = torch.as_tensor(rows)
+        if r.dtype.is_floating_point or r.dtype == torch.bool or r.dtype.is_complex:
+            raise ValueError("rows must be a pair of ints or a [%d,2] tensor of ints" % n)
+        r = r.detach().to(device="cpu", dtype=torch.int64)
+        if tuple(r.shape) == (2,):
+            r = r[None].expand(n, 2)
+        if tuple(r.shape) != (n, 2):
+            raise ValueError(f"rows must be a pair of ints or a [{n},2] tensor, got {tuple(r.shape)}")
+        if bool((r[:, 0] < 0).any()) or bool((r[:, 0] >= r[:, 1]).any()) or bool((r[:, 1] > 0x7fffffff).any()):
+            raise ValueError("rows must satisfy 0 <= j0 < j1")
+        rows = r.to(torch.int32).contiguous()
+    return target.to(torch.float32), w.contiguous(), N.to(torch.int32).contiguous(), rows
+
+
 def preview_args(every, snapshots):
     """Argument checks of enable_previews, before any device work: ints with every >= 1 and 0 <= snapshots <= 64; ValueError otherwise."""
     for name, v in (("every", every), ("snapshots", snapshots)):
@@ -131,6 +176,27 @@ class _Previews:
         return self._engine.previews(slots, snapshot)
 
 
+class _Guidance:
+    """model.set_guidance / clear_guidance / disable_guidance of both model classes (they share the engine's methods)."""
+
+    def set_guidance(self, target, weight, scale, rows=None, slots=None):
+        """Low-pass fidelity guidance: from now on every sampling.sample call pulls the denoised estimate of the prepared batch's faces in
+        `slots` (None: all, in order) towards `target` [n,4,L,L] in the low frequencies -- x0 <- x0 + w (LP_N(target) - LP_N(x0)) on the rows
+        `rows` = (j0, j1) of each face's own schedule (None: all rows) -- with weight w in (0, 1] (a float or [n]) and block size N = scale,
+        a divisor of L (an int or [n]); sampling.low_pass is LP_N.  Switches guidance on for the model when needed (one recapture of the
+        step graphs); the faces stay guided until clear_guidance, the next prepare of a batch, or prepare_slots of their slot.  ValueError
+        for wrong shapes, a weight outside (0, 1], a scale that does not divide L, or rows without 0 <= j0 < j1."""
+        self._engine.set_guidance(target, weight, scale, rows, slots)
+
+    def clear_guidance(self, slots=None):
+        """Stop guiding the faces in `slots` (None: every face); guidance stays switched on."""
+        self._engine.clear_guidance(slots)
+
+    def disable_guidance(self):
+        """Stop guiding every face and switch guidance off: the step loses its extra launch again (one recapture of the step graphs)."""
+        self._engine.disable_guidance()
+
+
 class _Engine:
     """Owns the hd_ctx of one (latent_res, device)."""
 
@@ -144,6 +210,7 @@ class _Engine:
         self.cond_key = None
         self.batch = None
         self.preview_cfg = None    # (every, snapshots) while previews are on: given to every context this engine creates
+        self.guide_on = False      # hd_guide_config: given to every context this engine creates
 
     def ensure(self, device):
         device = torch.device(device)
@@ -165,6 +232,8 @@ class _Engine:
         _lib.check((L.hd_create if self.conditional else L.hd_create_unconditional)(ctypes.byref(ctx), self.latent_res, idx))
         if self.preview_cfg is not None:
             _lib.check(L.hd_preview_config(ctx, 1, *self.preview_cfg), ctx)
+        if self.guide_on:
+            _lib.check(L.hd_guide_config(ctx, 1), ctx)
         return ctx
 
     def manifest(self):
@@ -296,6 +365,43 @@ class _Engine:
         sp = None if sl is None else ctypes.cast(sl.data_ptr(), ctypes.POINTER(ctypes.c_int32))
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().hd_mask_faces(self.ctx, n, sp, None, None, None, _stream(self.device)), self.ctx)
+
+    def set_guidance(self, target, weight, scale, rows=None, slots=None):
+        """hd_guide_faces: the faces in `slots` (None: the whole prepared batch, in order) are guided from now on -- see
+        FacialRefiner.set_guidance.  Switches hd_guide_config on when it is off."""
+        if self.batch is None:                             # the argument errors come first
+            guidance_args(target, weight, scale, rows, torch.as_tensor(target).shape[0] if target is not None else 0, self.latent_res)
+            raise RuntimeError("no batch is prepared: prepare the batch before guiding it")
+        sl = None if slots is None else slots_arg(slots, self.batch)
+        n = self.batch if sl is None else sl.numel()
+        g, w, N, r = guidance_args(target, weight, scale, rows, n, self.latent_res)
+        self.require_loaded()
+        g = _f32c(g, self.device)
+        i32p = lambda t: None if t is None else ctypes.cast(t.data_ptr(), ctypes.POINTER(ctypes.c_int32))   # noqa: E731
+        r0, r1 = (None, None) if r is None else (r[:, 0].contiguous(), r[:, 1].contiguous())
+        with torch.cuda.device(self.device):
+            if not self.guide_on:
+                _lib.check(_lib.lib().hd_guide_config(self.ctx, 1), self.ctx)
+                self.guide_on = True
+            _lib.check(_lib.lib().hd_guide_faces(self.ctx, n, i32p(sl), g.data_ptr(), ctypes.cast(w.data_ptr(), ctypes.POINTER(ctypes.c_float)),
+                                                 i32p(N), i32p(r0), i32p(r1), _stream(self.device)), self.ctx)
+
+    def clear_guidance(self, slots=None):
+        """Stop guiding the faces in `slots` (None: every face); a no-op without a prepared batch."""
+        if self.batch is None or self.ctx is None:
+            return
+        sl = None if slots is None else slots_arg(slots, self.batch)
+        n = self.batch if sl is None else sl.numel()
+        sp = None if sl is None else ctypes.cast(sl.data_ptr(), ctypes.POINTER(ctypes.c_int32))
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().hd_guide_faces(self.ctx, n, sp, None, None, None, None, None, _stream(self.device)), self.ctx)
+
+    def disable_guidance(self):
+        """hd_guide_config(on = 0): no face is guided and the step has no guided launch."""
+        self.guide_on = False
+        if self.ctx is not None:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().hd_guide_config(self.ctx, 0), self.ctx)
 
     def enable_previews(self, every=1, snapshots=0):
         """hd_preview_config(on = 1): see FacialRefiner.enable_previews.  Before the model has a device only the setting is kept."""
@@ -475,7 +581,7 @@ class FusedDenoiser(_SubModule):
         self._engine.prior_key = None
 
 
-class Denoiser(_Previews, nn.Module):
+class Denoiser(_Previews, _Guidance, nn.Module):
     """The unconditional pre-training network (models/denoiser/model.py:32-134): `model(latents, t).sample`, as the
     sampling loop of pretrain_denoiser.py:101-110 calls it.  State-dict keys are the reference's (no prefix)."""
 
@@ -536,7 +642,7 @@ class Denoiser(_Previews, nn.Module):
         return UNet2DOutput(e.eps(latents, timesteps))
 
 
-class FacialRefiner(_Previews, nn.Module):
+class FacialRefiner(_Previews, _Guidance, nn.Module):
     def __init__(self, latent_res=16, idc_ckpt=None, denoiser_ckpt=None, cache_conditioning=True):
         super().__init__()
         if latent_res % 16 != 0 or latent_res < 16:

@@ -119,6 +119,32 @@ def region_mask(boxes, latent_res, image_res=128, feather=0):
     return m.clamp(0.0, 1.0).to(torch.float32)
 
 
+def low_pass(x, N):
+    """LP_N of the guidance (model.set_guidance): every L x L plane of x [..., L, L] is replaced by the mean over its N x N blocks, upsampled
+    bilinearly back to L x L with align_corners=False -- F.interpolate(F.avg_pool2d(x, N), size=L, mode="bilinear"), in closed form: for
+    output index i in either axis s = max((i + 0.5)/N - 0.5, 0), i0 = floor(s), i1 = min(i0 + 1, P - 1), frac = s - i0 with P = L/N.  N = 1
+    returns x itself (as a copy), N = L the plane mean everywhere.  Any device, any floating dtype; ValueError unless N divides L."""
+    x = torch.as_tensor(x)
+    if x.dim() < 2 or x.shape[-1] != x.shape[-2]:
+        raise ValueError(f"low_pass needs square planes [..., L, L], got {tuple(x.shape)}")
+    if isinstance(N, bool) or not isinstance(N, int):
+        raise ValueError(f"N must be an int, got {N!r}")
+    L = int(x.shape[-1])
+    if N < 1 or L % N != 0:
+        raise ValueError(f"N = {N} does not divide the plane size {L}")
+    if N == 1:
+        return x.clone()
+    P = L // N
+    bm = x.reshape(x.shape[:-2] + (P, N, P, N)).mean(dim=(-3, -1))
+    i = torch.arange(L, device=x.device, dtype=torch.float64)
+    s = ((i + 0.5) / N - 0.5).clamp(min=0.0)
+    i0 = s.floor().long()
+    i1 = (i0 + 1).clamp(max=P - 1)
+    f = (s - i0.to(s.dtype)).to(x.dtype)
+    rows = (1 - f)[:, None] * bm[..., i0, :] + f[:, None] * bm[..., i1, :]           # [..., L, P]
+    return (1 - f) * rows[..., i0] + f * rows[..., i1]
+
+
 class ScheduleSet:
     """Several schedules as one table, for batches whose faces run different step counts or solvers (hd_sample_spans).
 
@@ -191,7 +217,7 @@ class ScheduleSet:
 @torch.no_grad()
 def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, prepare=True, check=True,
            start_steps=None, n_iters=None, resume=False, face_seeds=None, mask=None, known=None, known_noise=None, schedules=None,
-           previews=None):
+           previews=None, guide=None, guide_weight=1.0, guide_scale=4, guide_rows=None):
     """Whole loop on the GPU: returns the final latents (a new tensor).
 
     The scheduler's coefficient table picks the entry point: 7 columns (DDIM / DDPM) -> hd_sample, 8 columns
@@ -219,6 +245,12 @@ def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, pr
     defaults to the longest remaining run, and resume (a bool or a [B] tensor) continues a face's history as above -- it needs
     start_steps[f] > 0.  A face's z counts rows from the start of its own schedule; an explicit noise tensor is indexed by the row of the
     concatenated table ([N, B, 4, L, L]).  With a plain scheduler `schedules` must stay None.
+    guide (low-pass fidelity guidance; None: off): a [B,4,L,L] target -- usually cr_latent -- that every face's denoised estimate is pulled
+    towards in the low frequencies, x0 <- x0 + w (LP_N(guide) - LP_N(x0)) (low_pass is LP_N): guide_weight w in (0, 1] (a float or [B]),
+    guide_scale N, a divisor of L (an int or [B]; 1: every element, L: only each channel's mean), guide_rows (j0, j1) or [B,2]: the rows
+    of each face's own schedule on which it is guided (None: all).  Set on the engine after preparing (model.set_guidance).  guide=None
+    with prepare=True removes any guidance the engine still holds (the conditioning cache can hit without a new prepare); with
+    prepare=False the engine's guidance is left alone (continuous batching, a loop split over calls).
     previews: None, or an int k >= 1: the call also returns every k-th denoised estimate of each face -- (latents, x0_snaps [S,B,4,L,L],
     rows [S,B] int32) with S = ceil(longest schedule / k) (at most 64): x0_snaps[s, f] is face f's x0 of row (s + 1) * k - 1 of its own
     schedule (a masked face: blended with its known latent) and rows[s, f] that row of the table, or zeros and -1 where the face did
@@ -252,6 +284,9 @@ def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, pr
     if mask is not None:
         from .refiner import mask_args
         mask, known, known_noise = mask_args(mask, known, known_noise, B, model.engine.latent_res)
+    if guide is not None:
+        from .refiner import guidance_args
+        guide = guidance_args(guide, guide_weight, guide_scale, guide_rows, B, model.engine.latent_res)
     e = model.engine
     e.ensure(latents.device)
     if B == 0:                                             # empty batch: nothing to sample
@@ -264,6 +299,10 @@ def sample(model, latents, cr_face, cr_latent, scheduler, noise=None, seed=0, pr
         e.set_mask(mask, known, known_noise)
     elif prepare:
         e.clear_mask()
+    if guide is not None:
+        e.set_guidance(*guide)
+    elif prepare and getattr(e, "guide_on", False):        # (an engine that never switched guidance on holds none)
+        e.clear_guidance()
     x = latents.to(device=e.device, dtype=torch.float32).contiguous().clone()
     if previews is None:
         return _run(e, x, scheduler.coefficient_table(), rows, spans, n_iters, resume, face_seeds, noise, seed, check)
@@ -526,7 +565,7 @@ class ContinuousSampler:
         self.sset = scheduler if isinstance(scheduler, ScheduleSet) else None
         self.n_steps = int(scheduler.coefficient_table()[0].numel()) if self.sset else int(scheduler.timesteps.numel())
         self.table = SlotTable(self.batch, self.n_steps)
-        self.queue = []                 # (rid, cr_face, cr_latent, seed, strength, mask, schedule) in submission order
+        self.queue = []                 # (rid, cr_face, cr_latent, seed, strength, mask, fidelity, schedule) in submission order
         self.finished = {}
         self.seeds = [0] * self.batch
         self.x = None                   # [B,4,L,L] device latents of every slot
@@ -535,10 +574,13 @@ class ContinuousSampler:
         self.calls = 0
         self.refilled = 0
 
-    def submit(self, cr_face, cr_latent, seed, strength=1.0, mask=None, schedule=None):
+    def submit(self, cr_face, cr_latent, seed, strength=1.0, mask=None, schedule=None, fidelity=None, fidelity_scale=4, fidelity_rows=None):
         """schedule: the member of the ScheduleSet this request runs (None: the first member; without a set it must stay None).
         mask: None, or [L,L] / [1,L,L] in [0, 1] (1: resample): the request is inpainted -- its known latent is cr_latent, the noise of
         the kept region the z its start is drawn from (inpaint_start; strength 1 starts from pure noise).  Masked and unmasked requests
+        share a batch.
+        fidelity: None, or a weight in (0, 1]: the request is guided towards its own cr_latent (model.set_guidance) with block size
+        fidelity_scale (a divisor of L) on the rows fidelity_rows = (j0, j1) of its own schedule (None: all).  Guided and unguided requests
         share a batch."""
         L = self.L
         if self.sset is None:
@@ -555,6 +597,14 @@ class ContinuousSampler:
             if cr_latent is None:
                 raise ValueError("the refiner needs cr_face and cr_latent")
             mask = mask_args(mask[None] if mask.dim() == 2 else mask, cr_latent[None], cr_latent[None], 1, L)[0][0].cpu()
+        if fidelity is not None:
+            if not self.conditional:
+                raise ValueError("fidelity needs the refiner: the request's target is its cr_latent")
+            if cr_latent is None:
+                raise ValueError("the refiner needs cr_face and cr_latent")
+            from .refiner import guidance_args
+            _, w, N, r = guidance_args(torch.as_tensor(cr_latent)[None], fidelity, fidelity_scale, fidelity_rows, 1, L)
+            fidelity = (float(w[0]), int(N[0]), None if r is None else (int(r[0, 0]), int(r[0, 1])))
         if self.conditional:
             if cr_face is None or cr_latent is None:
                 raise ValueError("the refiner needs cr_face and cr_latent")
@@ -569,7 +619,7 @@ class ContinuousSampler:
             raise ValueError("seed must lie in [0, 2**63)")
         rid = self.next_id
         self.next_id += 1
-        self.queue.append((rid, cr_face, cr_latent, seed, float(strength), mask, schedule))
+        self.queue.append((rid, cr_face, cr_latent, seed, float(strength), mask, fidelity, schedule))
         return rid
 
     def _z(self, seed):
@@ -592,9 +642,9 @@ class ContinuousSampler:
         return lat[0], int(start[0])
 
     def _refill(self, dev):
-        new, masked = [], []
+        new, masked, guided = [], [], []
         while self.queue and self.table.free_slots():
-            rid, crf, crl, seed, strength, mask, schedule = self.queue.pop(0)
+            rid, crf, crl, seed, strength, mask, fidelity, schedule = self.queue.pop(0)
             lat, start = self._start(crl, seed, strength, mask is not None, schedule)
             if self.sset is None:
                 slot = self.table.assign(rid, start)
@@ -606,6 +656,8 @@ class ContinuousSampler:
             new.append((slot, crf, crl))
             if mask is not None:
                 masked.append((slot, mask, crl, self._z(seed)[0]))
+            if fidelity is not None:
+                guided.append((slot, crl, fidelity))
         if not new or not self.conditional:
             return
         slots = [s for s, _, _ in new]
@@ -625,6 +677,11 @@ class ContinuousSampler:
         if masked:                      # after the prepare: it has cleared the masks of the slots it filled
             self.model.set_mask(torch.stack([m for _, m, _, _ in masked]), torch.stack([l.detach().float().cpu() for _, _, l, _ in masked]),
                                 torch.stack([z for _, _, _, z in masked]), slots=[s for s, _, _, _ in masked])
+        if guided:                      # likewise: the prepare has cleared the guidance of the slots it filled
+            big = 0x7fffffff            # "all rows" next to requests that gave a window
+            self.model.set_guidance(torch.stack([l.detach().float().cpu() for _, l, _ in guided]), torch.tensor([f[0] for _, _, f in guided]),
+                                    torch.tensor([f[1] for _, _, f in guided]),
+                                    rows=torch.tensor([f[2] if f[2] is not None else (0, big) for _, _, f in guided]), slots=[s for s, _, _ in guided])
 
     def step(self):
         """Refill free slots from the queue, then run one call of up to refill_every iterations.  Returns the number of iterations."""

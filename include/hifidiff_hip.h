@@ -217,6 +217,35 @@ int hd_sample_spans(hd_ctx* ctx, float* x_inout, const hd_schedule_ms* table, co
  * pointers, or a CoarseRestoration / VAE context. */
 int hd_mask_faces(hd_ctx* ctx, int n, const int32_t* slots, const float* mask, const float* known, const float* known_noise, void* stream);
 
+/* Low-pass fidelity guidance (ILVR's low-pass conditioning; the control CodeFormer calls `w` and DiffBIR `g_scale`): how far a face's result
+ * may drift from a target -- usually its coarse restoration -- in the low frequencies, while the diffusion adds the detail.
+ * hd_guide_config(on): the switch of the context.  While it is on, every step of the loop ends with one small launch more (the guided
+ * update, one workgroup per face and channel plane); flipping it makes the captured step graphs stale, so the next hd_sample* call
+ * recaptures once.  A context that never switches it on keeps its launches, its graphs and its bits.  on = 0 also stops guiding every face.
+ * hd_guide_faces: guide n faces of the prepared batch: slots[j] (host [n], distinct, in [0, B); NULL: n == B, faces in order) is pulled
+ * towards target[j] [4,L,L] (device fp32) with weight[j] in (0, 1] and block size scale[j] = N, a divisor of L (host [n] each), on rows
+ * row_from[j] <= i < row_to[j] of the face's own schedule (host [n], 0 <= row_from < row_to; both NULL: all rows; i = k - begin_f, the row
+ * inside the face's span, begin_f = 0 without hd_sample_spans).  LP_N(target) is computed in stream order by this call and stored: the
+ * caller's tensor is free once the stream has passed the call.  On a guided row k of such a face every hd_sample* call (all seven loop
+ * entry points) computes, with x, eps, c[0..7], h, z as in hd_schedule / hd_schedule_ms,
+ *     x0  = clamp((x - c0*eps)/c1, +-c2)
+ *     x0g = x0 + w * (LP_N(target) - LP_N(x0))                 per channel plane
+ *     e'  = (x - c1*x0g)/c0                                    where the row uses eps (c5 != 0)
+ *     x  <- c3*x0g + c4*x + c5*e' + c6*z + c7*h ;  h <- x0g    (a first-order first row folds c7 into c3, as without guidance)
+ * and the mask blend and the preview store follow as they do without guidance (the preview stores x0g).  LP_N of an L x L plane is the
+ * mean over each N x N block, upsampled bilinearly back to L x L with align_corners = False: F.interpolate(F.avg_pool2d(x, N), size = L,
+ * mode = "bilinear").  N = 1 is the identity (the guidance is element-wise), N = L the plane mean (only each channel's mean is pulled).
+ * target == NULL stops guiding the given faces (weight .. row_to are not read).  Setting, changing or clearing faces captures nothing.
+ * Lifetime as for the masks: the guidance stays across hd_sample* calls, every hd_prepare* clears all faces and hd_prepare_slots those of
+ * the slots it refills.  hd_get_option "guide" returns the switch and "guided_faces" the number of guided faces; hd_debug_read names
+ * "guide_lp" [B,4,L,L] (the stored LP_N(target)), "guide_weight" [B] (0: not guided) and "guide_scale" [B] (int32 bits) read the buffers.
+ * hd_eps and hd_scheduler_step* know no guidance.  HD_ERR_NOT_READY without a prepared batch; HD_ERR_INVALID for a duplicate or
+ * out-of-range slot, n outside [1, B], slots == NULL with n != B, a target while the switch is off, a weight outside (0, 1] or not finite,
+ * a scale that does not divide L, row_from >= row_to or row_from < 0, only one of row_from / row_to, or a CoarseRestoration / VAE context. */
+int hd_guide_config(hd_ctx* ctx, int on);
+int hd_guide_faces(hd_ctx* ctx, int n, const int32_t* slots, const float* target, const float* weight, const int32_t* scale,
+                   const int32_t* row_from, const int32_t* row_to, void* stream);
+
 /* Progress previews: the denoised estimate of the row a face last ran, as an output of the sampling loop (diffusers'
  * `pred_original_sample` / `callback_on_step_end`).
  * hd_preview_config(on = 1, every, snapshots): from the next hd_prepare* on -- at once, when a batch is prepared -- the context owns the
