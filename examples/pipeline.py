@@ -43,6 +43,9 @@ def main():
                     help="continuous batching: N synthetic requests with strengths in [0.2, 1.0] through sampling.ContinuousSampler "
                          "(--batch slots), then VAE decode")
     ap.add_argument("--refill-every", type=int, default=5, metavar="K", help="--stream: iterations per call between refills")
+    ap.add_argument("--prefetch", type=int, default=0, metavar="P",
+                    help="--stream: prepare the conditioning of up to P queued requests ahead, in one call, and refill slots by copy "
+                         "(sampling.ContinuousSampler(prefetch=P), hd_pool_prepare / hd_pool_commit; 0: prepare at every refill)")
     ap.add_argument("--steps-mix", default=None, metavar="N1,N2,..",
                     help="--stream: per-request schedules -- the requests cycle through these step counts of --scheduler, all in the same "
                          "slots (sampling.ScheduleSet, hd_sample_spans)")
@@ -89,6 +92,10 @@ def main():
 
     if a.steps_mix and a.stream is None:
         ap.error("--steps-mix needs --stream")
+    if a.prefetch and a.stream is None:
+        ap.error("--prefetch needs --stream")
+    if a.prefetch < 0:
+        ap.error("--prefetch must be >= 0")
     if a.stream is not None:
         return stream(a, cr, vae, model, sch, steps, dev)
 
@@ -136,7 +143,8 @@ def main():
 
 def stream(a, cr, vae, model, sch, steps, dev):
     """N requests, each with its own seed and strength, through the serving loop: a finished face leaves its slot and the next request
-    takes it (FacialRefiner.prepare_slots), so no slot waits for the slowest face of a batch."""
+    takes it (FacialRefiner.prepare_slots; with --prefetch its conditioning was prepared ahead, together with that of the requests queued
+    behind it, and FacialRefiner.pool_commit copies it in), so no slot waits for the slowest face of a batch."""
     N = a.stream
     g = torch.Generator().manual_seed(3)
     strength = (0.2 + 0.8 * torch.rand(N, generator=g)).tolist()
@@ -158,7 +166,8 @@ def stream(a, cr, vae, model, sch, steps, dev):
             s.set_timesteps(n)
         sch, steps = sampling.ScheduleSet(members), a.steps_mix
         pick = [counts[i % len(counts)] for i in range(N)]
-    cs = sampling.ContinuousSampler(model, sch, batch=a.batch, refill_every=a.refill_every, previews=a.preview_every is not None)
+    cs = sampling.ContinuousSampler(model, sch, batch=a.batch, refill_every=a.refill_every, previews=a.preview_every is not None,
+                                    prefetch=a.prefetch)
     torch.cuda.synchronize(); t1 = time.time()
     fid = {} if a.fidelity is None else dict(fidelity=a.fidelity, fidelity_scale=a.fidelity_scale, fidelity_rows=a.fid_rows)
     ids = [cs.submit(f, l, seed=1000 + i, strength=strength[i], mask=a.mask, **fid, **({"schedule": pick[i]} if a.steps_mix else {}))
@@ -180,7 +189,7 @@ def stream(a, cr, vae, model, sch, steps, dev):
     torch.cuda.synchronize(); t3 = time.time()
     print(f"stream of {N} requests (strength 0.2..1.0), {a.batch} slots, refill every {a.refill_every}: coarse restoration + VAE encode "
           f"{1e3 * (t1 - t0):.1f} ms, {steps}-step {a.scheduler} {1e3 * (t2 - t1):.1f} ms ({N / (t2 - t1):.1f} faces/s, {cs.calls} calls, "
-          f"{cs.refilled} slots refilled), VAE decode {1e3 * (t3 - t2):.1f} ms; images {tuple(images.shape)} finite "
+          f"{cs.refilled} slots refilled{f', {cs.pool_prepared} of them prepared ahead in {cs.pool_calls} calls' if a.prefetch else ''}), VAE decode {1e3 * (t3 - t2):.1f} ms; images {tuple(images.shape)} finite "
           f"{bool(torch.isfinite(images).all())}")
 
 

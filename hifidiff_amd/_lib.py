@@ -39,6 +39,7 @@ def unit_deps(unit):
 EXPORTS = [
     "hd_create", "hd_create_unconditional", "hd_prepare_unconditional", "hd_cr_create", "hd_cr_forward", "hd_vae_create", "hd_vae_encode", "hd_vae_decode", "hd_destroy", "hd_last_error", "hd_load_weights", "hd_finalize_weights", "hd_prepare",
     "hd_prepare_from_priors", "hd_fpg", "hd_idc", "hd_eps", "hd_sample", "hd_sample_multistep", "hd_sample_rows", "hd_sample_rows_multistep", "hd_prepare_slots",
+    "hd_pool_config", "hd_pool_prepare", "hd_pool_commit",
     "hd_sample_faces", "hd_sample_faces_multistep", "hd_sample_spans", "hd_mask_faces", "hd_guide_config", "hd_guide_faces", "hd_preview_config", "hd_preview_read", "hd_scheduler_step",
     "hd_scheduler_step_multistep", "hd_num_ops", "hd_num_chains",
     "hd_debug_limit_ops", "hd_debug_op_name", "hd_debug_read_op", "hd_debug_read", "hd_debug_write", "hd_set_option", "hd_get_option", "hd_check",
@@ -124,6 +125,9 @@ def lib():
     L.hd_sample_rows.argtypes = [vp, vp, ctypes.POINTER(Schedule), vp, i32, vp, u64, vp]
     L.hd_sample_rows_multistep.argtypes = [vp, vp, ctypes.POINTER(ScheduleMS), vp, i32, i32, vp, u64, vp]
     L.hd_prepare_slots.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_int32), vp, vp, vp, vp]
+    L.hd_pool_config.argtypes = [vp, i32]
+    L.hd_pool_prepare.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_int32), vp, vp, vp, vp]
+    L.hd_pool_commit.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), vp]
     L.hd_sample_faces.argtypes = [vp, vp, ctypes.POINTER(Schedule), ctypes.POINTER(ctypes.c_int32), i32, ctypes.POINTER(u64), vp, u64, vp]
     L.hd_sample_faces_multistep.argtypes = [vp, vp, ctypes.POINTER(ScheduleMS), ctypes.POINTER(ctypes.c_int32), i32, ctypes.POINTER(ctypes.c_int32),
                                             ctypes.POINTER(u64), vp, u64, vp]

@@ -163,7 +163,8 @@ struct Workspace {
     float *lat = nullptr, *eps = nullptr;    // [B,4,L,L] of the whole batch; chains own contiguous face ranges
     float* x0_hist = nullptr;                // [B,4,L,L]: previous step's x0 of a multistep schedule (hd_sample_multistep)
     // hd_prepare_slots: a private chain of capacity B (allocated on first use) on which the conditioning prologue runs at batch n,
-    // and the [B] device list of the slots it is scattered to
+    // and the [2B] device lists of a call: the slots it is scattered to (hd_prepare_slots), the pool entries it is stored in
+    // (hd_pool_prepare), or the slots followed by the entries they are filled from (hd_pool_commit) -- one upload per call
     Chain slot_stage;
     bool slot_stage_ok = false;
     int* slots_dev = nullptr;
@@ -359,6 +360,16 @@ struct hd_ctx {
     double last_loop_ms = 0.0;
     int last_steps = 0;
     std::map<std::string, std::pair<void*, std::pair<size_t, int>>> dbg;   // context-lifetime names (film, temb); hd_debug_read looks in Workspace::dbg first
+
+    // conditioning pool (hd_pool_config): pool_cap entries, each one face's conditioning in the staging chain's layout -- buffer b of
+    // CondCopyP order (5 x (prior, w_c, w_s), idc term, id_emb) is pool_buf[b] [pool_cap][pool_sz[b]], all in the one allocation
+    // pool_dev, every buffer 16-byte aligned.  The sizes depend on L only, so the pool is the context's: it outlives hd_prepare* and
+    // parked workspaces.  pool_ok[e]: entry e holds a prepared face (hd_pool_prepare sets it, hd_pool_config clears all).
+    int pool_cap = 0;
+    float* pool_dev = nullptr;
+    float* pool_buf[kSlotBufs] = {};
+    int pool_sz[kSlotBufs] = {};
+    std::vector<char> pool_ok;
 };
 
 // The FiLM rows a denoiser LayerNorm of chain chp reads in the context's mode (the table above), and the one way a launch closure puts

@@ -567,23 +567,36 @@ static __global__ void preview_gather_kernel(const PreviewReadP p) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < p.ll4; i += gridDim.x * blockDim.x) p.out[(size_t)j * p.ll4 + i] = p.plane[(size_t)slot * p.ll4 + i];
 }
 
-// hd_prepare_slots: copy face j (< n) of the n-face conditioning (the staging chain's buffers: 5 priors NHWC, 5 w_c, 5 w_s, the idc term and
-// id_emb, face-contiguous with sz[b] floats per face) to slot slots[j] of the batch: chain slots[j] / faces_per_chain, face slots[j] % faces_per_chain
-// of that chain.  grid (x, n, kSlotBufs); the slots are checked on the host (distinct, in [0, B)).
+// The one copy of per-face conditioning (hd_prepare_slots, hd_pool_prepare, hd_pool_commit).  A face's conditioning is kSlotBufs buffers --
+// 5 priors NHWC, 5 w_c, 5 w_s, the idc term and id_emb -- each face-contiguous with sz[b] floats per face (1 float: w_s of a 1 x 1 level;
+// 32768 S^2: prior 4).  Face j (< n) of the call is read from face src_idx[j] of src (src_idx NULL: face j -- the staging chain's n
+// faces in order) and written to dst_idx[j]: with faces_per_chain > 0 a slot of the batch (chain dst_idx[j] / faces_per_chain, face
+// dst_idx[j] % faces_per_chain of that chain), with faces_per_chain == 0 an entry of the conditioning pool (dst[0]).  grid (x, n,
+// kSlotBufs); the lists are checked on the host (in range; destinations distinct).  16 bytes per lane where the per-face size and both
+// face addresses allow it; the small gates (sizes that are no multiple of 4) take the scalar loop.
 constexpr int kSlotBufs = 17, kSlotChains = 8;
-struct SlotScatterP {
+struct CondCopyP {
     const float* src[kSlotBufs];
     float* dst[kSlotChains][kSlotBufs];
     int sz[kSlotBufs];
-    const int* slots;
+    const int* src_idx;
+    const int* dst_idx;
     int faces_per_chain;
 };
-static __global__ __launch_bounds__(256) void slot_scatter_kernel(const SlotScatterP p) {
+static __global__ __launch_bounds__(256) void cond_copy_kernel(const CondCopyP p) {
     const int j = blockIdx.y, b = blockIdx.z, sz = p.sz[b];
-    const int slot = p.slots[j], ch = slot / p.faces_per_chain, f = slot - ch * p.faces_per_chain;
-    const float* __restrict__ src = p.src[b] + (size_t)j * sz;
+    const int from = p.src_idx ? p.src_idx[j] : j, to = p.dst_idx[j];
+    const int ch = p.faces_per_chain ? to / p.faces_per_chain : 0, f = to - ch * p.faces_per_chain;
+    const float* __restrict__ src = p.src[b] + (size_t)from * sz;
     float* __restrict__ dst = p.dst[ch][b] + (size_t)f * sz;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < sz; i += gridDim.x * blockDim.x) dst[i] = src[i];
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, nt = gridDim.x * blockDim.x;
+    if ((sz & 3) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {
+        const float4* __restrict__ s4 = reinterpret_cast<const float4*>(src);
+        float4* __restrict__ d4 = reinterpret_cast<float4*>(dst);
+        for (int i = t; i < sz / 4; i += nt) d4[i] = s4[i];
+    } else {
+        for (int i = t; i < sz; i += nt) dst[i] = src[i];
+    }
 }
 
 // ----------------------------------------------------------------------- depthwise 3x3 + gate + pool

@@ -1521,36 +1521,40 @@ int hd_sample_spans(hd_ctx* c, float* x_inout, const hd_schedule_ms* table, cons
     return sample_impl(c, x_inout, call, stream);
 }
 
-// Replace the conditioning of n slots.  The prologue (FPG, ResNet-50 or the given embedding, HCA gates, idc_conv) runs at batch n on the
-// workspace's private staging chain -- the same launches hd_prepare issues for a batch of n, so the n faces' conditioning is bit for bit
-// that of hd_prepare(n) -- and slot_scatter_kernel copies it into the slots.  Nothing of the batch's chains is rebuilt, parked or
-// recaptured; only the refilled slots' buffers are written.
-int hd_prepare_slots(hd_ctx* c, int n, const int32_t* slots, const float* cr_latent, const float* cr_face, const float* id_emb, void* stream) {
-    if (!c) return HD_ERR_INVALID;
-    if (c->cr || c->vae || !c->conditional)
-        HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: this context holds the unconditional Denoiser, CoarseRestoration or the VAE (no conditioning)");
-    int rc = check_ready(c, true);
-    if (rc) return rc;
-    if (n < 1 || n > c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: n = %d outside [1, %d]", n, c->ws->B);
-    if (!slots || !cr_latent || (!cr_face == !id_emb))
-        HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: need slots, cr_latent and exactly one of cr_face / id_emb");
-    {
-        std::vector<char> seen((size_t)c->ws->B, 0);
-        for (int j = 0; j < n; ++j) {
-            if (slots[j] < 0 || slots[j] >= c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: slots[%d] = %d outside [0, %d)", j, slots[j], c->ws->B);
-            if (seen[slots[j]]) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: slot %d given twice", slots[j]);
-            seen[slots[j]] = 1;
-        }
+// Continuous batching: hd_prepare_slots, hd_pool_prepare and hd_pool_commit are made of the same four pieces.
+// check_index_list: a host list `what` of n indices in [0, limit), distinct where asked for.
+static int check_index_list(hd_ctx* c, const char* fn, const char* what, const int32_t* v, int n, int limit, bool distinct) {
+    std::vector<char> seen(distinct ? (size_t)limit : 0, 0);
+    for (int j = 0; j < n; ++j) {
+        if (v[j] < 0 || v[j] >= limit) HD_FAIL(c, HD_ERR_INVALID, "%s: %s[%d] = %d outside [0, %d)", fn, what, j, v[j], limit);
+        if (!distinct) continue;
+        if (seen[v[j]]) HD_FAIL(c, HD_ERR_INVALID, "%s: %s holds %d twice", fn, what, v[j]);
+        seen[v[j]] = 1;
     }
-    if (c->ws->chains.size() > (size_t)kSlotChains) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: more than %d chains", kSlotChains);
-    HIPCHECK(c, hipSetDevice(c->device));
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    return HD_OK;
+}
+// The index lists of a call to ws->slots_dev in one upload: a [n], then b [n] (b may be NULL).  The caller's arrays are free on return.
+static int stage_index_lists(hd_ctx* c, const int32_t* a, const int32_t* b, int n, hipStream_t s) {
+    if (!c->ws->slots_dev) {
+        const int rc = ws_alloc(c, &c->ws->slots_dev, (size_t)2 * c->ws->B);
+        if (rc) return rc;
+    }
+    if (!b) return stage_slots(c, c->ws->slots_dev, a, n, s);
+    std::vector<int32_t> both((size_t)2 * n);
+    memcpy(both.data(), a, (size_t)n * sizeof(int32_t));
+    memcpy(both.data() + n, b, (size_t)n * sizeof(int32_t));
+    return stage_slots(c, c->ws->slots_dev, both.data(), 2 * n, s);
+}
+// The conditioning prologue (FPG, ResNet-50 or the given embedding, HCA gates, idc_conv) of n faces at batch n on the workspace's
+// private staging chain -- the same launches hd_prepare issues for a batch of n, so the staging chain then holds bit for bit the
+// conditioning hd_prepare(n) computes.  Nothing of the batch's chains is read or written.
+static int stage_prologue(hd_ctx* c, int n, const float* cr_latent, const float* cr_face, const float* id_emb, hipStream_t s) {
     Chain& sc = c->ws->slot_stage;
+    int rc;
     if (!c->ws->slot_stage_ok) {                               // first refill of this workspace: its buffers join the workspace's allocations
         sc = Chain();
         sc.index = -1; sc.B = c->ws->B; sc.face0 = 0;          // index -1: no introspection names (those stay on chain 0)
         rc = alloc_chain(c, sc);
-        if (!rc) rc = ws_alloc(c, &c->ws->slots_dev, (size_t)c->ws->B);
         if (rc) { destroy_chain_queue(sc); return rc; }
         c->ws->slot_stage_ok = true;
     }
@@ -1566,30 +1570,49 @@ int hd_prepare_slots(hd_ctx* c, int n, const int32_t* slots, const float* cr_lat
         add_idc_term(c, prog);
     }
     if (!cr_face) HIPCHECK(c, hipMemcpyAsync(sc.id_emb, id_emb, (size_t)n * 2048 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    rc = run_ops(c, prog, s);
-    if (rc) return rc;
-    rc = stage_slots(c, c->ws->slots_dev, slots, n, s);
-    if (rc) return rc;
-    SlotScatterP p{};
+    return run_ops(c, prog, s);
+}
+// The kSlotBufs conditioning buffers of a chain in CondCopyP order, and their per-face sizes (they depend on L only).
+static void cond_buffers(const Chain& ch, float* out[kSlotBufs]) {
+    int b = 0;
+    for (int i = 0; i < 5; ++i) { out[b++] = ch.prior[i]; out[b++] = ch.gate_c[i]; out[b++] = ch.gate_s[i]; }
+    out[b++] = ch.idc_term; out[b++] = ch.id_emb;
+}
+static void cond_sizes(const hd_ctx* c, int sz[kSlotBufs]) {
     int b = 0;
     for (int i = 0; i < 5; ++i) {
-        const Level& lv = sc.lv[4 - i];
-        const int sz[3] = {lv.H * lv.H * lv.C, lv.C, lv.H * lv.H};      // prior i (NHWC), w_c, w_s per face
-        float* const srcs[3] = {sc.prior[i], sc.gate_c[i], sc.gate_s[i]};
-        for (int q = 0; q < 3; ++q, ++b) {
-            p.src[b] = srcs[q]; p.sz[b] = sz[q];
-            for (size_t k = 0; k < c->ws->chains.size(); ++k) p.dst[k][b] = q == 0 ? c->ws->chains[k].prior[i] : q == 1 ? c->ws->chains[k].gate_c[i] : c->ws->chains[k].gate_s[i];
-        }
+        const int C = WIDTH << (4 - i), H = c->L >> (4 - i);    // prior i belongs to level 4 - i (coarsest first)
+        sz[b++] = H * H * C; sz[b++] = C; sz[b++] = H * H;      // prior i (NHWC), w_c, w_s per face
     }
-    p.src[b] = sc.idc_term; p.sz[b] = 2048 * c->S * c->S;
-    for (size_t k = 0; k < c->ws->chains.size(); ++k) p.dst[k][b] = c->ws->chains[k].idc_term;
-    ++b;
-    p.src[b] = sc.id_emb; p.sz[b] = 2048;
-    for (size_t k = 0; k < c->ws->chains.size(); ++k) p.dst[k][b] = c->ws->chains[k].id_emb;
-    p.slots = c->ws->slots_dev; p.faces_per_chain = c->ws->chains[0].B;
-    hipLaunchKernelGGL(slot_scatter_kernel, dim3(32, n, kSlotBufs), dim3(256), 0, s, p);
+    sz[b++] = 2048 * c->S * c->S; sz[b++] = 2048;
+}
+enum class CondEnd { Staging, Pool, Slots };
+// One cond_copy_kernel launch for the n faces of a call: from the staging chain (face j) or the pool (entry src_idx[j]) to the pool
+// (entry dst_idx[j]) or the batch's slots (slot dst_idx[j]); the lists are on the device already (stage_index_lists).
+static int copy_conditioning(hd_ctx* c, int n, CondEnd from, const int* src_idx, CondEnd to, const int* dst_idx, hipStream_t s) {
+    CondCopyP p{};
+    cond_sizes(c, p.sz);
+    float* bufs[kSlotBufs];
+    if (from == CondEnd::Staging) cond_buffers(c->ws->slot_stage, bufs);
+    for (int b = 0; b < kSlotBufs; ++b) p.src[b] = from == CondEnd::Staging ? bufs[b] : c->pool_buf[b];
+    if (to == CondEnd::Pool) {
+        for (int b = 0; b < kSlotBufs; ++b) p.dst[0][b] = c->pool_buf[b];
+        p.faces_per_chain = 0;
+    } else {
+        for (size_t k = 0; k < c->ws->chains.size(); ++k) {
+            cond_buffers(c->ws->chains[k], bufs);
+            for (int b = 0; b < kSlotBufs; ++b) p.dst[k][b] = bufs[b];
+        }
+        p.faces_per_chain = c->ws->chains[0].B;
+    }
+    p.src_idx = src_idx; p.dst_idx = dst_idx;
+    hipLaunchKernelGGL(cond_copy_kernel, dim3(32, n, kSlotBufs), dim3(256), 0, s, p);
     HIPCHECK(c, hipGetLastError());
-    // the refilled faces carry no mask (their flags are cleared in stream order; the slot list is on the device already)
+    return HD_OK;
+}
+// What a slot loses when it is given a new face: its mask, its guidance, its previews and its multistep history.  The slot list is
+// on the device already (the first n of ws->slots_dev); the flags are cleared in stream order.
+static int reset_slots(hd_ctx* c, int n, const int32_t* slots, hipStream_t s) {
     if (c->mask_face.size() == (size_t)c->ws->B) {
         bool any = false;
         for (int j = 0; j < n; ++j) { any |= c->mask_face[slots[j]] != 0; c->mask_face[slots[j]] = 0; }
@@ -1622,6 +1645,103 @@ int hd_prepare_slots(hd_ctx* c, int n, const int32_t* slots, const float* cr_lat
         for (int j = 0; j < n; ++j) c->hist_face[slots[j]] = 0;
     c->hist_valid = false;
     return HD_OK;
+}
+// The checks the three entry points share: a conditional context with a prepared batch (and, for the pool calls, a pool).
+static int slots_enter(hd_ctx* c, const char* fn, bool need_pool) {
+    if (!c) return HD_ERR_INVALID;
+    if (c->cr || c->vae || !c->conditional)
+        HD_FAIL(c, HD_ERR_INVALID, "%s: this context holds the unconditional Denoiser, CoarseRestoration or the VAE (no conditioning)", fn);
+    const int rc = check_ready(c, true);
+    if (rc) return rc;
+    if (need_pool && c->pool_cap == 0) HD_FAIL(c, HD_ERR_NOT_READY, "%s: no pool is configured (hd_pool_config)", fn);
+    return HD_OK;
+}
+
+// Replace the conditioning of n slots.  The prologue runs at batch n on the workspace's private staging chain, so the n faces'
+// conditioning is bit for bit that of hd_prepare(n), and cond_copy_kernel copies it straight into the slots.  Nothing of the batch's
+// chains is rebuilt, parked or recaptured; only the refilled slots' buffers are written.
+int hd_prepare_slots(hd_ctx* c, int n, const int32_t* slots, const float* cr_latent, const float* cr_face, const float* id_emb, void* stream) {
+    int rc = slots_enter(c, "hd_prepare_slots", false);
+    if (rc) return rc;
+    if (n < 1 || n > c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: n = %d outside [1, %d]", n, c->ws->B);
+    if (!slots || !cr_latent || (!cr_face == !id_emb))
+        HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: need slots, cr_latent and exactly one of cr_face / id_emb");
+    rc = check_index_list(c, "hd_prepare_slots", "slots", slots, n, c->ws->B, true);
+    if (rc) return rc;
+    if (c->ws->chains.size() > (size_t)kSlotChains) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_slots: more than %d chains", kSlotChains);
+    HIPCHECK(c, hipSetDevice(c->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    rc = stage_prologue(c, n, cr_latent, cr_face, id_emb, s);
+    if (!rc) rc = stage_index_lists(c, slots, nullptr, n, s);
+    if (!rc) rc = copy_conditioning(c, n, CondEnd::Staging, nullptr, CondEnd::Slots, c->ws->slots_dev, s);
+    if (!rc) rc = reset_slots(c, n, slots, s);
+    return rc;
+}
+
+// The conditioning pool: `capacity` entries of one face's conditioning each (0: none).  Every entry is invalid afterwards.
+int hd_pool_config(hd_ctx* c, int capacity) {
+    if (!c) return HD_ERR_INVALID;
+    if (c->cr || c->vae || !c->conditional)
+        HD_FAIL(c, HD_ERR_INVALID, "hd_pool_config: this context holds the unconditional Denoiser, CoarseRestoration or the VAE (no conditioning)");
+    if (capacity < 0 || capacity > 4096) HD_FAIL(c, HD_ERR_INVALID, "hd_pool_config: capacity = %d outside [0, 4096]", capacity);
+    HIPCHECK(c, hipSetDevice(c->device));
+    if (c->pool_dev) {                                     // copies that read or write the old pool may still be in flight
+        HIPCHECK(c, hipDeviceSynchronize());
+        dev_free(c, c->pool_dev);
+    }
+    c->pool_dev = nullptr; c->pool_cap = 0; c->pool_ok.clear();
+    for (int b = 0; b < kSlotBufs; ++b) c->pool_buf[b] = nullptr;
+    if (capacity == 0) return HD_OK;
+    cond_sizes(c, c->pool_sz);
+    size_t off[kSlotBufs], total = 0;
+    for (int b = 0; b < kSlotBufs; ++b) { off[b] = total; total += ((size_t)capacity * c->pool_sz[b] + 3) / 4 * 4; }   // every buffer starts 16-byte aligned
+    const int rc = dev_alloc(c, &c->pool_dev, total);
+    if (rc) { c->pool_dev = nullptr; return rc; }
+    for (int b = 0; b < kSlotBufs; ++b) c->pool_buf[b] = c->pool_dev + off[b];
+    c->pool_cap = capacity;
+    c->pool_ok.assign((size_t)capacity, 0);
+    return HD_OK;
+}
+
+// The prologue of hd_prepare_slots for n faces, kept: face j goes to pool entry entries[j] instead of a slot.  The running batch is not
+// touched -- no slot buffer, mask, guidance, preview or history flag -- so a loop split around this call gives the bits it gives without it.
+int hd_pool_prepare(hd_ctx* c, int n, const int32_t* entries, const float* cr_latent, const float* cr_face, const float* id_emb, void* stream) {
+    int rc = slots_enter(c, "hd_pool_prepare", true);
+    if (rc) return rc;
+    const int most = c->ws->B < c->pool_cap ? c->ws->B : c->pool_cap;
+    if (n < 1 || n > most) HD_FAIL(c, HD_ERR_INVALID, "hd_pool_prepare: n = %d outside [1, %d] (the batch and the pool's capacity)", n, most);
+    if (!entries || !cr_latent || (!cr_face == !id_emb))
+        HD_FAIL(c, HD_ERR_INVALID, "hd_pool_prepare: need entries, cr_latent and exactly one of cr_face / id_emb");
+    rc = check_index_list(c, "hd_pool_prepare", "entries", entries, n, c->pool_cap, true);
+    if (rc) return rc;
+    HIPCHECK(c, hipSetDevice(c->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    rc = stage_prologue(c, n, cr_latent, cr_face, id_emb, s);
+    if (!rc) rc = stage_index_lists(c, entries, nullptr, n, s);
+    if (!rc) rc = copy_conditioning(c, n, CondEnd::Staging, nullptr, CondEnd::Pool, c->ws->slots_dev, s);
+    if (rc) return rc;
+    for (int j = 0; j < n; ++j) c->pool_ok[entries[j]] = 1;
+    return HD_OK;
+}
+
+// The second half of hd_prepare_slots: slot slots[j] gets a copy of pool entry entries[j] and loses what a refilled slot loses.
+int hd_pool_commit(hd_ctx* c, int n, const int32_t* slots, const int32_t* entries, void* stream) {
+    int rc = slots_enter(c, "hd_pool_commit", true);
+    if (rc) return rc;
+    if (n < 1 || n > c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_pool_commit: n = %d outside [1, %d]", n, c->ws->B);
+    if (!slots || !entries) HD_FAIL(c, HD_ERR_INVALID, "hd_pool_commit: need slots and entries");
+    rc = check_index_list(c, "hd_pool_commit", "slots", slots, n, c->ws->B, true);
+    if (!rc) rc = check_index_list(c, "hd_pool_commit", "entries", entries, n, c->pool_cap, false);
+    if (rc) return rc;
+    for (int j = 0; j < n; ++j)
+        if (!c->pool_ok[entries[j]]) HD_FAIL(c, HD_ERR_INVALID, "hd_pool_commit: entries[%d] = %d was never prepared (hd_pool_prepare)", j, entries[j]);
+    if (c->ws->chains.size() > (size_t)kSlotChains) HD_FAIL(c, HD_ERR_INVALID, "hd_pool_commit: more than %d chains", kSlotChains);
+    HIPCHECK(c, hipSetDevice(c->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    rc = stage_index_lists(c, slots, entries, n, s);
+    if (!rc) rc = copy_conditioning(c, n, CondEnd::Pool, c->ws->slots_dev + n, CondEnd::Slots, c->ws->slots_dev, s);
+    if (!rc) rc = reset_slots(c, n, slots, s);
+    return rc;
 }
 
 // Give n faces of the prepared batch a mask, the known latent and its noise (or take their masks away: all three NULL).  The tensors are
@@ -1977,6 +2097,8 @@ int hd_get_option(hd_ctx* c, const char* key) {
     if (k == "preview") return c->pv_on ? 1 : 0;                 // hd_preview_config
     if (k == "guide") return c->guide_on ? 1 : 0;                // hd_guide_config
     if (k == "guided_faces") return c->guide_face.size() == (size_t)c->ws->B ? guided_faces(c) : 0;   // faces that are guided (hd_guide_faces)
+    if (k == "pool_capacity") return c->pool_cap;                // hd_pool_config
+    if (k == "pool_valid") { int n = 0; for (char v : c->pool_ok) n += v != 0; return n; }   // entries that hold a prepared face
     if (k == "graph_captures") return c->graph_captures;         // step graphs instantiated by this context (hd_prepare_slots adds none)
     // the folds of the program built for the batch in use (0 before the first call): the decisions build_denoiser_program made, and
     // whether the launch that carries them still runs -- the face-stage entries need the face stages on and a single chain

@@ -76,6 +76,33 @@ def slots_arg(slots, batch):
     return t.to(torch.int32).contiguous()
 
 
+def pool_capacity_arg(capacity):
+    """Argument check of enable_pool: an int in [1, 4096]; ValueError otherwise."""
+    if isinstance(capacity, bool) or not isinstance(capacity, int):
+        raise ValueError(f"capacity must be an int, got {capacity!r}")
+    if not 1 <= capacity <= 4096:
+        raise ValueError(f"capacity must lie in [1, 4096], got {capacity}")
+    return capacity
+
+
+def entries_arg(entries, capacity, most, distinct):
+    """entries (int list / int tensor) -> int32 CPU tensor of 1..most pool entries in [0, capacity), distinct where asked for; ValueError
+    otherwise."""
+    if capacity is None:
+        raise RuntimeError("no pool is configured: call enable_pool(capacity) first")
+    t = torch.as_tensor(entries)
+    if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise ValueError("entries must be integers")
+    t = t.flatten().to(device="cpu", dtype=torch.int64)
+    if t.numel() < 1 or t.numel() > most:
+        raise ValueError(f"between 1 and {most} entries must be given, got {t.numel()}")
+    if bool(((t < 0) | (t >= capacity)).any()):
+        raise ValueError(f"entries must lie in [0, {capacity})")
+    if distinct and t.unique().numel() != t.numel():
+        raise ValueError("entries must be distinct")
+    return t.to(torch.int32).contiguous()
+
+
 def mask_args(mask, known, noise, n, L):
     """Argument checks of set_mask, before any device work: mask [n,L,L] or [n,1,L,L], finite and in [0, 1]; known and noise [n,4,L,L].
     Returns the three as fp32 tensors ([n,L,L], [n,4,L,L], [n,4,L,L]) on the devices they came from; ValueError otherwise."""
@@ -211,6 +238,7 @@ class _Engine:
         self.batch = None
         self.preview_cfg = None    # (every, snapshots) while previews are on: given to every context this engine creates
         self.guide_on = False      # hd_guide_config: given to every context this engine creates
+        self.pool_cap = None       # hd_pool_config: the capacity while a pool is on; given to every context this engine creates
 
     def ensure(self, device):
         device = torch.device(device)
@@ -234,6 +262,8 @@ class _Engine:
             _lib.check(L.hd_preview_config(ctx, 1, *self.preview_cfg), ctx)
         if self.guide_on:
             _lib.check(L.hd_guide_config(ctx, 1), ctx)
+        if self.pool_cap is not None:
+            _lib.check(L.hd_pool_config(ctx, self.pool_cap), ctx)
         return ctx
 
     def manifest(self):
@@ -338,6 +368,60 @@ class _Engine:
             _lib.check(_lib.lib().hd_prepare_slots(self.ctx, n, ctypes.cast(sl.data_ptr(), ctypes.POINTER(ctypes.c_int32)), crl.data_ptr(),
                                                    crf.data_ptr() if crf is not None else None, emb.data_ptr() if emb is not None else None,
                                                    _stream(self.device)), self.ctx)
+        self.cond_key, self.prior_key = None, None         # the batch no longer matches any one pair of tensors
+
+    def enable_pool(self, capacity):
+        """hd_pool_config: a conditioning pool of `capacity` (1..4096) entries; every entry is invalid afterwards.  Before the model has a
+        device only the setting is kept."""
+        if not self.conditional:
+            raise RuntimeError("the conditioning pool needs the conditional refiner")
+        self.pool_cap = pool_capacity_arg(capacity)
+        if self.ctx is not None:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().hd_pool_config(self.ctx, self.pool_cap), self.ctx)
+
+    def disable_pool(self):
+        """Free the pool."""
+        self.pool_cap = None
+        if self.ctx is not None:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().hd_pool_config(self.ctx, 0), self.ctx)
+
+    def pool_prepare(self, entries, cr_latent, cr_face=None, id_emb=None):
+        """hd_pool_prepare: compute the conditioning of n faces and keep face j in pool entry entries[j] (n distinct ints in
+        [0, capacity), n <= the prepared batch).  The prepared batch is not touched."""
+        self.require_loaded()
+        if self.batch is None:
+            raise RuntimeError("no batch is prepared: call prepare(cr_face, cr_latent) for the whole batch first")
+        en = entries_arg(entries, self.pool_cap, min(self.batch, self.pool_cap or 0), True)
+        n, L = en.numel(), self.latent_res
+        if tuple(cr_latent.shape) != (n, 4, L, L):
+            raise RuntimeError("cr_latent must be (%d,4,%d,%d), got %s" % (n, L, L, tuple(cr_latent.shape)))
+        if (cr_face is None) == (id_emb is None):
+            raise RuntimeError("need exactly one of cr_face / id_emb")
+        if cr_face is not None and tuple(cr_face.shape) != (n, 3, 128, 128):
+            raise RuntimeError("cr_face must be (%d,3,128,128), got %s" % (n, tuple(cr_face.shape)))
+        crl = _f32c(cr_latent, self.device)
+        crf = _f32c(cr_face, self.device) if cr_face is not None else None
+        emb = _f32c(id_emb.reshape(n, -1), self.device) if id_emb is not None else None
+        if emb is not None and emb.shape[1] != 2048:
+            raise RuntimeError("identity embedding must have 2048 features")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().hd_pool_prepare(self.ctx, n, ctypes.cast(en.data_ptr(), ctypes.POINTER(ctypes.c_int32)), crl.data_ptr(),
+                                                  crf.data_ptr() if crf is not None else None, emb.data_ptr() if emb is not None else None,
+                                                  _stream(self.device)), self.ctx)
+
+    def pool_commit(self, slots, entries):
+        """hd_pool_commit: the prepared batch's faces in `slots` (n distinct ints in [0, B)) take the conditioning kept in `entries`
+        (n prepared pool entries; one entry may fill several slots)."""
+        self.require_loaded()
+        sl = slots_arg(slots, self.batch)
+        en = entries_arg(entries, self.pool_cap, self.batch, False)
+        if en.numel() != sl.numel():
+            raise ValueError(f"{sl.numel()} slots but {en.numel()} entries")
+        i32p = lambda t: ctypes.cast(t.data_ptr(), ctypes.POINTER(ctypes.c_int32))   # noqa: E731
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().hd_pool_commit(self.ctx, sl.numel(), i32p(sl), i32p(en), _stream(self.device)), self.ctx)
         self.cond_key, self.prior_key = None, None         # the batch no longer matches any one pair of tensors
 
     def set_mask(self, mask, known, noise, slots=None):
@@ -720,6 +804,32 @@ class FacialRefiner(_Previews, _Guidance, nn.Module):
         if not e.conditional:
             raise RuntimeError("prepare_slots needs the conditional refiner")
         e.prepare_slots(slots, cr_latent, cr_face=cr_face)
+
+    def enable_pool(self, capacity):
+        """Conditioning pool: the model keeps room for the prepared conditioning of `capacity` (1..4096) faces, about 0.29 MB each at
+        latent 16 and 1.1 MB at latent 32.  pool_prepare fills entries, pool_commit copies them into slots of the prepared batch: the
+        two halves of prepare_slots, so that a serving loop prepares its queued requests together (the prologue costs about the same for
+        64 faces as for one) and refills a slot with one copy.  The pool outlives prepare; enable_pool again empties it."""
+        self._engine.enable_pool(capacity)
+
+    def disable_pool(self):
+        """Free the conditioning pool."""
+        self._engine.disable_pool()
+
+    def pool_prepare(self, entries, cr_face, cr_latent):
+        """Compute the conditioning of cr_face [n,3,128,128] / cr_latent [n,4,L,L] and keep face j in pool entry entries[j] (n distinct
+        ints in [0, capacity), n <= the prepared batch).  Needs a prepared batch (the prologue runs on its staging buffers) and leaves it
+        alone bit for bit; preparing an entry again overwrites it."""
+        e = self._engine
+        e.ensure(cr_latent.device)
+        e.pool_prepare(entries, cr_latent, cr_face=cr_face)
+
+    def pool_commit(self, slots, entries):
+        """The prepared batch's faces in `slots` (n distinct ints in [0, B)) take the conditioning kept in `entries` (n prepared entries;
+        one entry may fill several slots, e.g. several seeds of one face), bit for bit what prepare_slots would have given them, and lose
+        their mask, guidance, previews and multistep history as after prepare_slots.  The entries stay valid.  Continue with
+        sample(..., prepare=False)."""
+        self._engine.pool_commit(slots, entries)
 
     def set_mask(self, mask, known, noise, slots=None):
         """Inpainting: give the prepared batch's faces in `slots` (None: all, in order) a mask [n,L,L] or [n,1,L,L] in [0, 1] (1: resample,

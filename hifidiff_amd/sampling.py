@@ -529,6 +529,53 @@ class SlotTable:
         return done
 
 
+class PoolTable:
+    """Entry bookkeeping of the conditioning pool (host only, no device): which request holds which of `capacity` entries.
+
+    take(req_ids) gives each request the lowest free entry and queues it as prepared; pop(n) hands the n oldest prepared requests back
+    in submission order (FIFO) as (request id, entry) -- they are about to be committed to slots -- and release(entry) frees the entry
+    of a committed request for the next take."""
+
+    def __init__(self, capacity):
+        if isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 1:
+            raise ValueError("capacity must be an int >= 1")
+        self.capacity = capacity
+        self.req = [None] * capacity            # request id per entry (None: free)
+        self.fifo = []                          # entries of the prepared, uncommitted requests, oldest first
+
+    def free_entries(self):
+        return [e for e, r in enumerate(self.req) if r is None]
+
+    def pending(self):
+        """[(request id, entry)] of the prepared requests no slot has taken yet, oldest first."""
+        return [(self.req[e], e) for e in self.fifo]
+
+    def take(self, req_ids):
+        """Give each of req_ids (in submission order) a free entry, lowest first; returns the entries.  RuntimeError when fewer are free."""
+        req_ids = list(req_ids)
+        free = self.free_entries()
+        if len(req_ids) > len(free):
+            raise RuntimeError(f"no free entry: {len(req_ids)} requests for {len(free)} free entries of {self.capacity}")
+        entries = free[:len(req_ids)]
+        for e, r in zip(entries, req_ids):
+            self.req[e] = r
+        self.fifo += entries
+        return entries
+
+    def pop(self, n):
+        """The n oldest prepared requests as [(request id, entry)]; their entries stay taken until release."""
+        if not 0 <= n <= len(self.fifo):
+            raise ValueError(f"{n} requests asked for, {len(self.fifo)} are prepared")
+        out, self.fifo = [(self.req[e], e) for e in self.fifo[:n]], self.fifo[n:]
+        return out
+
+    def release(self, entry):
+        """Free the entry of a committed request."""
+        if self.req[entry] is None or entry in self.fifo:
+            raise ValueError(f"entry {entry} is free or its request is not committed yet")
+        self.req[entry] = None
+
+
 class ContinuousSampler:
     """Continuous batching: a serving loop that keeps the B slots of one prepared batch busy.  A request that reaches the last row
     leaves its slot, and the next queued request takes it (FacialRefiner.prepare_slots replaces that slot's conditioning alone, nothing
@@ -550,12 +597,28 @@ class ContinuousSampler:
     rows, its strength maps onto that member's row count, and its result is what it would be on that member alone.
 
     previews=True: previews() returns, between two step() calls, the progress and the current denoised estimate of every request that
-    is in a slot and has run a row; like its result, a request's preview does not depend on its slot or neighbours."""
+    is in a slot and has run a row; like its result, a request's preview does not depend on its slot or neighbours.
 
-    def __init__(self, model, scheduler, batch=64, refill_every=5, previews=False):
+    prefetch=P >= 1: the conditioning of queued requests is prepared ahead, up to P of them (and at most `batch`) in one
+    FacialRefiner.pool_prepare call, and a refill copies it into the freed slots with one pool_commit -- the prologue costs about the
+    same for 64 faces as for one, so refilling one or two slots at a time (refill_every=1) no longer pays it per refill.  The first fill
+    stays one prepare of the whole batch.  A refill commits at most the requests the pool holds, so P below `batch` caps the slots filled
+    per refill at P: the other free slots stay empty until the next step().  A request's conditioning is then computed at the batch size of its pool_prepare call instead
+    of its refill; everything else about it is unchanged.  pool_calls / pool_prepared count the calls and the requests they prepared."""
+
+    def __init__(self, model, scheduler, batch=64, refill_every=5, previews=False, prefetch=0):
         if batch < 1 or refill_every < 1:
             raise ValueError("batch and refill_every must be >= 1")
+        if isinstance(prefetch, bool) or not isinstance(prefetch, int) or prefetch < 0:
+            raise ValueError(f"prefetch must be an int >= 0, got {prefetch!r}")
+        if prefetch and not model.engine.conditional:
+            raise ValueError("prefetch needs the refiner: the unconditional Denoiser has no conditioning to prepare ahead")
         self.model, self.scheduler = model, scheduler
+        self.prefetch = prefetch
+        self.pool = None
+        if prefetch:                    # the model keeps the pool (model.disable_pool())
+            model.enable_pool(prefetch)
+            self.pool = PoolTable(prefetch)
         self.want_previews = bool(previews)
         if self.want_previews:          # the latest estimate of every slot; the model keeps the setting (model.disable_previews())
             model.enable_previews(1, 0)
@@ -573,6 +636,8 @@ class ContinuousSampler:
         self.next_id = 0
         self.calls = 0
         self.refilled = 0
+        self.pool_calls = 0             # pool_prepare calls, and the requests they prepared
+        self.pool_prepared = 0
 
     def submit(self, cr_face, cr_latent, seed, strength=1.0, mask=None, schedule=None, fidelity=None, fidelity_scale=4, fidelity_rows=None):
         """schedule: the member of the ScheduleSet this request runs (None: the first member; without a set it must stay None).
@@ -641,9 +706,38 @@ class ContinuousSampler:
             lat, start = img2img_start(sch, cr_latent.detach().float().cpu()[None], strength, noise=z)
         return lat[0], int(start[0])
 
+    @staticmethod
+    def _upload(tensors, dev):
+        """n tensors of one kind as [n, ...] fp32 on the device: one host-to-device transfer when they all live on the host."""
+        ts = [t.detach().to(torch.float32) for t in tensors]
+        if all(t.device.type == "cpu" for t in ts):
+            return torch.stack(ts).to(dev)
+        return torch.stack([t.to(dev) for t in ts])
+
+    def _top_up(self, dev, n_free):
+        """Prepare queued requests ahead when fewer are prepared than slots are free: min(unprepared, free entries, batch) of them, in
+        submission order, in one pool_prepare call.  The prepared requests are the head of the queue, in order."""
+        ahead = len(self.pool.pending())
+        unprepared = len(self.queue) - ahead
+        if ahead >= n_free or unprepared < 1:
+            return
+        k = min(unprepared, len(self.pool.free_entries()), self.batch)
+        if k < 1:
+            return
+        reqs = self.queue[ahead:ahead + k]
+        entries = self.pool.take([r[0] for r in reqs])
+        self.model.pool_prepare(entries, self._upload([r[1] for r in reqs], dev), self._upload([r[2] for r in reqs], dev))
+        self.pool_calls += 1
+        self.pool_prepared += k
+
     def _refill(self, dev):
-        new, masked, guided = [], [], []
-        while self.queue and self.table.free_slots():
+        free = self.table.free_slots()
+        pooled = self.pool is not None and self.prepared      # the first fill is one prepare of the whole batch
+        if pooled and free and self.queue:
+            self._top_up(dev, len(free))
+        n_new = min(len(self.queue), len(free), len(self.pool.pending()) if pooled else len(free))
+        new, lats, masked, guided = [], [], [], []
+        for _ in range(n_new):
             rid, crf, crl, seed, strength, mask, fidelity, schedule = self.queue.pop(0)
             lat, start = self._start(crl, seed, strength, mask is not None, schedule)
             if self.sset is None:
@@ -652,28 +746,37 @@ class ContinuousSampler:
                 begin, end = self.sset.span(schedule)
                 slot = self.table.assign(rid, begin + start, begin, end)
             self.seeds[slot] = seed
-            self.x[slot] = lat.to(dev)
+            lats.append(lat)
             new.append((slot, crf, crl))
             if mask is not None:
                 masked.append((slot, mask, crl, self._z(seed)[0]))
             if fidelity is not None:
                 guided.append((slot, crl, fidelity))
-        if not new or not self.conditional:
+        if not new:
             return
         slots = [s for s, _, _ in new]
-        crf = torch.stack([f.to(dev, torch.float32) for _, f, _ in new])
-        crl = torch.stack([l.to(dev, torch.float32) for _, _, l in new])
-        if not self.prepared:           # the first batch: the whole batch is prepared once (empty slots get zeros; they are held)
-            B, L = self.batch, self.L
-            full_f = torch.zeros((B, 3, 128, 128), device=dev)
-            full_l = torch.zeros((B, 4, L, L), device=dev)
-            full_f[slots], full_l[slots] = crf, crl
-            self.model.prepare(full_f, full_l)
-            self.model.engine.cond_key = None          # the batch belongs to the sampler: no cache hit on these tensors later
-            self.prepared = True
-        else:
-            self.model.prepare_slots(slots, crf, crl)
+        self.x[slots] = self._upload(lats, dev)
+        if not self.conditional:
+            return
+        if pooled:                      # the conditioning is in the pool already: the oldest prepared requests are these
+            took = self.pool.pop(len(slots))
+            self.model.pool_commit(slots, [e for _, e in took])
+            for _, e in took:
+                self.pool.release(e)
             self.refilled += len(slots)
+        else:
+            crf, crl = self._upload([f for _, f, _ in new], dev), self._upload([l for _, _, l in new], dev)
+            if not self.prepared:       # the first batch: the whole batch is prepared once (empty slots get zeros; they are held)
+                B, L = self.batch, self.L
+                full_f = torch.zeros((B, 3, 128, 128), device=dev)
+                full_l = torch.zeros((B, 4, L, L), device=dev)
+                full_f[slots], full_l[slots] = crf, crl
+                self.model.prepare(full_f, full_l)
+                self.model.engine.cond_key = None      # the batch belongs to the sampler: no cache hit on these tensors later
+                self.prepared = True
+            else:
+                self.model.prepare_slots(slots, crf, crl)
+                self.refilled += len(slots)
         if masked:                      # after the prepare: it has cleared the masks of the slots it filled
             self.model.set_mask(torch.stack([m for _, m, _, _ in masked]), torch.stack([l.detach().float().cpu() for _, _, l, _ in masked]),
                                 torch.stack([z for _, _, _, z in masked]), slots=[s for s, _, _, _ in masked])

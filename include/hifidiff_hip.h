@@ -169,6 +169,29 @@ int hd_sample_rows_multistep(hd_ctx* ctx, float* x_inout, const hd_schedule_ms* 
  * until every face has one again).  HD_ERR_NOT_READY without a prepared conditional batch; HD_ERR_INVALID for a duplicate or out-of-range
  * slot, n outside [1, B], an unconditional / CoarseRestoration / VAE context or a bad pointer combination. */
 int hd_prepare_slots(hd_ctx* ctx, int n, const int32_t* slots, const float* cr_latent, const float* cr_face, const float* id_emb, void* stream);
+/* The conditioning pool: hd_prepare_slots in two halves, with a place to keep prepared conditioning between them.  The requests waiting in
+ * a serving loop's queue are known long before a slot frees, and the prologue costs about the same for 64 faces as for one: prepare
+ * them together, and a refill is one copy launch.  Everything stays on the caller's one stream.
+ * hd_pool_config: the context owns `capacity` entries (0 <= capacity <= 4096; 0 frees the pool), each one face's conditioning: 5 priors,
+ * 5 w_c, 5 w_s, the idc term and id_emb -- about 72 k floats (0.29 MB) at latent 16, 270 k (1.1 MB) at latent 32.  The pool belongs to the
+ * context, not to a batch: it survives hd_prepare* (at another batch size too).  (Re)configuring invalidates every entry and may
+ * synchronise the device (not for the hot path).  hd_get_option "pool_capacity" / "pool_valid" (entries that hold a face) report it.
+ * hd_pool_prepare: run the prologue of hd_prepare_slots for n faces, 1 <= n <= min(B, capacity), and store face j in entry entries[j]
+ * (host [n], distinct, in [0, capacity)); cr_latent / cr_face / id_emb as for hd_prepare_slots.  The prologue runs on the prepared batch's
+ * staging chain, but nothing of the running batch is written: no slot's conditioning, mask, guidance, preview or history, and nothing is
+ * recaptured -- a loop split around the call gives the bits it gives without it.  The entries are valid afterwards; preparing an entry
+ * again overwrites it and does not touch a slot it was committed to.
+ * hd_pool_commit: copy entry entries[j] (host [n], valid, may repeat: several slots may take one face) into slot slots[j] (host [n],
+ * distinct, in [0, B)), 1 <= n <= B, and reset of those slots what hd_prepare_slots resets: mask, guidance, previews, multistep history.
+ * Entries stay valid.  Nothing is rebuilt or recaptured.  hd_pool_prepare of n faces followed by commits of them, in any grouping and
+ * order, leaves in each slot bit for bit what hd_prepare_slots of the same n faces in the same order leaves: what hd_prepare computes for
+ * them as a batch of n.
+ * HD_ERR_NOT_READY without a prepared conditional batch or (prepare, commit) without a pool; HD_ERR_INVALID, naming the argument, for an
+ * unconditional / CoarseRestoration / VAE context, a capacity or n out of range, a duplicate slot, a duplicate entry in hd_pool_prepare, an
+ * out-of-range slot or entry, an entry that was never prepared, or a bad pointer combination. */
+int hd_pool_config(hd_ctx* ctx, int capacity);
+int hd_pool_prepare(hd_ctx* ctx, int n, const int32_t* entries, const float* cr_latent, const float* cr_face, const float* id_emb, void* stream);
+int hd_pool_commit(hd_ctx* ctx, int n, const int32_t* slots, const int32_t* entries, void* stream);
 /* hd_sample_rows / hd_sample_rows_multistep with per-face noise keys and per-face resumption (same graphs, hd_check and NaN-poisoning rules).
  * face_seeds: host [B] or NULL.  With it, z of face f at row k, element e of the face (0 <= e < 4L^2) is Philox4x32-10(face_seeds[f]; k, e):
  *   independent of the slot, the batch size and the neighbours -- a face in slot 0 with key s gets exactly the z of hd_sample_rows(seed = s)

@@ -9,11 +9,17 @@ Also: hd_prepare_slots for n = 1, 8, 32, 64 against hd_prepare at 64, hd_sample_
 of a continuous run goes (refills against sampling calls; an instrumented run with a synchronisation around each part).
 --mixed-steps 10,20,50 runs one scenario instead (and appends to --out): the requests cycle through DDIM schedules of these step counts,
 strengths uniform in [0.2, 1.0]; one ContinuousSampler over a sampling.ScheduleSet (hd_sample_spans: all step counts share the 64 slots)
-against one ContinuousSampler per step count, run one after the other, shortest schedule first (what a single-schedule batch allows)."""
+against one ContinuousSampler per step count, run one after the other, shortest schedule first (what a single-schedule batch allows).
+--prefetch P measures the conditioning pool instead (writes profiles/r15_pool_bench.txt, or --out): scenarios (a), (b), (c) at K = 1, 5, 10
+with ContinuousSampler(prefetch=0) and (prefetch=P), and with --parent DIR (a checkout of the parent commit with its library built) the
+parent's sampler in a second process, all in alternating runs: faces/s median [min, max] and the instrumented refill share of each; then
+hd_pool_prepare and hd_pool_commit for n = 1, 8, 64 next to hd_prepare_slots.
+    python tools/stream_bench.py --prefetch 64 [--parent DIR] [--runs 3]"""
 import argparse
 import ctypes
 import os
 import statistics
+import subprocess
 import sys
 import time
 
@@ -54,9 +60,9 @@ def run_static(m, sch, reqs):
     return time.perf_counter() - t0, statistics.mean(lat)
 
 
-def run_continuous(m, sch, reqs, K, instrument=False):
+def run_continuous(m, sch, reqs, K, instrument=False, prefetch=0):
     from hifidiff_amd import sampling
-    cs = sampling.ContinuousSampler(m, sch, batch=64, refill_every=K)
+    cs = sampling.ContinuousSampler(m, sch, batch=64, refill_every=K, **({"prefetch": prefetch} if prefetch else {}))
     t_refill = [0.0]
     if instrument:
         inner = cs._refill
@@ -146,14 +152,162 @@ def mixed_steps(m, a):
         fh.write(txt)
 
 
+def scenarios():
+    from hifidiff_amd import schedulers
+
+    def ddim():
+        s = schedulers.DDIMScheduler(clip_sample_range=3.0)
+        s.set_timesteps(50)
+        return s
+
+    def dpm():
+        s = schedulers.DPMSolverMultistepScheduler()
+        s.set_timesteps(20)
+        return s
+    return [("a", "512 requests, strength 1.0, DDIM-50", ddim, False), ("b", "512 requests, strength U[0.2, 1.0], DDIM-50", ddim, True),
+            ("c", "512 requests, strength U[0.2, 1.0], DPM-Solver++ 2M 20 steps", dpm, True)]
+
+
+def t_ms(fn, reps=10):
+    fn()
+    sync()
+    v = []
+    for _ in range(reps):
+        sync()
+        t = time.perf_counter()
+        fn()
+        sync()
+        v.append((time.perf_counter() - t) * 1e3)
+    return statistics.median(v), min(v), max(v)
+
+
+def worker(root, n_req):
+    """--prefetch: one process per tree (this one, the parent's).  Commands on stdin: `run <scenario> <K> <prefetch> <instrument>` ->
+    `<seconds> <mean latency> <refill seconds> <calls>`; `cond` -> the pool call timings, one line each, then `end`."""
+    sys.path.insert(0, root)
+    from hifidiff_amd import synth
+    from hifidiff_amd.refiner import FacialRefiner
+    torch.set_grad_enabled(False)
+    m = FacialRefiner(16)
+    m.load_state_dict(synth.refiner_state_dict(16))
+    m.to("cuda:0")
+    scen = {key: (mk(), requests(n_req, mixed)) for key, _, mk, mixed in scenarios()}
+    print("ready", flush=True)
+    for line in sys.stdin:
+        cmd = line.split()
+        if cmd[0] == "quit":
+            break
+        if cmd[0] == "run":
+            sch, reqs = scen[cmd[1]]
+            total, lat, t_ref, calls = run_continuous(m, sch, reqs, int(cmd[2]), instrument=cmd[4] == "1", prefetch=int(cmd[3]))
+            if int(cmd[3]):
+                m.disable_pool()
+            print(f"{total:.6f} {lat:.6f} {t_ref:.6f} {calls}", flush=True)
+        elif cmd[0] == "cond":
+            _, crl, crf = synth.sample_inputs(64, 16)
+            crl, crf = crl.cuda(), crf.cuda()
+            e = m.engine
+            e.prepare(crl, cr_face=crf)
+            e.enable_pool(64)
+            for nn in (1, 8, 64):
+                idx = list(range(0, 64, 64 // nn))[:nn]
+                for name, fn in (("hd_prepare_slots", lambda: e.prepare_slots(idx, crl[:nn], cr_face=crf[:nn])),
+                                 ("hd_pool_prepare ", lambda: e.pool_prepare(idx, crl[:nn], cr_face=crf[:nn])),
+                                 ("hd_pool_commit  ", lambda: e.pool_commit(idx, idx))):
+                    t = t_ms(fn)
+                    print(f"{name}  n = {nn:2d}: {t[0]:7.3f} [{t[1]:.3f}, {t[2]:.3f}]", flush=True)
+            e.disable_pool()
+            print("end", flush=True)
+
+
+class Child:
+    def __init__(self, root, n_req):
+        self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", root, "--requests", str(n_req)],
+                                  stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
+        line = self.p.stdout.readline()
+        while line and not line.startswith("ready"):
+            line = self.p.stdout.readline()
+        if not line:
+            raise RuntimeError("the worker of %s ended before it was ready" % root)
+
+    def ask(self, cmd):
+        self.p.stdin.write(cmd + "\n")
+        self.p.stdin.flush()
+        line = self.p.stdout.readline()
+        if not line:
+            raise RuntimeError("the worker ended")
+        return line.rstrip("\n")
+
+    def run(self, key, K, prefetch, instrument=False):
+        v = self.ask(f"run {key} {K} {prefetch} {int(instrument)}").split()
+        return float(v[0]), float(v[1]), float(v[2]), int(v[3])
+
+    def close(self):
+        self.p.stdin.write("quit\n")
+        self.p.stdin.flush()
+        self.p.wait()
+
+
+def pool_bench(a):
+    P, n = a.prefetch, a.requests
+    this = Child(ROOT, n)
+    parent = Child(os.path.abspath(a.parent), n) if a.parent else None
+    forms = ([("parent", parent, 0)] if parent else []) + [("prefetch 0", this, 0), (f"prefetch {P}", this, P)]
+    out = [f"# tools/stream_bench.py --prefetch {P}: batch 64, latent 16, synthetic weights, one MI355X; {n} requests queued at t = 0; "
+           f"{a.runs} alternating runs per configuration (median [min, max]); parent: the parent commit's build in a process of its own"
+           + ("" if parent else " (not run: no --parent)")]
+    for key, title, _, _ in scenarios():
+        out.append(f"\n({key}) {title}")
+        out.append("form                         faces/s median [min, max]        mean latency s   vs " + forms[0][0] + "   instrumented: refills of the run")
+        for K in (1, 5, 10):
+            for _, ch, pf in forms:                                        # warm: captures, FiLM table, staging chain, pool
+                ch.run(key, K, pf)
+            res = {f: [] for f, _, _ in forms}
+            for _ in range(a.runs):
+                for f, ch, pf in forms:
+                    res[f].append(ch.run(key, K, pf))
+            base = statistics.median(n / r[0] for r in res[forms[0][0]])
+            for f, ch, pf in forms:
+                fps = [n / r[0] for r in res[f]]
+                lat = statistics.median(r[1] for r in res[f])
+                total, _, t_ref, calls = ch.run(key, K, pf, instrument=True)
+                out.append(f"K={K:<2d} {f:<22} {statistics.median(fps):8.1f} [{min(fps):7.1f}, {max(fps):7.1f}]   {lat:10.3f}      "
+                           f"{statistics.median(fps) / base:5.2f}x      {t_ref:.3f} of {total:.3f} s ({100 * t_ref / total:.1f} %), {calls} calls")
+            print("\n".join(out[-len(forms):]), flush=True)
+    out.append("\nconditioning calls (ms, host-timed with synchronisation, median [min, max] of 10)")
+    this.p.stdin.write("cond\n")
+    this.p.stdin.flush()
+    for line in iter(this.p.stdout.readline, ""):
+        if line.startswith("end"):
+            break
+        out.append(line.rstrip("\n"))
+    this.close()
+    if parent:
+        parent.close()
+    txt = "\n".join(out) + "\n"
+    print(txt)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as fh:
+        fh.write(txt)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--requests", type=int, default=512)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08_stream_bench.txt"))
+    ap.add_argument("--out", default=None, help="default: profiles/r08_stream_bench.txt (--prefetch: profiles/r15_pool_bench.txt)")
     ap.add_argument("--mixed-steps", help="comma-separated step counts: run the mixed-schedule scenario only, appended to --out")
+    ap.add_argument("--prefetch", type=int, default=0, metavar="P", help="measure the conditioning pool: prefetch 0 and P (and --parent) at K = 1, 5, 10")
+    ap.add_argument("--parent", help="--prefetch: checkout of the parent commit (library built): its sampler is alternated with this tree's")
+    ap.add_argument("--worker", help=argparse.SUPPRESS)
     a = ap.parse_args()
-    from hifidiff_amd import _lib, schedulers, synth
+    if a.worker:
+        return worker(a.worker, a.requests)
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "r15_pool_bench.txt" if a.prefetch else "r08_stream_bench.txt")
+    if a.prefetch:
+        return pool_bench(a)
+    from hifidiff_amd import _lib, synth
     from hifidiff_amd.refiner import FacialRefiner
     torch.set_grad_enabled(False)
     m = FacialRefiner(16)
@@ -165,18 +319,8 @@ def main():
     out = ["# tools/stream_bench.py: batch 64, latent 16, synthetic weights, one MI355X; requests queued at t = 0; "
            f"{a.runs} alternating runs per configuration (median [min, max])"]
 
-    def ddim():
-        s = schedulers.DDIMScheduler(clip_sample_range=3.0)
-        s.set_timesteps(50)
-        return s
-
-    def dpm():
-        s = schedulers.DPMSolverMultistepScheduler()
-        s.set_timesteps(20)
-        return s
-
-    scen = [("a", "512 requests, strength 1.0, DDIM-50", ddim, False), ("b", "512 requests, strength U[0.2, 1.0], DDIM-50", ddim, True),
-            ("c", "512 requests, strength U[0.2, 1.0], DPM-Solver++ 2M 20 steps", dpm, True)]
+    scen = scenarios()
+    ddim = scen[0][2]
     forms = ["static"] + [f"continuous K={k}" for k in (1, 5, 10)]
     for key, title, mk, mixed in scen:
         reqs = requests(a.requests, mixed)
@@ -212,17 +356,6 @@ def main():
     crl, crf = crl.cuda(), crf.cuda()
     m.engine.prepare(crl, cr_face=crf)
 
-    def t_ms(fn, reps=10):
-        fn()
-        sync()
-        v = []
-        for _ in range(reps):
-            sync()
-            t = time.perf_counter()
-            fn()
-            sync()
-            v.append((time.perf_counter() - t) * 1e3)
-        return statistics.median(v), min(v), max(v)
     out.append("\nconditioning (ms, host-timed with synchronisation, median [min, max] of 10)")
     t = t_ms(lambda: m.engine.prepare(crl, cr_face=crf))
     out.append(f"hd_prepare        B = 64: {t[0]:7.3f} [{t[1]:.3f}, {t[2]:.3f}]")
