@@ -42,7 +42,7 @@ EXPORTS = [
     "hd_pool_config", "hd_pool_prepare", "hd_pool_commit",
     "hd_sample_faces", "hd_sample_faces_multistep", "hd_sample_spans", "hd_mask_faces", "hd_guide_config", "hd_guide_faces", "hd_preview_config", "hd_preview_read", "hd_scheduler_step",
     "hd_scheduler_step_multistep", "hd_num_ops", "hd_num_chains",
-    "hd_debug_limit_ops", "hd_debug_op_name", "hd_debug_read_op", "hd_debug_read", "hd_debug_write", "hd_set_option", "hd_get_option", "hd_check",
+    "hd_debug_limit_ops", "hd_debug_op_name", "hd_debug_op_info", "hd_debug_read_op", "hd_debug_read", "hd_debug_write", "hd_set_option", "hd_get_option", "hd_check",
     "hd_set_profiling", "hd_get_profile",
 ]
 
@@ -144,6 +144,7 @@ def lib():
     L.hd_num_chains.argtypes = [vp]
     L.hd_debug_limit_ops.argtypes = [vp, i32, i32]
     L.hd_debug_op_name.argtypes = [vp, i32, i32]; L.hd_debug_op_name.restype = ctypes.c_char_p
+    L.hd_debug_op_info.argtypes = [vp, i32, i32]
     L.hd_debug_read_op.argtypes = [vp, i32, i32, vp, i64]; L.hd_debug_read_op.restype = i64
     L.hd_debug_read.argtypes = [vp, ctypes.c_char_p, vp, i64]; L.hd_debug_read.restype = i64
     L.hd_debug_write.argtypes = [vp, ctypes.c_char_p, vp, i64]

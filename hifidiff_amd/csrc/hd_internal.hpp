@@ -78,6 +78,7 @@ struct Op {
     const void* out = nullptr;       // output buffer of the launch (introspection only)
     size_t out_elems = 0;
     int out_bf16 = 0;
+    int lk = -1, ek = -1, mode = -1; // GEMM launches (add_gemm): loader kind, epilogue kind, final kernel mode; -1 otherwise (hd_debug_op_info)
 };
 
 struct Level { int C, H, M; float *X, *Y, *T1, *pooled, *S; unsigned short *G, *Xb, *Yb, *Xg, *pooled16; float2 *sx, *sy; };
@@ -776,6 +777,7 @@ void add_gemm(hd_ctx* c, std::vector<Op>& prog, const std::string& name, GemmP p
     Chain* chp = c->ch;
     auto gp = std::make_shared<GemmP>(p);
     op.gemm = gp;
+    op.lk = (int)lk; op.ek = (int)ek; op.mode = t128;
     op.skinny_affine = p.xcd_tile_affine && (t128 & 48) == 0 && t128 != 0 && t128 != 1 && t128 != 4;     // bit 16 = deep kernel, bit 32 = wide kernel (launch_tile routes those elsewhere); base modes 0/1/4 are the tall kernel
     op.run = [c, chp, gp, lk, ek, t128, film](hipStream_t s) mutable -> hipError_t {
                         if (film && gp->film == nullptr) {        // denoiser FiLM rows live in the (re-allocatable) table

@@ -1977,6 +1977,15 @@ const char* hd_debug_op_name(hd_ctx* c, int which, int i) {
     auto* p = which_program(c, which);
     return (i >= 0 && i < (int)p->size()) ? (*p)[i].name.c_str() : "";
 }
+int hd_debug_op_info(hd_ctx* c, int which, int i) {
+    if (!c) return HD_ERR_INVALID;
+    auto* p = which_program(c, which);
+    if (i < 0 || i >= (int)p->size()) HD_FAIL(c, HD_ERR_INVALID, "no such op %d", i);
+    const Op& op = (*p)[i];
+    if (!op.gemm || op.lk < 0) return 0;
+    return ((op.lk + 1) & 0xff) | (((op.ek + 1) & 0xff) << 8) | (((op.mode + 1) & 0xff) << 16) | ((op.gemm->xcd_tile_affine ? 1 : 0) << 24) |
+           ((op.gemm->w_nt ? 1 : 0) << 25);
+}
 static int64_t read_to_host(hd_ctx* c, const void* dev, size_t n, int is_bf16, float* host_out, int64_t max_elems) {
     if (!host_out) return (int64_t)n;
     if ((int64_t)n > max_elems) HD_FAIL(c, HD_ERR_INVALID, "debug read needs %zu elements", n);

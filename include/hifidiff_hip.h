@@ -313,6 +313,15 @@ int hd_num_ops(hd_ctx* ctx, int which);                    /* kernel launches in
 int hd_num_chains(hd_ctx* ctx);                            /* concurrently scheduled sub-batches       */
 int hd_debug_limit_ops(hd_ctx* ctx, int which, int n_ops); /* run only the first n ops (<0: all)      */
 const char* hd_debug_op_name(hd_ctx* ctx, int which, int i);
+/* How launch i is dispatched.  0 for a launch that is not one of the shared GEMM kernels; otherwise
+ *   bits 0-7   loader kind + 1    (0 F32, 1 LN, 2 BF16, 3 BF16S, 4 CONV_F32, 5 CONV_F32G, 6 CONV_BF16)
+ *   bits 8-15  epilogue kind + 1  (0 BIASF32, 1 RESID, 2 GATE, 3 PIXSHUF, 4 BIASBF16, 5 DWGATE, 6 SCA)
+ *   bits 16-23 kernel mode + 1    (0 / 1 tall 128 / 64 rows, 2 / 3 skinny 64 / 32 rows, 4 tall 32 rows x 256 columns, 5 / 6 skinny with
+ *                                  128 / 256-row M-split workgroups; + 16 deep-prefetch tall kernel, + 32 role-split wide kernel) -- the
+ *                                  mode the launch is given after the caller's hint and the HD_GEMM_MODE / HD_OP_MODE overrides
+ *   bit 24     xcd_tile_affine (the workgroups of an XCD share weight tiles), bit 25 w_nt (non-temporal weight loads)
+ * Negative: HD_ERR_INVALID (no such launch). */
+int hd_debug_op_info(hd_ctx* ctx, int which, int i);
 /* copy the output buffer of op i to the host as fp32; host_out NULL -> just return the element count */
 int64_t hd_debug_read_op(hd_ctx* ctx, int which, int i, float* host_out, int64_t max_elems);
 /* copy a named internal buffer (DESIGN.md "Buffers") to the host as fp32; returns the element count */
