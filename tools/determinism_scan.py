@@ -9,7 +9,7 @@ import numpy as np
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hifidiff_amd import _lib, refiner, synth
-from tools.op_parity import read_op
+from tools.forced import read_op
 
 
 def scan(B=64, latent=16, reps=3, model=None, verbose=True, max_bad=5, which=0, per_face=True, only=None):
@@ -45,7 +45,7 @@ def scan(B=64, latent=16, reps=3, model=None, verbose=True, max_bad=5, which=0, 
             else:
                 e.eps(x, t)
             torch.cuda.synchronize()
-            o = read_op(L, e.ctx, which, i).numpy()
+            o = read_op(e.ctx, which, i).numpy()
             if r < 2 or not np.array_equal(outs[0].view(np.uint32), o.view(np.uint32)):
                 outs.append(o.copy())
                 if r >= 2:

@@ -7,16 +7,15 @@ and including that launch, its output buffer is read back and compared with the 
 same name.  The first op whose error jumps is the broken one.  (Test infrastructure: uses oracle/.)
 """
 import argparse
-import ctypes
 import os
 import sys
 import time
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
+from forced import read_op                                # noqa: E402
 from hifidiff_amd import _lib, synth                      # noqa: E402
 from hifidiff_amd.refiner import FacialRefiner            # noqa: E402
 from oracle import hifidiff_oracle as O                   # noqa: E402
@@ -32,14 +31,6 @@ def to_rows(name, t, s):
     if t.dim() == 4:
         return t.permute(0, 2, 3, 1).reshape(-1)
     return t.reshape(-1)
-
-
-def read_op(L, ctx, which, i):
-    n = L.hd_debug_read_op(ctx, which, i, None, 0)
-    _lib.check(n, ctx)
-    buf = np.empty(n, dtype=np.float32)
-    _lib.check(L.hd_debug_read_op(ctx, which, i, buf.ctypes.data_as(ctypes.c_void_p), n), ctx)
-    return torch.from_numpy(buf)
 
 
 def compare(name, got, ref):
@@ -96,7 +87,7 @@ def scan(model, P, x, crl, crf, t, report, which, taps=None, floor=None, slack=(
         if name not in taps:
             report.append(f"{which}:{i:3d} {name:45s} (no tap)")
             continue
-        nm, rel, mx, note = compare(name, read_op(L, e.ctx, which, i), to_rows(name, taps[name], s))
+        nm, rel, mx, note = compare(name, read_op(e.ctx, which, i), to_rows(name, taps[name], s))
         lim = 5e-3 if floor is None else slack[0] * floor.get(name, 0.0) + slack[1]
         flag = "  <<<<<<" if not (rel < lim) else ""
         worst = max(worst, rel if rel == rel else 1e9)

@@ -6,14 +6,13 @@ The workspace buffers (X, T, S, H, H2, Xb, U, Q, K, V, mom) are reused and conv2
 the state is taken by prefix runs: for n = 1 .. N the program runs with `hd_debug_limit_ops(ctx, 0, n)` (one limit for both
 programs) and the output of launch n - 1 is read back (`hd_debug_read_op`, which = 0 encode / 1 decode) and kept on the host.
 Every launch's inputs are then earlier launches' outputs, and the oracle's arithmetic for that one launch (bf16-operand
-emulation at the points the kernels round) is applied to exactly those values.  Compared by rel-L2; a bf16-stored output is
-compared with the reference rounded to bf16 (RNE).  Bounds (the project's own for this kernel family and storage, as in
-op_forced.py): 3e-4 for fp32 outputs, 3e-3 for bf16-stored outputs.  Pure data movement (`encoder.input`, the `nearest`
+emulation at the points the kernels round) is applied to exactly those values.  Helpers, the `Check` class and its bounds (3e-4 for
+fp32 outputs, 3e-3 for bf16-stored outputs, compared with the reference rounded to bf16) and the prefix runs: tools/forced.py; the
+rules here are the VAE's own (nothing in it is a NAF block).  Pure data movement (`encoder.input`, the `nearest`
 upsamplers, `decoder.output`) must be bit-exact.  What is not a GEMM (GroupNorm, softmax(QK^T/sqrt(C)) V, quant_conv + posterior
 sample, post_quant_conv) is held against float64.  Report lines carry `<<<<<<` where a bound is exceeded; a launch without a
 rule is reported as `no rule`.  (Test infrastructure: uses oracle/.)
 """
-import ctypes
 import math
 import os
 import sys
@@ -23,12 +22,11 @@ import torch
 import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from hifidiff_amd import _lib                                  # noqa: E402
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
+from forced import BF16_BOUND, FP32_BOUND, Check, PrefixRun, nchw, q as _q64, read_op, rows      # noqa: E402
 from oracle import hifidiff_oracle as O                         # noqa: E402
 
 PR = O.BF16
-FP32_BOUND, BF16_BOUND = 3e-4, 3e-3
 ENC_OPS, DEC_OPS = 56, 75                                       # launches of the two programs without the bicubic resize (57 with it)
 
 # ---- the `stress` weight set: synth.vae_state_dict() with the changes below (tests/test_vae_ops.py verifies, from the values
@@ -52,38 +50,8 @@ def stress_state_dict(P):
 
 
 # ---------------------------------------------------------------------------------------------- helpers
-def _names(L, ctx, which):
-    return [L.hd_debug_op_name(ctx, which, i).decode() for i in range(L.hd_num_ops(ctx, which))]
-
-
-def _read_op(L, ctx, which, i):
-    n = L.hd_debug_read_op(ctx, which, i, None, 0)
-    _lib.check(n, ctx)
-    buf = np.empty(n, dtype=np.float32)
-    _lib.check(L.hd_debug_read_op(ctx, which, i, buf.ctypes.data_as(ctypes.c_void_p), n), ctx)
-    return torch.from_numpy(buf)
-
-
-def _nchw(flat, B, C, H):
-    return flat[:B * H * H * C].reshape(B, H, H, C).permute(0, 3, 1, 2).contiguous()
-
-
-def _rows(t):
-    return t.permute(0, 2, 3, 1).reshape(-1)
-
-
 def _side(flat, B, C):
     return math.isqrt(flat.numel() // (B * C))
-
-
-def _rel(got, want):
-    d = got.double() - want.double()
-    return float(d.norm() / want.double().norm().clamp_min(1e-30)), float(d.abs().max())
-
-
-def _q64(x):
-    """float64 reference -> the bf16 value the kernel stores (RNE), as fp32."""
-    return x.to(torch.float32).to(torch.bfloat16).to(torch.float32)
 
 
 def group_ratio(x):
@@ -100,36 +68,22 @@ def attention_stats(q, k):
             "argmax_past_tile0": float((am >= 64).double().mean())}
 
 
-class _Check:
-    def __init__(self, report, fp32_bound, bf16_bound):
-        self.report, self.fp32_bound, self.bf16_bound = report, fp32_bound, bf16_bound
-        self.worst = {}                                         # launch kind -> worst rel-L2 (exact kinds: number of differing elements)
-
-    def rel(self, i, name, kind, what, got, want, stored_bf16):
-        rel, mx = _rel(got, want)
-        lim = self.bf16_bound if stored_bf16 else self.fp32_bound
-        if rel != rel:
-            rel = 1e9
-        self.worst[kind] = max(self.worst.get(kind, 0.0), rel)
-        self.report.append(f"{i:3d} {name:52s} {what:8s} rel {rel:.3e} maxabs {mx:.3e} ({'bf16' if stored_bf16 else 'fp32'} <= {lim:.0e}){'' if rel <= lim else '  <<<<<<'}")
-
-    def exact(self, i, name, kind, what, got, want):
-        bad = int((got.view(torch.int32) != want.view(torch.int32)).sum()) if got.shape == want.shape else max(got.numel(), want.numel())
-        self.worst[kind] = max(self.worst.get(kind, 0), bad)
-        self.report.append(f"{i:3d} {name:52s} {what:8s} {bad} of {want.numel()} elements differ (bit-exact){'' if bad == 0 else '  <<<<<<'}")
+def _check(report, fp32_bound=FP32_BOUND, bf16_bound=BF16_BOUND):
+    return Check(report, None, fp32_bound, bf16_bound, 52, 8)
 
 
-def _prefix_outputs(L, ctx, which, run, n_ops):
-    """outs[i] = output of launch i after a run of launches 0 .. i only."""
-    outs = []
+def _prefix_outputs(pre):
+    """(names, outs) of pre's program: outs[i] = output of launch i after a run of launches 0 .. i only."""
     try:
-        for n in range(1, n_ops + 1):
-            _lib.check(L.hd_debug_limit_ops(ctx, 0, n), ctx)
-            run()
-            outs.append(_read_op(L, ctx, which, n - 1))
+        pre.run_to(1)                                           # builds the program for the run's arguments
+        names = pre.names()
+        outs = [pre.op(0)]
+        for n in range(2, len(names) + 1):
+            pre.run_to(n)
+            outs.append(pre.op(n - 1))
     finally:
-        L.hd_debug_limit_ops(ctx, 0, -1)
-    return outs
+        pre.reset()
+    return names, outs
 
 
 def _groupnorm64(x, w, b, silu):
@@ -179,42 +133,42 @@ def _scan(P, names, outs, B, feed, ck, info, first=0, X=None):
         elif leaf == "conv_in":                                 # cin 3 / 4 zero padded to 8
             cin = P[wk].shape[1]
             H = _side(outs[i - 1], B, 8)
-            src = _nchw(outs[i - 1], B, 8, H)[:, :cin]
+            src = nchw(outs[i - 1], B, 8, H)[:, :cin]
             want = O._gemm_conv(src, P[wk], P[bk], PR, padding=1)
-            ck.rel(i, name, "conv_in", "X", out, _rows(want), False)
-            X = _nchw(out, B, want.shape[1], H)
+            ck.rel(i, name, "conv_in", "X", out, rows(want), False)
+            X = nchw(out, B, want.shape[1], H)
         elif leaf in ("norm1", "norm2", "group_norm", "conv_norm_out"):
             C = P[wk].shape[0]
-            src = X if leaf != "norm2" else _nchw(outs[i - 1], B, C, _side(outs[i - 1], B, C))
+            src = X if leaf != "norm2" else nchw(outs[i - 1], B, C, _side(outs[i - 1], B, C))
             info.setdefault("gn_ratio", {})[name] = group_ratio(src)
             want = _groupnorm64(src, P[wk], P[bk], leaf != "group_norm")
-            ck.rel(i, name, "groupnorm", "H", out, _rows(_q64(want)), True)
+            ck.rel(i, name, "groupnorm", "H", out, rows(_q64(want)), True)
         elif leaf == "conv1":
             cin = P[wk].shape[1]
-            src = _nchw(outs[i - 1], B, cin, _side(outs[i - 1], B, cin))
+            src = nchw(outs[i - 1], B, cin, _side(outs[i - 1], B, cin))
             want = O._gemm_conv(src, P[wk], P[bk], PR, padding=1)
-            ck.rel(i, name, "conv3x3", "T", out, _rows(want), False)
+            ck.rel(i, name, "conv3x3", "T", out, rows(want), False)
         elif leaf == "conv_shortcut":                            # 1x1 on the fp32 loader: the residual stream itself is the operand
             want = O._gemm_conv(X, P[wk], P[bk], PR)
-            ck.rel(i, name, "conv_shortcut", "S", out, _rows(want), False)
-            S = _nchw(out, B, want.shape[1], X.shape[2])
+            ck.rel(i, name, "conv_shortcut", "S", out, rows(want), False)
+            S = nchw(out, B, want.shape[1], X.shape[2])
         elif leaf == "conv2":
             j = i - 1 if names[i - 1].endswith(".norm2") else i - 2
             cin = P[wk].shape[1]
-            src = _nchw(outs[j], B, cin, _side(outs[j], B, cin))
+            src = nchw(outs[j], B, cin, _side(outs[j], B, cin))
             resid = S if names[i - 1].endswith(".conv_shortcut") else X
             want = resid + O._gemm_conv(src, P[wk], P[bk], PR, padding=1)
-            ck.rel(i, name, "conv3x3", "X", out, _rows(want), False)
+            ck.rel(i, name, "conv3x3", "X", out, rows(want), False)
             # the block's own contribution x' - x: the residual carries part of the norm of x'
-            ck.rel(i, name, "conv3x3", "X'-X", out - _rows(resid), _rows(want - resid), False)
-            X, S = _nchw(out, B, want.shape[1], want.shape[2]), None
+            ck.rel(i, name, "conv3x3", "X'-X", out - rows(resid), rows(want - resid), False)
+            X, S = nchw(out, B, want.shape[1], want.shape[2]), None
         elif name.endswith(".downsamplers.0.conv"):              # stride 2, zeros read past the right and bottom edge
             want = O._gemm_conv(F.pad(X, (0, 1, 0, 1)), P[wk], P[bk], PR, stride=2)
-            got = _nchw(out, B, want.shape[1], want.shape[2])
+            got = nchw(out, B, want.shape[1], want.shape[2])
             ck.rel(i, name, "downsample", "X", got, want, False)
             ck.rel(i, name, "downsample", "last row", got[:, :, -1, :], want[:, :, -1, :], False)
             ck.rel(i, name, "downsample", "last col", got[:, :, :, -1], want[:, :, :, -1], False)
-            X = _nchw(out, B, want.shape[1], want.shape[2])
+            X = nchw(out, B, want.shape[1], want.shape[2])
         elif leaf in ("to_q", "to_k", "to_v"):
             g = i - 1 - ("to_q", "to_k", "to_v").index(leaf)
             assert names[g].endswith(".group_norm"), names[g]
@@ -229,25 +183,25 @@ def _scan(P, names, outs, B, feed, ck, info, first=0, X=None):
             a = outs[i - 1].reshape(B, -1, 512)
             o = O._gemm_linear(a, P[wk], P[bk], PR)
             want = X + o.transpose(1, 2).reshape(X.shape)
-            ck.rel(i, name, "to_out", "X", out, _rows(want), False)
-            ck.rel(i, name, "to_out", "X'-X", out - _rows(X), _rows(want - X), False)
-            X = _nchw(out, B, 512, X.shape[2])
+            ck.rel(i, name, "to_out", "X", out, rows(want), False)
+            ck.rel(i, name, "to_out", "X'-X", out - rows(X), rows(want - X), False)
+            X = nchw(out, B, 512, X.shape[2])
         elif name.endswith(".upsamplers.0.nearest"):
             want = F.interpolate(PR.q(X), scale_factor=2.0, mode="nearest")
-            ck.exact(i, name, "nearest", "U", out, _rows(want))
+            ck.exact(i, name, "nearest", "U", out, rows(want))
         elif name.endswith(".upsamplers.0.conv"):
             C, H = X.shape[1], 2 * X.shape[2]
-            want = O._gemm_conv(_nchw(outs[i - 1], B, C, H), P[wk], P[bk], PR, padding=1)
-            ck.rel(i, name, "upsample_conv", "X", out, _rows(want), False)
-            X = _nchw(out, B, C, H)
+            want = O._gemm_conv(nchw(outs[i - 1], B, C, H), P[wk], P[bk], PR, padding=1)
+            ck.rel(i, name, "upsample_conv", "X", out, rows(want), False)
+            X = nchw(out, B, C, H)
         elif leaf == "conv_out":                                # N = 8 / N = 3 output columns
             cin = P[wk].shape[1]
-            src = _nchw(outs[i - 1], B, cin, X.shape[2])
+            src = nchw(outs[i - 1], B, cin, X.shape[2])
             want = O._gemm_conv(src, P[wk], P[bk], PR, padding=1)
-            ck.rel(i, name, "conv_out", "out", out, _rows(want), False)
+            ck.rel(i, name, "conv_out", "out", out, rows(want), False)
         elif name == "quant_conv.sample":
             Lr = X.shape[2]
-            mom = _nchw(outs[i - 1], B, 8, Lr).double()          # the encoder.conv_out output this launch read
+            mom = nchw(outs[i - 1], B, 8, Lr).double()          # the encoder.conv_out output this launch read
             m = F.conv2d(mom, P["quant_conv.weight"].double(), P["quant_conv.bias"].double())
             lv = m[:, 4:]
             info["logvar"] = (float((lv < -30.0).double().mean()), float((lv > 20.0).double().mean()))
@@ -258,9 +212,9 @@ def _scan(P, names, outs, B, feed, ck, info, first=0, X=None):
                 ck.rel(i, name, "quant_conv.sample", "moments", out, m.reshape(-1), False)
         elif name == "decoder.output":
             H = X.shape[2]
-            ck.exact(i, name, "decoder.output", "images", out, _nchw(outs[i - 1], B, 3, H).reshape(-1))
+            ck.exact(i, name, "decoder.output", "images", out, nchw(outs[i - 1], B, 3, H).reshape(-1))
         else:
-            ck.report.append(f"{i:3d} {name:52s} (no rule)")
+            ck.no_rule(i, name)
 
 
 def _scan_last(P, names, outs, B, feed, ck, info, X):
@@ -284,25 +238,15 @@ def _encode_run(vae, xd, R, vae_range, nzd):
 def encode_scan(vae, P, x, image_res, report, noise=None, vae_range=False, info=None, fp32_bound=FP32_BOUND, bf16_bound=BF16_BOUND):
     """Every launch of hd_vae_encode(x [B,3,r,r] -> image_res; noise [B,4,L,L]: the posterior sample, None: the moments).
     Returns {launch kind: worst rel-L2}; info (a dict) receives the statistics of the inputs the launches read."""
-    L = _lib.lib()
     xd = x.cuda()
     nzd = noise.cuda() if noise is not None else None
-    run = _encode_run(vae, xd, image_res, vae_range, nzd)
-    _lib.check(L.hd_debug_limit_ops(vae._ctx, 0, 1), vae._ctx)
-    try:
-        run()                                                   # builds the program for these arguments
-    finally:
-        L.hd_debug_limit_ops(vae._ctx, 0, -1)
-    names = _names(L, vae._ctx, 0)
-    outs = _prefix_outputs(L, vae._ctx, 0, run, len(names))
-    ck = _Check(report, fp32_bound, bf16_bound)
+    names, outs = _prefix_outputs(PrefixRun(vae._ctx, _encode_run(vae, xd, image_res, vae_range, nzd)))
+    ck = _check(report, fp32_bound, bf16_bound)
     _scan(P, names, outs, x.shape[0], {"images": x, "vae_range": vae_range, "noise": noise}, ck, info if info is not None else {})
     # the last launch has two forms (vae_sample_kernel / vae_moments_kernel): the other one, in a whole run of its own
-    other = _encode_run(vae, xd, image_res, vae_range, None if nzd is not None else torch.zeros(x.shape[0], 4, image_res // 8, image_res // 8).cuda())
-    other()
-    n = len(names)
-    tail = [None] * (n - 2) + [_read_op(L, vae._ctx, 0, n - 2), _read_op(L, vae._ctx, 0, n - 1)]
-    Lr = image_res // 8
+    n, Lr = len(names), image_res // 8
+    _encode_run(vae, xd, image_res, vae_range, None if nzd is not None else torch.zeros(x.shape[0], 4, Lr, Lr).cuda())()
+    tail = [None] * (n - 2) + [read_op(vae._ctx, 0, n - 2), read_op(vae._ctx, 0, n - 1)]
     Xl = torch.zeros(x.shape[0], 1, Lr, Lr)                      # only its side is used by the rule
     _scan_last(P, names, tail, x.shape[0], {"noise": None if nzd is not None else torch.zeros(x.shape[0], 4, Lr, Lr)}, ck, {}, Xl)
     ck.worst["launches"] = n
@@ -311,17 +255,9 @@ def encode_scan(vae, P, x, image_res, report, noise=None, vae_range=False, info=
 
 def decode_scan(vae, P, z, report, info=None, fp32_bound=FP32_BOUND, bf16_bound=BF16_BOUND):
     """Every launch of hd_vae_decode(z [B,4,L,L] scaled latents)."""
-    L = _lib.lib()
     zd = z.cuda()
-    run = lambda: vae.decode_scaled(zd)                          # noqa: E731
-    _lib.check(L.hd_debug_limit_ops(vae._ctx, 0, 1), vae._ctx)
-    try:
-        run()
-    finally:
-        L.hd_debug_limit_ops(vae._ctx, 0, -1)
-    names = _names(L, vae._ctx, 1)
-    outs = _prefix_outputs(L, vae._ctx, 1, run, len(names))
-    ck = _Check(report, fp32_bound, bf16_bound)
+    names, outs = _prefix_outputs(PrefixRun(vae._ctx, lambda: vae.decode_scaled(zd), 1, 0))
+    ck = _check(report, fp32_bound, bf16_bound)
     _scan(P, names, outs, z.shape[0], {"latents": z}, ck, info if info is not None else {})
     ck.worst["launches"] = len(names)
     return ck.worst
@@ -331,37 +267,31 @@ def attention_prefix(vae, which, run, B, report, bf16_bound=BF16_BOUND):
     """The program run up to `...softmax_qk_v` only; Q, K, V are the to_q / to_k / to_v outputs (buffers of their own, written by
     nothing else, so one prefix run holds all four).  Returns (rel-L2 of the attention output against float64 rounded to bf16,
     attention_stats of the Q, K it read)."""
-    L = _lib.lib()
-    ctx = vae._ctx
+    pre = PrefixRun(vae._ctx, run, which, 0)
     try:
-        _lib.check(L.hd_debug_limit_ops(ctx, 0, 1), ctx)
-        run()
-        names = _names(L, ctx, which)
+        pre.run_to(1)
+        names = pre.names()
         s = next(i for i, n in enumerate(names) if n.endswith(".softmax_qk_v"))
         assert [n.split(".")[-1] for n in names[s - 3:s]] == ["to_q", "to_k", "to_v"], names[s - 3:s]
-        _lib.check(L.hd_debug_limit_ops(ctx, 0, s + 1), ctx)
-        run()
-        q, k, v = (_read_op(L, ctx, which, s - 3 + j).reshape(B, -1, 512) for j in range(3))
-        got = _read_op(L, ctx, which, s)
+        pre.run_to(s + 1)
+        qq, k, v = (pre.op(s - 3 + j).reshape(B, -1, 512) for j in range(3))
+        got = pre.op(s)
     finally:
-        L.hd_debug_limit_ops(ctx, 0, -1)
-    ck = _Check(report, FP32_BOUND, bf16_bound)
-    ck.rel(s, names[s], "softmax_qk_v", f"T={q.shape[1]}", got, _q64(attention64(q, k, v)).reshape(-1), True)
-    return ck.worst["softmax_qk_v"], attention_stats(q, k)
+        pre.reset()
+    ck = _check(report, FP32_BOUND, bf16_bound)
+    ck.rel(s, names[s], "softmax_qk_v", f"T={qq.shape[1]}", got, _q64(attention64(qq, k, v)).reshape(-1), True)
+    return ck.worst["softmax_qk_v"], attention_stats(qq, k)
 
 
 def first_op(vae, x, image_res, vae_range=False):
     """Launch 0 of the encode program alone (limit 1): the bicubic resize when x is not image_res wide, else encoder.input."""
-    L = _lib.lib()
-    ctx = vae._ctx
     xd = x.cuda()
+    pre = PrefixRun(vae._ctx, lambda: vae._encode(xd, image_res, vae_range, True, None, 0))
     try:
-        _lib.check(L.hd_debug_limit_ops(ctx, 0, 1), ctx)
-        vae._encode(xd, image_res, vae_range, True, None, 0)
-        name = L.hd_debug_op_name(ctx, 0, 0).decode()
-        return name, _read_op(L, ctx, 0, 0)
+        pre.run_to(1)
+        return pre.names()[0], pre.op(0)
     finally:
-        L.hd_debug_limit_ops(ctx, 0, -1)
+        pre.reset()
 
 
 def main():
