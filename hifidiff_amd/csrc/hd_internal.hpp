@@ -26,6 +26,7 @@
 #include "hd_gemm.hpp"
 #include "hd_kernels.hpp"
 #include "hd_end.hpp"
+#include "hd_faceset.hpp"
 #include "hd_vae.hpp"
 #include "hd_stage_api.hpp"
 
@@ -205,6 +206,64 @@ static_assert(!mode_is_rows(EvalMode::EpsShared) && !mode_is_rows(EvalMode::EpsF
 static_assert(mode_shared_row(EvalMode::EpsShared) && !mode_shared_row(EvalMode::EpsFaces) && mode_shared_row(EvalMode::LoopShared) && !mode_shared_row(EvalMode::LoopRows), "EvalMode table");
 static_assert(mode_allows_stages(EvalMode::EpsShared) && !mode_allows_stages(EvalMode::EpsFaces) && mode_allows_stages(EvalMode::LoopShared) && mode_allows_stages(EvalMode::LoopRows), "EvalMode table");
 
+// The per-face extras of the prepared batch.  Each owns its device buffers (context lifetime, sized by the batch in use, reached through
+// StepState: no graph holds these pointers), its cap or configuration and the host's copy of its flags, and answers the same four
+// questions: active -- does the next loop hand its pointers to StepState; fill -- the pointers of the chain whose first face is f0;
+// clear_all; clear_slots (the slot list on the host and, already uploaded, on the device).  What clears what, and when: the lifetime
+// table in hd_lib.hip.
+struct hd_ctx;
+// masked sampling (hd_mask_faces): the masks [B,L,L], known latents and their noise [B,4,L,L], the per-face flags and the slot list of a
+// call; `faces`: which faces carry a mask
+struct MaskState {
+    float *dmask = nullptr, *dknown = nullptr, *dnoise = nullptr;
+    int *on = nullptr, *slots = nullptr;
+    int cap = 0;
+    FaceSet faces;
+    bool active(const hd_ctx* c) const;
+    void fill(const hd_ctx* c, StepState& st, size_t f0) const;
+    int clear_all(hd_ctx* c, hipStream_t s);
+    int clear_slots(hd_ctx* c, int n, const int32_t* slots, const int* slots_dev, hipStream_t s);
+};
+// low-pass fidelity guidance (hd_guide_config / hd_guide_faces): the switch -- while it is on the step ends with guided_update_kernel, so
+// flipping it makes the captured step graphs stale -- the stored LP_N(g) [B,4,L,L], the weights [B] (0: not guided), block sizes [B], row
+// windows [2][cap], and the staged [n] arrays of a call (slots | weight | scale | row_from | row_to); `faces`: which faces are guided
+struct GuideState {
+    bool on = false;
+    float *lp = nullptr, *w = nullptr;
+    int *n = nullptr, *rows = nullptr, *args = nullptr;
+    int cap = 0;
+    FaceSet faces;
+    bool active(const hd_ctx* c) const;
+    void fill(const hd_ctx* c, StepState& st, size_t f0) const;
+    int clear_all(hd_ctx* c, hipStream_t s);
+    int clear_slots(hd_ctx* c, int n, const int32_t* slots, const int* slots_dev, hipStream_t s);
+};
+// progress previews (hd_preview_config): the configuration (it survives hd_prepare*), and the planes of the batch they were allocated for
+// (B faces, `planes` snapshot planes): x0 [B,4,L,L], snapshots [planes][B,4,L,L], rows [1 + planes][B] (latest, then one per snapshot
+// plane; -1: none) and the slot list of a read.  No host flags: a face's row says whether it has an estimate.
+struct PreviewState {
+    bool on = false;
+    int every = 1, snaps = 0, B = 0, planes = 0;
+    float *x0 = nullptr, *snap = nullptr;
+    int *row = nullptr, *slots = nullptr;
+    bool active(const hd_ctx* c) const;
+    void fill(const hd_ctx* c, StepState& st, size_t f0) const;
+    int clear_all(hd_ctx* c, hipStream_t s);
+    int clear_slots(hd_ctx* c, int n, const int32_t* slots, const int* slots_dev, hipStream_t s);
+    void free_planes(hd_ctx* c);
+};
+// the x0 history left by the last multistep call (the buffers are the chains' x0_hist): `valid`: hd_sample_rows_multistep resume = 1 may
+// continue the whole batch (record_history); `faces`: hd_sample_faces_multistep / hd_sample_spans resume[f] = 1 may continue face f.
+// Nothing of it goes through fill: a multistep call hands x0_hist to StepState itself.
+struct HistState {
+    bool valid = false;
+    FaceSet faces;
+    bool active(const hd_ctx*) const { return false; }
+    void fill(const hd_ctx*, StepState&, size_t) const {}
+    int clear_all(hd_ctx* c, hipStream_t s);
+    int clear_slots(hd_ctx* c, int n, const int32_t* slots, const int* slots_dev, hipStream_t s);
+};
+
 struct hd_ctx {
     int L = 16, device = 0, S = 1;            // S = L/16
     bool conditional = true;                  // false: the unconditional Denoiser (models/denoiser/model.py:32-134): no priors, HCAs or IDC
@@ -259,38 +318,11 @@ struct hd_ctx {
     // generations of the captured step graphs: invalidate_step_graphs bumps both; rows_gen (the per-face graphs, Chain::rows_gen) also
     // moves when film_pf grows, graphs_gen (the plain graphs, Workspace::graph_gen) does not
     unsigned rows_gen = 1, graphs_gen = 1;
-    // the x0 history left by the last multistep call (hd_sample_rows_multistep resume = 1 continues it): valid for batch hist_B until
-    // hd_prepare* or a single-step sampling call
-    bool hist_valid = false;
-    int hist_B = 0;
-    // the same per face (hd_sample_faces_multistep resume[f] = 1 needs hist_face[f]): [hist_B] flags, cleared where hist_valid is, per slot
-    // by hd_prepare_slots; set for every face that ran a row of a multistep rows / faces call
-    std::vector<char> hist_face;
-    // masked sampling (hd_mask_faces): the batch's masks [B,L,L], known latents and their noise [B,4,L,L], the per-face flags and the slot
-    // list of a call (sized by the batch like faces_dev, read through StepState: no graph holds these pointers).  mask_face: the host's copy of the flags
-    // ([B], empty: none set) -- sample_impl hands the buffers to StepState only while a face is masked.  Masks outlive hd_sample* calls;
-    // every hd_prepare* clears them all, hd_prepare_slots those of the slots it refills.
-    float *mask_dev = nullptr, *mask_known_dev = nullptr, *mask_noise_dev = nullptr;
-    int *mask_on_dev = nullptr, *mask_slots_dev = nullptr;
-    int mask_cap = 0;
-    std::vector<char> mask_face;
-    // progress previews (hd_preview_config): the configuration (it survives hd_prepare*), and the planes of the batch they were allocated
-    // for (pv_B faces, pv_planes snapshot planes): x0 [B,4,L,L], snapshots [pv_planes][B,4,L,L], rows [1 + pv_planes][B] (latest, then one
-    // per snapshot plane; -1: none) and the slot list of a read.  Read and written through StepState: no graph holds these pointers.
-    bool pv_on = false;
-    int pv_every = 1, pv_snaps = 0, pv_B = 0, pv_planes = 0;
-    float *pv_x0_dev = nullptr, *pv_snap_dev = nullptr;
-    int *pv_row_dev = nullptr, *pv_slots_dev = nullptr;
-    // low-pass fidelity guidance (hd_guide_config / hd_guide_faces): the switch -- while it is on the step ends with guided_update_kernel,
-    // so flipping it makes the captured step graphs stale -- and, sized by the batch like the mask buffers and read through StepState, the
-    // stored LP_N(g) [B,4,L,L], the weights [B] (0: not guided), block sizes [B] and row windows [2][guide_cap], and the staged [n] arrays
-    // of a call (slots | weight | scale | row_from | row_to).  guide_face: the host's copy of "is guided" ([B], empty: none).  Lifetime as
-    // for the masks: every hd_prepare* clears all faces, hd_prepare_slots those it refills.
-    bool guide_on = false;
-    float *guide_lp_dev = nullptr, *guide_w_dev = nullptr;
-    int *guide_n_dev = nullptr, *guide_rows_dev = nullptr, *guide_args_dev = nullptr;
-    int guide_cap = 0;
-    std::vector<char> guide_face;
+    // the per-face extras of the prepared batch (structs above; hd_lib.hip has their lifetime table)
+    MaskState mask;
+    GuideState guide;
+    PreviewState preview;
+    HistState hist;
     int graph_captures = 0;                   // step-graph instantiations of this context (hd_get_option "graph_captures")
     // persistent-stage launches recorded by the last one-step capture of each form (hd_get_option "sample_stage_launches",
     // "sample_face_stage_launches", "rows_stage_launches"); stage_count / face_stage_count count while a capture runs
@@ -412,6 +444,31 @@ void dev_free(hd_ctx* c, void* p) {
     for (auto& a : c->allocs)
         if (a == p) { a = nullptr; break; }
     (void)hipFree(p);
+}
+
+// A feature's device buffers for a new size: free, null, allocate, zero where asked.  On failure the feature is left with no buffers.
+struct BufSpec { char** p; size_t bytes; bool zero; };
+template <class T> BufSpec buf_spec(T** p, size_t count, bool zero) { return {reinterpret_cast<char**>(p), count * sizeof(T), zero}; }
+int realloc_buffers(hd_ctx* c, std::initializer_list<BufSpec> bufs, hipStream_t s) {
+    auto drop = [&] { for (const BufSpec& b : bufs) { dev_free(c, *b.p); *b.p = nullptr; } };
+    auto make = [&]() -> int {
+        for (const BufSpec& b : bufs) { const int rc = dev_alloc(c, b.p, b.bytes); if (rc) return rc; }
+        for (const BufSpec& b : bufs) if (b.zero) HIPCHECK(c, hipMemsetAsync(*b.p, 0, b.bytes, s));
+        return HD_OK;
+    };
+    drop();
+    const int rc = make();
+    if (rc) drop();
+    return rc;
+}
+// f(feature) for each per-face extra of the context, until one fails
+template <class F>
+int each_extra(hd_ctx* c, F f) {
+    int rc = f(c->mask);
+    if (!rc) rc = f(c->guide);
+    if (!rc) rc = f(c->preview);
+    if (!rc) rc = f(c->hist);
+    return rc;
 }
 
 // Points hd_ctx::ch at the chain the builder functions are to work on; the previous one is back on every exit of the scope.

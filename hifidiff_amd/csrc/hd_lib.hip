@@ -336,7 +336,7 @@ int build_denoiser_program(hd_ctx* c) {
                         };
         prog.push_back({"ending", [=](hipStream_t s) -> hipError_t {
                             const hipError_t e = ending_run(s);
-                            if (e != hipSuccess || !c->guide_on || !mode_is_loop(c->mode)) return e;
+                            if (e != hipSuccess || !c->guide.on || !mode_is_loop(c->mode)) return e;
                             const SchedArgs sa = sched_args();
                             GuideArgs g{};
                             g.lat = sa.lat; g.eps = eps; g.coef = sa.coef; g.st = sa.st; g.elem0 = sa.elem0; g.n_total = sa.n_total; g.L = L;
@@ -899,63 +899,126 @@ static int prepare_common(hd_ctx* c, int batch) {
     return alloc_workspace(c, batch);
 }
 
-static int masked_faces(const hd_ctx* c) {
-    int n = 0;
-    for (char m : c->mask_face) n += m != 0;
-    return n;
+// ---------------------------------------------------------------------------------- per-face extras: masks, guidance, previews, history
+// What each event does to each feature (MaskState, GuideState, PreviewState, HistState in hd_internal.hpp).  Two functions state it:
+// extras_clear_all (every hd_prepare*) and extras_clear_slots (a slot refill: hd_prepare_slots, hd_pool_commit); a further per-face
+// feature joins each_extra (hd_internal.hpp) and gets a column here.
+//   event             c->mask                  c->guide                      c->preview                               c->hist
+//   hd_prepare*       every face: no mask      every face: not guided        every face: rows -1, zeroed planes;      valid = false, no face has a history
+//                                                                            planes reallocated when the batch or
+//                                                                            the snapshot count has changed
+//   slot refill       its slots: no mask       its slots: not guided         its slots: rows -1, zeroed planes        its slots: no history; valid = false
+//   config off        (no switch)              hd_guide_config(0): every     hd_preview_config(0): planes freed       (no switch)
+//                                              face, as hd_prepare*
+//   hd_sample*        kept, read               kept, read                    written                                  rewritten (record_history)
+//   hd_pool_prepare   nothing                  nothing                       nothing                                  nothing
+// A clear launches device work only when a flag was set (the previews have no flags: theirs always runs while they are on).
+static int extras_clear_all(hd_ctx* c, hipStream_t s) { return each_extra(c, [&](auto& x) { return x.clear_all(c, s); }); }
+// the slot list is on the device already (the first n of ws->slots_dev); the flags are cleared in stream order
+static int extras_clear_slots(hd_ctx* c, int n, const int32_t* slots, hipStream_t s) {
+    return each_extra(c, [&](auto& x) { return x.clear_slots(c, n, slots, c->ws->slots_dev, s); });
 }
-// Progress previews (hd_preview_config): the planes are sized by the batch in use and the configuration, like the mask buffers.
-static void free_previews(hd_ctx* c) {
-    dev_free(c, c->pv_x0_dev); dev_free(c, c->pv_snap_dev); dev_free(c, c->pv_row_dev); dev_free(c, c->pv_slots_dev);
-    c->pv_x0_dev = c->pv_snap_dev = nullptr; c->pv_row_dev = c->pv_slots_dev = nullptr; c->pv_B = 0;
+static bool extras_active(hd_ctx* c) {
+    bool any = false;
+    each_extra(c, [&](auto& x) { any |= x.active(c); return HD_OK; });
+    return any;
 }
-// every face: no estimate (rows -1, zeroed planes); the planes are (re)allocated when the batch or the snapshot count has changed
-static int reset_previews(hd_ctx* c, hipStream_t s) {
-    if (!c->pv_on) return HD_OK;
-    const size_t B = (size_t)c->ws->B, per_face = (size_t)4 * c->L * c->L, planes = (size_t)c->pv_snaps;
-    if (c->pv_B != c->ws->B || c->pv_planes != c->pv_snaps) {
-        free_previews(c);
-        int rc = dev_alloc(c, &c->pv_x0_dev, B * per_face);
-        if (!rc) rc = dev_alloc(c, &c->pv_snap_dev, (planes ? planes : 1) * B * per_face);
-        if (!rc) rc = dev_alloc(c, &c->pv_row_dev, (1 + planes) * B);
-        if (!rc) rc = dev_alloc(c, &c->pv_slots_dev, B);
-        if (rc) { free_previews(c); return rc; }
-        c->pv_B = c->ws->B; c->pv_planes = c->pv_snaps;
+
+// The slots' flags of a set that is valid for the batch go to 0; was one of them set?
+static bool unset_slots(FaceSet& fs, int B, int n, const int32_t* slots) {
+    bool any = false;
+    for (int j = 0; j < n && fs.valid_for(B); ++j) { any |= fs.get(slots[j]); fs.set(slots[j], false); }
+    return any;
+}
+bool MaskState::active(const hd_ctx* c) const { return faces.any(c->ws->B); }
+void MaskState::fill(const hd_ctx* c, StepState& st, size_t f0) const {
+    const size_t ll = (size_t)c->L * c->L;
+    st.mask = dmask + f0 * ll; st.mask_known = dknown + f0 * 4 * ll;
+    st.mask_noise = dnoise + f0 * 4 * ll; st.mask_on = on + f0;
+}
+int MaskState::clear_all(hd_ctx* c, hipStream_t s) {
+    if (faces.count() > 0) HIPCHECK(c, hipMemsetAsync(on, 0, (size_t)cap * sizeof(int), s));
+    faces.drop();
+    return HD_OK;
+}
+int MaskState::clear_slots(hd_ctx* c, int n, const int32_t* slots_host, const int* slots_dev, hipStream_t s) {
+    if (!unset_slots(faces, c->ws->B, n, slots_host)) return HD_OK;
+    MaskScatterP mp{};
+    mp.on = on; mp.slots = slots_dev; mp.ll = c->L * c->L;
+    hipLaunchKernelGGL(mask_scatter_kernel, dim3(1, n), dim3(64), 0, s, mp);
+    HIPCHECK(c, hipGetLastError());
+    return HD_OK;
+}
+
+bool GuideState::active(const hd_ctx* c) const { return on && faces.any(c->ws->B); }
+void GuideState::fill(const hd_ctx* c, StepState& st, size_t f0) const {
+    st.gd_lp = lp + f0 * 4 * c->L * c->L; st.gd_w = w + f0; st.gd_n = n + f0;
+    st.gd_j0 = rows + f0; st.gd_j1 = rows + cap + f0;
+}
+int GuideState::clear_all(hd_ctx* c, hipStream_t s) {       // weight 0: not guided
+    if (faces.count() > 0) HIPCHECK(c, hipMemsetAsync(w, 0, (size_t)cap * sizeof(float), s));
+    faces.drop();
+    return HD_OK;
+}
+int GuideState::clear_slots(hd_ctx* c, int n_slots, const int32_t* slots_host, const int* slots_dev, hipStream_t s) {
+    if (!unset_slots(faces, c->ws->B, n_slots, slots_host)) return HD_OK;
+    GuideScatterP gp{};
+    gp.w = w; gp.slots = slots_dev;
+    hipLaunchKernelGGL(guide_scatter_kernel, dim3(1, n_slots), dim3(64), 0, s, gp);
+    HIPCHECK(c, hipGetLastError());
+    return HD_OK;
+}
+
+bool PreviewState::active(const hd_ctx* c) const { return on && x0 && B == c->ws->B && planes == snaps; }
+void PreviewState::fill(const hd_ctx* c, StepState& st, size_t f0) const {
+    const size_t per_face = (size_t)4 * c->L * c->L;
+    st.pv_x0 = x0 + f0 * per_face; st.pv_snap = snap + f0 * per_face; st.pv_row = row + f0;
+    st.pv_every = every; st.pv_snaps = snaps; st.pv_batch = c->ws->B;
+}
+void PreviewState::free_planes(hd_ctx* c) {
+    for (void* p : {(void*)x0, (void*)snap, (void*)row, (void*)slots}) dev_free(c, p);
+    x0 = snap = nullptr; row = slots = nullptr; B = 0;
+}
+// the planes are (re)allocated when the batch or the snapshot count has changed: B is the snapshot-plane stride
+int PreviewState::clear_all(hd_ctx* c, hipStream_t s) {
+    if (!on) return HD_OK;
+    const size_t nB = (size_t)c->ws->B, per_face = (size_t)4 * c->L * c->L, np = (size_t)snaps;
+    if (B != c->ws->B || planes != snaps) {
+        B = 0;
+        const int rc = realloc_buffers(c, {buf_spec(&x0, nB * per_face, false), buf_spec(&snap, (np ? np : 1) * nB * per_face, false),
+                                           buf_spec(&row, (1 + np) * nB, false), buf_spec(&slots, nB, false)}, s);
+        if (rc) return rc;
+        B = c->ws->B; planes = snaps;
     }
-    HIPCHECK(c, hipMemsetAsync(c->pv_x0_dev, 0, B * per_face * sizeof(float), s));
-    if (planes) HIPCHECK(c, hipMemsetAsync(c->pv_snap_dev, 0, planes * B * per_face * sizeof(float), s));
-    HIPCHECK(c, hipMemsetAsync(c->pv_row_dev, 0xff, (1 + planes) * B * sizeof(int), s));      // -1
+    HIPCHECK(c, hipMemsetAsync(x0, 0, nB * per_face * sizeof(float), s));
+    if (np) HIPCHECK(c, hipMemsetAsync(snap, 0, np * nB * per_face * sizeof(float), s));
+    HIPCHECK(c, hipMemsetAsync(row, 0xff, (1 + np) * nB * sizeof(int), s));      // -1
     return HD_OK;
 }
-static bool previews_ready(const hd_ctx* c) { return c->pv_on && c->pv_x0_dev && c->pv_B == c->ws->B && c->pv_planes == c->pv_snaps; }
-
-static int guided_faces(const hd_ctx* c) {
-    int n = 0;
-    for (char g : c->guide_face) n += g != 0;
-    return n;
-}
-// no face is guided any more (weight 0)
-static int clear_guidance(hd_ctx* c, hipStream_t s) {
-    if (guided_faces(c) > 0) HIPCHECK(c, hipMemsetAsync(c->guide_w_dev, 0, (size_t)c->guide_cap * sizeof(float), s));
-    c->guide_face.clear();
+int PreviewState::clear_slots(hd_ctx* c, int n, const int32_t*, const int* slots_dev, hipStream_t s) {
+    if (!active(c)) return HD_OK;
+    PreviewP pp{};
+    pp.x0 = x0; pp.snap = snap; pp.rows = row; pp.slots = slots_dev;
+    pp.B = c->ws->B; pp.snaps = snaps; pp.ll4 = 4 * c->L * c->L;
+    hipLaunchKernelGGL(preview_reset_kernel, dim3(4, n), dim3(256), 0, s, pp);
+    HIPCHECK(c, hipGetLastError());
     return HD_OK;
 }
 
-// every hd_prepare*: the new batch has no masks, no guidance and no previews
-static int clear_masks(hd_ctx* c, hipStream_t s) {
-    if (masked_faces(c) > 0) HIPCHECK(c, hipMemsetAsync(c->mask_on_dev, 0, (size_t)c->mask_cap * sizeof(int), s));
-    c->mask_face.clear();
-    { const int rc = clear_guidance(c, s); if (rc) return rc; }
-    return reset_previews(c, s);
+// a new batch has no multistep history to resume; a refilled face has none, and hd_sample_rows_multistep(resume = 1) no longer
+// continues the whole batch
+int HistState::clear_all(hd_ctx*, hipStream_t) { valid = false; faces.drop(); return HD_OK; }
+int HistState::clear_slots(hd_ctx* c, int n, const int32_t* slots_host, const int*, hipStream_t) {
+    unset_slots(faces, c->ws->B, n, slots_host);
+    valid = false;
+    return HD_OK;
 }
 
 // the common end of every hd_prepare*
 static int finish_prepare(hd_ctx* c, hipStream_t s) {
-    const int rc = clear_masks(c, s);
+    const int rc = extras_clear_all(c, s);
     if (rc) return rc;
     c->prepared = true;
-    c->hist_valid = false;                               // a new batch: no multistep history to resume
-    c->hist_face.clear();
     return HD_OK;
 }
 
@@ -1150,9 +1213,6 @@ static int stage_slots(hd_ctx* c, int* dev, const int32_t* slots, int n, hipStre
     return stage_submit(c, sg, s);
 }
 
-static bool any_guided(const hd_ctx* c) { return c->guide_on && c->guide_face.size() == (size_t)c->ws->B && guided_faces(c) > 0; }   // hd_guide_faces
-static bool any_mask(const hd_ctx* c) { return c->mask_face.size() == (size_t)c->ws->B && masked_faces(c) > 0; }   // hd_mask_faces
-
 static int grow_loop_buffers(hd_ctx* c, const SampleCall& call) {
     const int n = call.n;
     int rc = ensure_film_rows(c, n);
@@ -1193,8 +1253,7 @@ static int grow_loop_buffers(hd_ctx* c, const SampleCall& call) {
 static int stage_loop_state(hd_ctx* c, const SampleCall& call, bool upload_timesteps, hipStream_t s) {
     const int n = call.n;
     const bool ms = call.ncoef == 8, pf = call.start_rows != nullptr;
-    const bool mk = any_mask(c), pv = previews_ready(c), gd = any_guided(c);
-    const size_t nst = (ms || pf || mk || pv || gd) ? c->ws->chains.size() : 1;
+    const size_t nst = (ms || pf || extras_active(c)) ? c->ws->chains.size() : 1;
     StageCursor cur;
     const size_t coef0 = cur.take((size_t)n * 7 * sizeof(float)), ts0 = cur.take((size_t)n * sizeof(float));
     const size_t c70 = cur.take(ms ? (size_t)n * sizeof(float) : 0), st0 = cur.take(nst * sizeof(StepState));
@@ -1227,20 +1286,7 @@ static int stage_loop_state(hd_ctx* c, const SampleCall& call, bool upload_times
         if (call.face_seeds) st.face_seeds = dev.seeds + f0;
         if (call.first) st.face_first = dev.first + f0;
         if (call.begin_rows) { st.begin_rows = dev.begins + f0; st.end_rows = dev.ends + f0; }
-        if (mk) {
-            const size_t ll = (size_t)c->L * c->L;
-            st.mask = c->mask_dev + f0 * ll; st.mask_known = c->mask_known_dev + f0 * 4 * ll;
-            st.mask_noise = c->mask_noise_dev + f0 * 4 * ll; st.mask_on = c->mask_on_dev + f0;
-        }
-        if (pv) {
-            const size_t per_face = (size_t)4 * c->L * c->L;
-            st.pv_x0 = c->pv_x0_dev + f0 * per_face; st.pv_snap = c->pv_snap_dev + f0 * per_face; st.pv_row = c->pv_row_dev + f0;
-            st.pv_every = c->pv_every; st.pv_snaps = c->pv_snaps; st.pv_batch = c->ws->B;
-        }
-        if (gd) {
-            st.gd_lp = c->guide_lp_dev + f0 * 4 * c->L * c->L; st.gd_w = c->guide_w_dev + f0; st.gd_n = c->guide_n_dev + f0;
-            st.gd_j0 = c->guide_rows_dev + f0; st.gd_j1 = c->guide_rows_dev + c->guide_cap + f0;
-        }
+        each_extra(c, [&](auto& x) { if (x.active(c)) x.fill(c, st, f0); return HD_OK; });
         memcpy(host + st0 + k * sizeof(StepState), &st, sizeof(st));
     }
     if (pf) {                                             // one upload; an array the call did not give is zero and nothing reads it
@@ -1346,18 +1392,17 @@ static int replay_step_graphs(hd_ctx* c, bool pf, int n_iters, hipStream_t s) {
 
 // What a later hd_sample_rows_multistep(resume = 1) may continue, and per face what hd_sample_faces_multistep / hd_sample_spans
 // (resume[f] = 1) may: a whole-batch call leaves every face's history (multistep) or none; a multistep per-face call that of every face
-// that ran a row.  hist_valid after a rows-multistep call holds regardless of held faces; after a call with per-face flags
+// that ran a row.  hist.valid after a rows-multistep call holds regardless of held faces; after a call with per-face flags
 // (faces / spans) only when every face has a history.
 static void record_history(hd_ctx* c, const SampleCall& call) {
     const bool ms = call.ncoef == 8;
-    if (c->hist_B != c->ws->B || c->hist_face.size() != (size_t)c->ws->B) c->hist_face.assign((size_t)c->ws->B, 0);
-    if (ms && call.start_rows) {
-        for (int f = 0; f < c->ws->B; ++f) if (call.start_rows[f] < (call.end_rows ? call.end_rows[f] : call.n)) c->hist_face[f] = 1;
-    } else {
-        c->hist_face.assign((size_t)c->ws->B, ms ? 1 : 0);
-    }
-    c->hist_valid = ms; c->hist_B = c->ws->B;
-    if (ms && call.first) for (char h : c->hist_face) c->hist_valid = c->hist_valid && h;
+    const int B = c->ws->B;
+    FaceSet& hf = c->hist.faces;
+    const bool some = ms && call.start_rows;              // only the faces that ran a row gain a history; the others keep what they have
+    if (!some || !hf.valid_for(B)) hf.reset(B);
+    for (int f = 0; f < B && ms; ++f)
+        if (!some || call.start_rows[f] < (call.end_rows ? call.end_rows[f] : call.n)) hf.set(f, true);
+    c->hist.valid = ms && (!call.first || hf.all(B));
 }
 
 static int sample_impl(hd_ctx* c, float* x_inout, const SampleCall& call, void* stream) {
@@ -1421,8 +1466,7 @@ static int check_rows(hd_ctx* c, SampleCall& call, const int32_t* rows, int n_it
 // resume[f] of hd_sample_faces_multistep / hd_sample_spans: 0 or 1, and 1 only for a face that has a history; first_f = !resume_f
 static int check_face_resume(hd_ctx* c, const char* fn, int f, int32_t resume_f, int32_t* first_f) {
     if (resume_f != 0 && resume_f != 1) HD_FAIL(c, HD_ERR_INVALID, "%s: resume[%d] = %d is not 0 or 1", fn, f, resume_f);
-    const bool have = c->hist_B == c->ws->B && c->hist_face.size() == (size_t)c->ws->B;
-    if (resume_f && !(have && c->hist_face[f]))
+    if (resume_f && !(c->hist.faces.valid_for(c->ws->B) && c->hist.faces.get(f)))
         HD_FAIL(c, HD_ERR_INVALID, "%s: resume[%d] = 1 but face %d has no multistep history (no multistep row since "
                                    "hd_prepare*, hd_prepare_slots refilled it, or a single-step call in between)", fn, f, f);
     *first_f = resume_f ? 0 : 1;
@@ -1459,7 +1503,7 @@ int hd_sample_rows_multistep(hd_ctx* c, float* x_inout, const hd_schedule_ms* sc
     int rc = sample_enter(c, "hd_sample_rows_multistep", x_inout, as_rows_of_8(sched), 8, start_rows && (resume == 0 || resume == 1), noise, seed, call);
     if (!rc) rc = check_rows(c, call, start_rows, n_iters);
     if (rc) return rc;
-    if (resume && !(c->hist_valid && c->hist_B == c->ws->B))
+    if (resume && !(c->hist.valid && c->hist.faces.valid_for(c->ws->B)))
         HD_FAIL(c, HD_ERR_INVALID, "hd_sample_rows_multistep: resume = 1 but no multistep history of this batch (no earlier multistep call, "
                                    "hd_prepare since, another batch size or a single-step call in between)");
     call.resume = resume;
@@ -1610,42 +1654,6 @@ static int copy_conditioning(hd_ctx* c, int n, CondEnd from, const int* src_idx,
     HIPCHECK(c, hipGetLastError());
     return HD_OK;
 }
-// What a slot loses when it is given a new face: its mask, its guidance, its previews and its multistep history.  The slot list is
-// on the device already (the first n of ws->slots_dev); the flags are cleared in stream order.
-static int reset_slots(hd_ctx* c, int n, const int32_t* slots, hipStream_t s) {
-    if (c->mask_face.size() == (size_t)c->ws->B) {
-        bool any = false;
-        for (int j = 0; j < n; ++j) { any |= c->mask_face[slots[j]] != 0; c->mask_face[slots[j]] = 0; }
-        if (any) {
-            MaskScatterP mp{};
-            mp.on = c->mask_on_dev; mp.slots = c->ws->slots_dev; mp.ll = c->L * c->L;
-            hipLaunchKernelGGL(mask_scatter_kernel, dim3(1, n), dim3(64), 0, s, mp);
-            HIPCHECK(c, hipGetLastError());
-        }
-    }
-    if (c->guide_face.size() == (size_t)c->ws->B) {         // ... no guidance (weight 0)
-        bool any = false;
-        for (int j = 0; j < n; ++j) { any |= c->guide_face[slots[j]] != 0; c->guide_face[slots[j]] = 0; }
-        if (any) {
-            GuideScatterP gp{};
-            gp.w = c->guide_w_dev; gp.slots = c->ws->slots_dev;
-            hipLaunchKernelGGL(guide_scatter_kernel, dim3(1, n), dim3(64), 0, s, gp);
-            HIPCHECK(c, hipGetLastError());
-        }
-    }
-    if (previews_ready(c)) {                               // ... and no preview: row -1, zeroed planes
-        PreviewP pp{};
-        pp.x0 = c->pv_x0_dev; pp.snap = c->pv_snap_dev; pp.rows = c->pv_row_dev; pp.slots = c->ws->slots_dev;
-        pp.B = c->ws->B; pp.snaps = c->pv_snaps; pp.ll4 = 4 * c->L * c->L;
-        hipLaunchKernelGGL(preview_reset_kernel, dim3(4, n), dim3(256), 0, s, pp);
-        HIPCHECK(c, hipGetLastError());
-    }
-    // the refilled faces have no multistep history; hd_sample_rows_multistep(resume = 1) no longer continues the whole batch
-    if (c->hist_B == c->ws->B && c->hist_face.size() == (size_t)c->ws->B)
-        for (int j = 0; j < n; ++j) c->hist_face[slots[j]] = 0;
-    c->hist_valid = false;
-    return HD_OK;
-}
 // The checks the three entry points share: a conditional context with a prepared batch (and, for the pool calls, a pool).
 static int slots_enter(hd_ctx* c, const char* fn, bool need_pool) {
     if (!c) return HD_ERR_INVALID;
@@ -1674,7 +1682,7 @@ int hd_prepare_slots(hd_ctx* c, int n, const int32_t* slots, const float* cr_lat
     rc = stage_prologue(c, n, cr_latent, cr_face, id_emb, s);
     if (!rc) rc = stage_index_lists(c, slots, nullptr, n, s);
     if (!rc) rc = copy_conditioning(c, n, CondEnd::Staging, nullptr, CondEnd::Slots, c->ws->slots_dev, s);
-    if (!rc) rc = reset_slots(c, n, slots, s);
+    if (!rc) rc = extras_clear_slots(c, n, slots, s);
     return rc;
 }
 
@@ -1740,81 +1748,78 @@ int hd_pool_commit(hd_ctx* c, int n, const int32_t* slots, const int32_t* entrie
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     rc = stage_index_lists(c, slots, entries, n, s);
     if (!rc) rc = copy_conditioning(c, n, CondEnd::Pool, c->ws->slots_dev + n, CondEnd::Slots, c->ws->slots_dev, s);
-    if (!rc) rc = reset_slots(c, n, slots, s);
+    if (!rc) rc = extras_clear_slots(c, n, slots, s);
     return rc;
+}
+
+// What the per-face calls open with (hd_mask_faces, hd_guide_faces, hd_preview_read; the two config calls: loop_ctx_enter alone): a
+// context with a sampling loop and a prepared batch (not-ready comes before any argument error), n faces of it, and either no slot
+// list (the whole batch, in order) or n distinct slots.
+static int loop_ctx_enter(hd_ctx* c, const char* fn) {
+    if (!c) return HD_ERR_INVALID;
+    if (c->cr || c->vae) HD_FAIL(c, HD_ERR_INVALID, "%s: this context holds CoarseRestoration or the VAE (no sampling loop)", fn);
+    return HD_OK;
+}
+static int faces_enter(hd_ctx* c, const char* fn, int n, const int32_t* slots) {
+    int rc = loop_ctx_enter(c, fn);
+    if (!rc) rc = check_ready(c, true);
+    if (rc) return rc;
+    if (n < 1 || n > c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "%s: n = %d outside [1, %d]", fn, n, c->ws->B);
+    if (!slots && n != c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "%s: slots == NULL needs n == batch (%d), got %d", fn, c->ws->B, n);
+    return slots ? check_index_list(c, fn, "slots", slots, n, c->ws->B, true) : HD_OK;
 }
 
 // Give n faces of the prepared batch a mask, the known latent and its noise (or take their masks away: all three NULL).  The tensors are
 // copied in stream order into buffers of the context that the step kernels reach through StepState: no launch program is rebuilt and no
 // graph recaptured, and while no face is masked the loop's launches read nothing of this.
 int hd_mask_faces(hd_ctx* c, int n, const int32_t* slots, const float* mask, const float* known, const float* known_noise, void* stream) {
-    if (!c) return HD_ERR_INVALID;
-    if (c->cr || c->vae) HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: this context holds CoarseRestoration or the VAE (no sampling loop)");
-    int rc = check_ready(c, true);
+    int rc = faces_enter(c, "hd_mask_faces", n, slots);
     if (rc) return rc;
-    if (n < 1 || n > c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: n = %d outside [1, %d]", n, c->ws->B);
-    if (!slots && n != c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: slots == NULL needs n == batch (%d), got %d", c->ws->B, n);
     if ((!mask != !known) || (!mask != !known_noise))
         HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: give mask, known and known_noise together, or none of them (clear)");
-    if (slots) {
-        std::vector<char> seen((size_t)c->ws->B, 0);
-        for (int j = 0; j < n; ++j) {
-            if (slots[j] < 0 || slots[j] >= c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: slots[%d] = %d outside [0, %d)", j, slots[j], c->ws->B);
-            if (seen[slots[j]]) HD_FAIL(c, HD_ERR_INVALID, "hd_mask_faces: slot %d given twice", slots[j]);
-            seen[slots[j]] = 1;
-        }
-    }
-    if (c->mask_face.size() != (size_t)c->ws->B) c->mask_face.assign((size_t)c->ws->B, 0);
-    if (!mask && masked_faces(c) == 0) return HD_OK;       // nothing to clear
+    MaskState& m = c->mask;
+    const size_t B = (size_t)c->ws->B, ll = (size_t)c->L * c->L;
+    if (!m.faces.valid_for(c->ws->B)) m.faces.reset(c->ws->B);
+    if (!mask && m.faces.count() == 0) return HD_OK;       // nothing to clear
     HIPCHECK(c, hipSetDevice(c->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const size_t ll = (size_t)c->L * c->L;
-    if (c->ws->B > c->mask_cap) {                              // a larger batch than ever masked: hd_prepare* has cleared every mask since
-        dev_free(c, c->mask_dev); dev_free(c, c->mask_known_dev); dev_free(c, c->mask_noise_dev);
-        dev_free(c, c->mask_on_dev); dev_free(c, c->mask_slots_dev);
-        c->mask_dev = c->mask_known_dev = c->mask_noise_dev = nullptr; c->mask_on_dev = c->mask_slots_dev = nullptr; c->mask_cap = 0;
-        rc = dev_alloc(c, &c->mask_dev, (size_t)c->ws->B * ll);
-        if (!rc) rc = dev_alloc(c, &c->mask_known_dev, (size_t)c->ws->B * 4 * ll);
-        if (!rc) rc = dev_alloc(c, &c->mask_noise_dev, (size_t)c->ws->B * 4 * ll);
-        if (!rc) rc = dev_alloc(c, &c->mask_on_dev, (size_t)c->ws->B);
-        if (!rc) rc = dev_alloc(c, &c->mask_slots_dev, (size_t)c->ws->B);
+    if (c->ws->B > m.cap) {                                // a larger batch than ever masked: hd_prepare* has cleared every mask since
+        m.cap = 0;
+        rc = realloc_buffers(c, {buf_spec(&m.dmask, B * ll, true), buf_spec(&m.dknown, B * 4 * ll, true), buf_spec(&m.dnoise, B * 4 * ll, true),
+                                 buf_spec(&m.on, B, true), buf_spec(&m.slots, B, false)}, s);
         if (rc) return rc;
-        c->mask_cap = c->ws->B;
-        HIPCHECK(c, hipMemsetAsync(c->mask_dev, 0, (size_t)c->ws->B * ll * sizeof(float), s));
-        HIPCHECK(c, hipMemsetAsync(c->mask_known_dev, 0, (size_t)c->ws->B * 4 * ll * sizeof(float), s));
-        HIPCHECK(c, hipMemsetAsync(c->mask_noise_dev, 0, (size_t)c->ws->B * 4 * ll * sizeof(float), s));
-        HIPCHECK(c, hipMemsetAsync(c->mask_on_dev, 0, (size_t)c->ws->B * sizeof(int), s));
+        m.cap = c->ws->B;
     }
     if (slots) {
-        rc = stage_slots(c, c->mask_slots_dev, slots, n, s);
+        rc = stage_slots(c, m.slots, slots, n, s);
         if (rc) return rc;
     }
     MaskScatterP p{};
     p.mask = mask; p.known = known; p.noise = known_noise;
-    p.dmask = c->mask_dev; p.dknown = c->mask_known_dev; p.dnoise = c->mask_noise_dev;
-    p.on = c->mask_on_dev; p.slots = slots ? c->mask_slots_dev : nullptr; p.ll = (int)ll;
+    p.dmask = m.dmask; p.dknown = m.dknown; p.dnoise = m.dnoise;
+    p.on = m.on; p.slots = slots ? m.slots : nullptr; p.ll = (int)ll;
     hipLaunchKernelGGL(mask_scatter_kernel, dim3(mask ? 4 : 1, n), dim3(256), 0, s, p);
     HIPCHECK(c, hipGetLastError());
-    for (int j = 0; j < n; ++j) c->mask_face[slots ? slots[j] : j] = mask ? 1 : 0;
+    for (int j = 0; j < n; ++j) m.faces.set(slots ? slots[j] : j, mask != nullptr);
     return HD_OK;
 }
 
 // Low-pass fidelity guidance.  The switch decides whether the captured step ends with guided_update_kernel: flipping it makes the step
 // graphs stale (one recapture at the next loop), and with it off no launch, graph or bit differs from a context that never had it on.
 int hd_guide_config(hd_ctx* c, int on) {
-    if (!c) return HD_ERR_INVALID;
-    if (c->cr || c->vae) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_config: this context holds CoarseRestoration or the VAE (no sampling loop)");
+    int rc = loop_ctx_enter(c, "hd_guide_config");
+    if (rc) return rc;
     if (on != 0 && on != 1) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_config: on = %d is not 0 or 1", on);
-    if (c->guide_on == (on != 0)) return HD_OK;
-    if (!on && guided_faces(c) > 0) {                      // switching off clears every face (the weights in stream order of the null stream)
+    if (c->guide.on == (on != 0)) return HD_OK;
+    if (!on && c->guide.faces.count() > 0) {               // switching off clears every face (the weights in stream order of the null stream)
         HIPCHECK(c, hipSetDevice(c->device));
         HIPCHECK(c, hipDeviceSynchronize());               // a loop in flight may still read them
-        const int rc = clear_guidance(c, nullptr);
+        rc = c->guide.clear_all(c, nullptr);
         if (rc) return rc;
         HIPCHECK(c, hipStreamSynchronize(nullptr));
     }
-    c->guide_face.clear();
-    c->guide_on = on != 0;
+    c->guide.faces.drop();
+    c->guide.on = on != 0;
     invalidate_step_graphs(c);                             // the ending op launches one kernel more, or one fewer
     return HD_OK;
 }
@@ -1824,22 +1829,11 @@ int hd_guide_config(hd_ctx* c, int on) {
 // row windows: no launch program is rebuilt and no graph recaptured by setting, changing or clearing faces.
 int hd_guide_faces(hd_ctx* c, int n, const int32_t* slots, const float* target, const float* weight, const int32_t* scale,
                    const int32_t* row_from, const int32_t* row_to, void* stream) {
-    if (!c) return HD_ERR_INVALID;
-    if (c->cr || c->vae) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: this context holds CoarseRestoration or the VAE (no sampling loop)");
-    int rc = check_ready(c, true);
+    int rc = faces_enter(c, "hd_guide_faces", n, slots);
     if (rc) return rc;
-    if (n < 1 || n > c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: n = %d outside [1, %d]", n, c->ws->B);
-    if (!slots && n != c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: slots == NULL needs n == batch (%d), got %d", c->ws->B, n);
-    if (slots) {
-        std::vector<char> seen((size_t)c->ws->B, 0);
-        for (int j = 0; j < n; ++j) {
-            if (slots[j] < 0 || slots[j] >= c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: slots[%d] = %d outside [0, %d)", j, slots[j], c->ws->B);
-            if (seen[slots[j]]) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: slot %d given twice", slots[j]);
-            seen[slots[j]] = 1;
-        }
-    }
+    GuideState& g = c->guide;
     if (target) {
-        if (!c->guide_on) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: guidance is switched off (hd_guide_config(ctx, 1) first)");
+        if (!g.on) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: guidance is switched off (hd_guide_config(ctx, 1) first)");
         if (!weight || !scale) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: a target needs weight and scale");
         if (!row_from != !row_to) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: give row_from and row_to together, or neither (all rows)");
         if (c->L > kGuideMaxL) HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: latent %d is larger than %d", c->L, kGuideMaxL);
@@ -1851,25 +1845,17 @@ int hd_guide_faces(hd_ctx* c, int n, const int32_t* slots, const float* target, 
                 HD_FAIL(c, HD_ERR_INVALID, "hd_guide_faces: rows [%d, %d) of face %d: need 0 <= row_from < row_to", row_from[j], row_to[j], j);
         }
     }
-    if (c->guide_face.size() != (size_t)c->ws->B) c->guide_face.assign((size_t)c->ws->B, 0);
-    if (!target && guided_faces(c) == 0) return HD_OK;     // nothing to clear
+    if (!g.faces.valid_for(c->ws->B)) g.faces.reset(c->ws->B);
+    if (!target && g.faces.count() == 0) return HD_OK;     // nothing to clear
     HIPCHECK(c, hipSetDevice(c->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const size_t B = (size_t)c->ws->B, ll = (size_t)c->L * c->L;
-    if (c->ws->B > c->guide_cap) {                         // a larger batch than ever guided: hd_prepare* has cleared every face since
-        dev_free(c, c->guide_lp_dev); dev_free(c, c->guide_w_dev); dev_free(c, c->guide_n_dev); dev_free(c, c->guide_rows_dev); dev_free(c, c->guide_args_dev);
-        c->guide_lp_dev = c->guide_w_dev = nullptr; c->guide_n_dev = c->guide_rows_dev = c->guide_args_dev = nullptr; c->guide_cap = 0;
-        rc = dev_alloc(c, &c->guide_lp_dev, B * 4 * ll);
-        if (!rc) rc = dev_alloc(c, &c->guide_w_dev, B);
-        if (!rc) rc = dev_alloc(c, &c->guide_n_dev, B);
-        if (!rc) rc = dev_alloc(c, &c->guide_rows_dev, 2 * B);
-        if (!rc) rc = dev_alloc(c, &c->guide_args_dev, 5 * B);
+    if (c->ws->B > g.cap) {                                // a larger batch than ever guided: hd_prepare* has cleared every face since
+        g.cap = 0;
+        rc = realloc_buffers(c, {buf_spec(&g.lp, B * 4 * ll, true), buf_spec(&g.w, B, true), buf_spec(&g.n, B, true),
+                                 buf_spec(&g.rows, 2 * B, true), buf_spec(&g.args, 5 * B, false)}, s);
         if (rc) return rc;
-        c->guide_cap = c->ws->B;
-        HIPCHECK(c, hipMemsetAsync(c->guide_lp_dev, 0, B * 4 * ll * sizeof(float), s));
-        HIPCHECK(c, hipMemsetAsync(c->guide_w_dev, 0, B * sizeof(float), s));
-        HIPCHECK(c, hipMemsetAsync(c->guide_n_dev, 0, B * sizeof(int), s));
-        HIPCHECK(c, hipMemsetAsync(c->guide_rows_dev, 0, 2 * B * sizeof(int), s));
+        g.cap = c->ws->B;
     }
     // the call's host arrays through the pinned staging buffer: slots | weight | scale | row_from | row_to, [n] each
     {
@@ -1885,18 +1871,18 @@ int hd_guide_faces(hd_ctx* c, int n, const int32_t* slots, const float* target, 
             h[3 * n + j] = (target && row_from) ? row_from[j] : 0;
             h[4 * n + j] = (target && row_from) ? row_to[j] : 0x7fffffff;
         }
-        HIPCHECK(c, hipMemcpyAsync(c->guide_args_dev, h, (size_t)5 * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIPCHECK(c, hipMemcpyAsync(g.args, h, (size_t)5 * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
         rc = stage_submit(c, sg, s);
         if (rc) return rc;
     }
     GuideScatterP p{};
-    p.target = target; p.lp = c->guide_lp_dev; p.w = c->guide_w_dev; p.n = c->guide_n_dev;
-    p.j0 = c->guide_rows_dev; p.j1 = c->guide_rows_dev + c->guide_cap;
-    p.slots = c->guide_args_dev; p.weight = reinterpret_cast<const float*>(c->guide_args_dev + n);
-    p.scale = c->guide_args_dev + 2 * n; p.row_from = c->guide_args_dev + 3 * n; p.row_to = c->guide_args_dev + 4 * n; p.L = c->L;
+    p.target = target; p.lp = g.lp; p.w = g.w; p.n = g.n;
+    p.j0 = g.rows; p.j1 = g.rows + g.cap;
+    p.slots = g.args; p.weight = reinterpret_cast<const float*>(g.args + n);
+    p.scale = g.args + 2 * n; p.row_from = g.args + 3 * n; p.row_to = g.args + 4 * n; p.L = c->L;
     hipLaunchKernelGGL(guide_scatter_kernel, dim3(target ? 4 : 1, n), dim3(256), target ? guide_lds_bytes(c->L) : 0, s, p);
     HIPCHECK(c, hipGetLastError());
-    for (int j = 0; j < n; ++j) c->guide_face[slots ? slots[j] : j] = target ? 1 : 0;
+    for (int j = 0; j < n; ++j) g.faces.set(slots ? slots[j] : j, target != nullptr);
     return HD_OK;
 }
 
@@ -1904,55 +1890,46 @@ int hd_guide_faces(hd_ctx* c, int n, const int32_t* slots, const float* target, 
 // kernels.  The planes belong to the context and are reached through StepState, like the masks: switching them on or off rebuilds no
 // launch program and recaptures no graph, and while they are off the loop's launches read and write nothing of this.
 int hd_preview_config(hd_ctx* c, int on, int every, int snapshots) {
-    if (!c) return HD_ERR_INVALID;
-    if (c->cr || c->vae) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_config: this context holds CoarseRestoration or the VAE (no sampling loop)");
+    int rc = loop_ctx_enter(c, "hd_preview_config");
+    if (rc) return rc;
     if (on != 0 && on != 1) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_config: on = %d is not 0 or 1", on);
     if (every < 1) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_config: every = %d must be >= 1", every);
     if (snapshots < 0 || snapshots > 64) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_config: snapshots = %d outside [0, 64]", snapshots);
     HIPCHECK(c, hipSetDevice(c->device));
-    c->pv_on = on != 0; c->pv_every = every; c->pv_snaps = snapshots;
+    PreviewState& pv = c->preview;
+    pv.on = on != 0; pv.every = every; pv.snaps = snapshots;
     if (!on) {
-        if (c->pv_x0_dev) HIPCHECK(c, hipDeviceSynchronize());      // a loop in flight may still write them
-        free_previews(c);
+        if (pv.x0) HIPCHECK(c, hipDeviceSynchronize());            // a loop in flight may still write them
+        pv.free_planes(c);
         return HD_OK;
     }
     if (!c->finalized || !c->prepared) return HD_OK;         // allocated by the next hd_prepare*
     HIPCHECK(c, hipDeviceSynchronize());
-    const int rc = reset_previews(c, nullptr);
+    rc = pv.clear_all(c, nullptr);
     if (rc) return rc;
     HIPCHECK(c, hipStreamSynchronize(nullptr));              // the chains' queues do not wait for the null stream
     return HD_OK;
 }
 
 int hd_preview_read(hd_ctx* c, int n, const int32_t* slots, int snapshot, float* x0_out, int32_t* rows_out, void* stream) {
-    if (!c) return HD_ERR_INVALID;
-    int rc = check_ready(c, true);
+    int rc = faces_enter(c, "hd_preview_read", n, slots);
     if (rc) return rc;
-    if (!previews_ready(c)) HD_FAIL(c, HD_ERR_NOT_READY, "hd_preview_read: previews are off (hd_preview_config)");
+    const PreviewState& pv = c->preview;
+    if (!pv.active(c)) HD_FAIL(c, HD_ERR_NOT_READY, "hd_preview_read: previews are off (hd_preview_config)");
     if (!x0_out) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: x0_out is NULL");
-    if (n < 1 || n > c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: n = %d outside [1, %d]", n, c->ws->B);
-    if (!slots && n != c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: slots == NULL needs n == batch (%d), got %d", c->ws->B, n);
-    if (snapshot < -1 || snapshot >= c->pv_snaps)
-        HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: snapshot = %d outside [-1, %d)", snapshot, c->pv_snaps);
-    if (slots) {
-        std::vector<char> seen((size_t)c->ws->B, 0);
-        for (int j = 0; j < n; ++j) {
-            if (slots[j] < 0 || slots[j] >= c->ws->B) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: slots[%d] = %d outside [0, %d)", j, slots[j], c->ws->B);
-            if (seen[slots[j]]) HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: slot %d given twice", slots[j]);
-            seen[slots[j]] = 1;
-        }
-    }
+    if (snapshot < -1 || snapshot >= pv.snaps)
+        HD_FAIL(c, HD_ERR_INVALID, "hd_preview_read: snapshot = %d outside [-1, %d)", snapshot, pv.snaps);
     HIPCHECK(c, hipSetDevice(c->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (slots) {
-        rc = stage_slots(c, c->pv_slots_dev, slots, n, s);
+        rc = stage_slots(c, pv.slots, slots, n, s);
         if (rc) return rc;
     }
     const size_t per_face = (size_t)4 * c->L * c->L;
     PreviewReadP p{};
-    p.plane = snapshot < 0 ? c->pv_x0_dev : c->pv_snap_dev + (size_t)snapshot * c->ws->B * per_face;
-    p.rows = c->pv_row_dev + (size_t)(1 + snapshot) * c->ws->B;
-    p.slots = slots ? c->pv_slots_dev : nullptr; p.out = x0_out; p.rows_out = rows_out; p.ll4 = (int)per_face;
+    p.plane = snapshot < 0 ? pv.x0 : pv.snap + (size_t)snapshot * c->ws->B * per_face;
+    p.rows = pv.row + (size_t)(1 + snapshot) * c->ws->B;
+    p.slots = slots ? pv.slots : nullptr; p.out = x0_out; p.rows_out = rows_out; p.ll4 = (int)per_face;
     hipLaunchKernelGGL(preview_gather_kernel, dim3(4, n), dim3(256), 0, s, p);
     HIPCHECK(c, hipGetLastError());
     return HD_OK;
@@ -2018,34 +1995,24 @@ static const std::pair<void*, std::pair<size_t, int>>* find_debug(hd_ctx* c, con
 
 int64_t hd_debug_read(hd_ctx* c, const char* name, float* host_out, int64_t max_elems) {
     if (!c || !name) return HD_ERR_INVALID;
-    {                                                      // the mask buffers belong to the context, not to a workspace: sized by the batch in use
-        const std::string k = name;
-        const bool m = k == "mask", mkn = k == "mask_known", mnz = k == "mask_noise";
-        if (m || mkn || mnz) {
-            if (!c->mask_dev || c->ws->B < 1 || c->ws->B > c->mask_cap) HD_FAIL(c, HD_ERR_INVALID, "debug buffer %s: no mask has been set for this batch", name);
-            const size_t ll = (size_t)c->L * c->L;
-            return read_to_host(c, m ? c->mask_dev : mkn ? c->mask_known_dev : c->mask_noise_dev, (size_t)c->ws->B * (m ? ll : 4 * ll), 0, host_out, max_elems);
-        }
-    }
-    {                                                      // the guidance buffers too (guide_scale: the int32 block sizes as they are, 4 bytes each)
-        const std::string k = name;
-        const bool gl = k == "guide_lp", gw = k == "guide_weight", gs = k == "guide_scale";
-        if (gl || gw || gs) {
-            if (!c->guide_lp_dev || c->ws->B < 1 || c->ws->B > c->guide_cap) HD_FAIL(c, HD_ERR_INVALID, "debug buffer %s: no guidance has been set for this batch", name);
-            return read_to_host(c, gl ? (const void*)c->guide_lp_dev : gw ? (const void*)c->guide_w_dev : (const void*)c->guide_n_dev,
-                                gl ? (size_t)c->ws->B * 4 * c->L * c->L : (size_t)c->ws->B, 0, host_out, max_elems);
-        }
-    }
-    {                                                      // the preview planes too (preview_rows: the int32 rows as they are, 4 bytes each)
-        const std::string k = name;
-        const bool px = k == "x0_preview", pr = k == "preview_rows", ps = k == "preview_snaps";
-        if (px || pr || ps) {
-            if (!previews_ready(c)) HD_FAIL(c, HD_ERR_INVALID, "debug buffer %s: previews are off or no batch has been prepared since", name);
-            const size_t n = (size_t)c->ws->B * 4 * c->L * c->L;
-            if (ps && c->pv_snaps == 0) return 0;
-            return read_to_host(c, px ? (const void*)c->pv_x0_dev : pr ? (const void*)c->pv_row_dev : (const void*)c->pv_snap_dev,
-                                px ? n : pr ? (size_t)c->ws->B : (size_t)c->pv_snaps * n, 0, host_out, max_elems);
-        }
+    // the per-face extras belong to the context, not to a workspace: sized by the batch in use (guide_scale, preview_rows: the int32
+    // values as they are, 4 bytes each)
+    const size_t B = (size_t)c->ws->B, ll = (size_t)c->L * c->L;
+    const bool mk = c->mask.dmask && c->ws->B >= 1 && c->ws->B <= c->mask.cap, gd = c->guide.lp && c->ws->B >= 1 && c->ws->B <= c->guide.cap;
+    const bool pv = c->preview.active(c);
+    const char *no_mask = "no mask has been set for this batch", *no_guide = "no guidance has been set for this batch";
+    const char* no_pv = "previews are off or no batch has been prepared since";
+    const struct { const char* name; const void* ptr; size_t elems; bool ok; const char* why; } extras[] = {
+        {"mask", c->mask.dmask, B * ll, mk, no_mask}, {"mask_known", c->mask.dknown, B * 4 * ll, mk, no_mask},
+        {"mask_noise", c->mask.dnoise, B * 4 * ll, mk, no_mask},
+        {"guide_lp", c->guide.lp, B * 4 * ll, gd, no_guide}, {"guide_weight", c->guide.w, B, gd, no_guide}, {"guide_scale", c->guide.n, B, gd, no_guide},
+        {"x0_preview", c->preview.x0, B * 4 * ll, pv, no_pv}, {"preview_rows", c->preview.row, B, pv, no_pv},
+        {"preview_snaps", c->preview.snap, (size_t)c->preview.snaps * B * 4 * ll, pv, no_pv},
+    };
+    for (const auto& x : extras) {
+        if (strcmp(name, x.name) != 0) continue;
+        if (!x.ok) HD_FAIL(c, HD_ERR_INVALID, "debug buffer %s: %s", name, x.why);
+        return x.elems ? read_to_host(c, x.ptr, x.elems, 0, host_out, max_elems) : 0;      // preview_snaps without snapshot planes
     }
     const auto* e = find_debug(c, name);
     if (!e) HD_FAIL(c, HD_ERR_INVALID, "unknown debug buffer %s", name);
@@ -2102,10 +2069,10 @@ int hd_get_option(hd_ctx* c, const char* key) {
     if (k == "sample_stage_launches") return c->sample_stages;
     if (k == "sample_face_stage_launches") return c->sample_face_stages;
     if (k == "rows_stage_launches") return c->rows_stages;
-    if (k == "masked_faces") return c->mask_face.size() == (size_t)c->ws->B ? masked_faces(c) : 0;   // faces that carry a mask (hd_mask_faces)
-    if (k == "preview") return c->pv_on ? 1 : 0;                 // hd_preview_config
-    if (k == "guide") return c->guide_on ? 1 : 0;                // hd_guide_config
-    if (k == "guided_faces") return c->guide_face.size() == (size_t)c->ws->B ? guided_faces(c) : 0;   // faces that are guided (hd_guide_faces)
+    if (k == "masked_faces") return c->mask.faces.valid_for(c->ws->B) ? c->mask.faces.count() : 0;   // faces that carry a mask (hd_mask_faces)
+    if (k == "preview") return c->preview.on ? 1 : 0;                 // hd_preview_config
+    if (k == "guide") return c->guide.on ? 1 : 0;                // hd_guide_config
+    if (k == "guided_faces") return c->guide.faces.valid_for(c->ws->B) ? c->guide.faces.count() : 0;   // faces that are guided (hd_guide_faces)
     if (k == "pool_capacity") return c->pool_cap;                // hd_pool_config
     if (k == "pool_valid") { int n = 0; for (char v : c->pool_ok) n += v != 0; return n; }   // entries that hold a prepared face
     if (k == "graph_captures") return c->graph_captures;         // step graphs instantiated by this context (hd_prepare_slots adds none)

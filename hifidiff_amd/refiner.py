@@ -50,6 +50,10 @@ def _f32c(t, device):
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
+def _i32p(t):
+    return None if t is None else ctypes.cast(t.data_ptr(), ctypes.POINTER(ctypes.c_int32))
+
+
 def _version(t):
     """Version counter of a tensor, or None for tensors that do not track one (created under torch.inference_mode():
     reading `_version` raises there).  None never matches a cached key, so such tensors are re-prepared on every call."""
@@ -181,49 +185,6 @@ def preview_args(every, snapshots):
     return every, snapshots
 
 
-class _Previews:
-    """model.enable_previews / disable_previews / previews of both model classes (they share the engine's methods)."""
-
-    def enable_previews(self, every=1, snapshots=0):
-        """Progress previews: from now on every sampling.sample call also stores each face's denoised estimate x0 of the row it last ran
-        (diffusers' pred_original_sample; a masked face: blended with its known latent), and the estimate of every `every`-th row of the
-        face's own schedule in one of `snapshots` (0..64) snapshot planes.  The final latents do not change by a bit and nothing is
-        recaptured.  A new prepare resets the previews, prepare_slots those of its slots; the setting stays until disable_previews().
-        ValueError for every < 1 or snapshots outside [0, 64]."""
-        self._engine.enable_previews(every, snapshots)
-
-    def disable_previews(self):
-        """Switch the previews off and free their buffers."""
-        self._engine.disable_previews()
-
-    def previews(self, slots=None, snapshot=None):
-        """(x0 [n,4,L,L] fp32, rows [n] int32) on the model's device, in stream order: the latest estimate (snapshot=None) or snapshot
-        plane `snapshot` of the prepared batch's faces in `slots` (None: all, in order), and the table row each was taken at -- -1 (and a
-        zero plane) for a face that has not written it since it was prepared or refilled."""
-        return self._engine.previews(slots, snapshot)
-
-
-class _Guidance:
-    """model.set_guidance / clear_guidance / disable_guidance of both model classes (they share the engine's methods)."""
-
-    def set_guidance(self, target, weight, scale, rows=None, slots=None):
-        """Low-pass fidelity guidance: from now on every sampling.sample call pulls the denoised estimate of the prepared batch's faces in
-        `slots` (None: all, in order) towards `target` [n,4,L,L] in the low frequencies -- x0 <- x0 + w (LP_N(target) - LP_N(x0)) on the rows
-        `rows` = (j0, j1) of each face's own schedule (None: all rows) -- with weight w in (0, 1] (a float or [n]) and block size N = scale,
-        a divisor of L (an int or [n]); sampling.low_pass is LP_N.  Switches guidance on for the model when needed (one recapture of the
-        step graphs); the faces stay guided until clear_guidance, the next prepare of a batch, or prepare_slots of their slot.  ValueError
-        for wrong shapes, a weight outside (0, 1], a scale that does not divide L, or rows without 0 <= j0 < j1."""
-        self._engine.set_guidance(target, weight, scale, rows, slots)
-
-    def clear_guidance(self, slots=None):
-        """Stop guiding the faces in `slots` (None: every face); guidance stays switched on."""
-        self._engine.clear_guidance(slots)
-
-    def disable_guidance(self):
-        """Stop guiding every face and switch guidance off: the step loses its extra launch again (one recapture of the step graphs)."""
-        self._engine.disable_guidance()
-
-
 class _Engine:
     """Owns the hd_ctx of one (latent_res, device)."""
 
@@ -329,45 +290,49 @@ class _Engine:
         if self.ctx is None or not self.loaded:
             raise RuntimeError("weights are not loaded: call load_state_dict(...) and move the model to a cuda device")
 
-    # ---- C-ABI calls ----
-    def prepare(self, cr_latent, cr_face=None, id_emb=None):
-        self.require_loaded()
-        B = cr_latent.shape[0]
-        L = self.latent_res
-        if tuple(cr_latent.shape) != (B, 4, L, L):
-            raise RuntimeError("cr_latent must be (B,4,%d,%d), got %s" % (L, L, tuple(cr_latent.shape)))
-        if cr_face is not None and tuple(cr_face.shape) != (B, 3, 128, 128):
-            raise RuntimeError("cr_face must be (B,3,128,128), got %s" % (tuple(cr_face.shape),))
-        crl = _f32c(cr_latent, self.device)
-        crf = _f32c(cr_face, self.device) if cr_face is not None else None
-        emb = _f32c(id_emb.reshape(B, -1), self.device) if id_emb is not None else None
-        if emb is not None and emb.shape[1] != 2048:
-            raise RuntimeError("identity embedding must have 2048 features")
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().hd_prepare(self.ctx, B, crl.data_ptr(), crf.data_ptr() if crf is not None else None,
-                                             emb.data_ptr() if emb is not None else None, _stream(self.device)), self.ctx)
-        self.batch, self.cond_key, self.prior_key = B, None, None
-
-    def prepare_slots(self, slots, cr_latent, cr_face=None, id_emb=None):
-        """hd_prepare_slots: replace the conditioning of the prepared batch's faces in `slots` (n distinct ints in [0, B))."""
-        self.require_loaded()
+    def _faces(self, slots):
+        """The faces a per-face call names: (n, int32 pointer or None, the int32 CPU tensor behind the pointer -- keep it until the call
+        has returned).  slots None: the whole prepared batch, in order (n is None while no batch is prepared)."""
+        if slots is None:
+            return self.batch, None, None
         sl = slots_arg(slots, self.batch)
-        n, L = sl.numel(), self.latent_res
+        return sl.numel(), _i32p(sl), sl
+
+    def _call(self, fn, *args):
+        """One C-ABI call on this engine's context and device; a negative return raises with hd_last_error."""
+        with torch.cuda.device(self.device):
+            return _lib.check(getattr(_lib.lib(), fn)(self.ctx, *args), self.ctx)
+
+    def _cond(self, n, cr_latent, cr_face, id_emb):
+        """The conditioning inputs of n faces as pointers (and the tensors behind them): cr_latent [n,4,L,L] and exactly one of cr_face
+        [n,3,128,128] / id_emb [n,2048]."""
+        L = self.latent_res
         if tuple(cr_latent.shape) != (n, 4, L, L):
             raise RuntimeError("cr_latent must be (%d,4,%d,%d), got %s" % (n, L, L, tuple(cr_latent.shape)))
         if (cr_face is None) == (id_emb is None):
             raise RuntimeError("need exactly one of cr_face / id_emb")
         if cr_face is not None and tuple(cr_face.shape) != (n, 3, 128, 128):
             raise RuntimeError("cr_face must be (%d,3,128,128), got %s" % (n, tuple(cr_face.shape)))
-        crl = _f32c(cr_latent, self.device)
-        crf = _f32c(cr_face, self.device) if cr_face is not None else None
-        emb = _f32c(id_emb.reshape(n, -1), self.device) if id_emb is not None else None
-        if emb is not None and emb.shape[1] != 2048:
+        keep = [_f32c(cr_latent, self.device), None if cr_face is None else _f32c(cr_face, self.device),
+                None if id_emb is None else _f32c(id_emb.reshape(n, -1), self.device)]
+        if keep[2] is not None and keep[2].shape[1] != 2048:
             raise RuntimeError("identity embedding must have 2048 features")
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().hd_prepare_slots(self.ctx, n, ctypes.cast(sl.data_ptr(), ctypes.POINTER(ctypes.c_int32)), crl.data_ptr(),
-                                                   crf.data_ptr() if crf is not None else None, emb.data_ptr() if emb is not None else None,
-                                                   _stream(self.device)), self.ctx)
+        return [None if t is None else t.data_ptr() for t in keep], keep
+
+    # ---- C-ABI calls ----
+    def prepare(self, cr_latent, cr_face=None, id_emb=None):
+        self.require_loaded()
+        B = cr_latent.shape[0]
+        ptrs, keep = self._cond(B, cr_latent, cr_face, id_emb)
+        self._call("hd_prepare", B, *ptrs, _stream(self.device))
+        self.batch, self.cond_key, self.prior_key = B, None, None
+
+    def prepare_slots(self, slots, cr_latent, cr_face=None, id_emb=None):
+        """hd_prepare_slots: replace the conditioning of the prepared batch's faces in `slots` (n distinct ints in [0, B))."""
+        self.require_loaded()
+        n, sp, sl = self._faces(slots)
+        ptrs, keep = self._cond(n, cr_latent, cr_face, id_emb)
+        self._call("hd_prepare_slots", n, sp, *ptrs, _stream(self.device))
         self.cond_key, self.prior_key = None, None         # the batch no longer matches any one pair of tensors
 
     def enable_pool(self, capacity):
@@ -377,15 +342,13 @@ class _Engine:
             raise RuntimeError("the conditioning pool needs the conditional refiner")
         self.pool_cap = pool_capacity_arg(capacity)
         if self.ctx is not None:
-            with torch.cuda.device(self.device):
-                _lib.check(_lib.lib().hd_pool_config(self.ctx, self.pool_cap), self.ctx)
+            self._call("hd_pool_config", self.pool_cap)
 
     def disable_pool(self):
         """Free the pool."""
         self.pool_cap = None
         if self.ctx is not None:
-            with torch.cuda.device(self.device):
-                _lib.check(_lib.lib().hd_pool_config(self.ctx, 0), self.ctx)
+            self._call("hd_pool_config", 0)
 
     def pool_prepare(self, entries, cr_latent, cr_face=None, id_emb=None):
         """hd_pool_prepare: compute the conditioning of n faces and keep face j in pool entry entries[j] (n distinct ints in
@@ -394,34 +357,18 @@ class _Engine:
         if self.batch is None:
             raise RuntimeError("no batch is prepared: call prepare(cr_face, cr_latent) for the whole batch first")
         en = entries_arg(entries, self.pool_cap, min(self.batch, self.pool_cap or 0), True)
-        n, L = en.numel(), self.latent_res
-        if tuple(cr_latent.shape) != (n, 4, L, L):
-            raise RuntimeError("cr_latent must be (%d,4,%d,%d), got %s" % (n, L, L, tuple(cr_latent.shape)))
-        if (cr_face is None) == (id_emb is None):
-            raise RuntimeError("need exactly one of cr_face / id_emb")
-        if cr_face is not None and tuple(cr_face.shape) != (n, 3, 128, 128):
-            raise RuntimeError("cr_face must be (%d,3,128,128), got %s" % (n, tuple(cr_face.shape)))
-        crl = _f32c(cr_latent, self.device)
-        crf = _f32c(cr_face, self.device) if cr_face is not None else None
-        emb = _f32c(id_emb.reshape(n, -1), self.device) if id_emb is not None else None
-        if emb is not None and emb.shape[1] != 2048:
-            raise RuntimeError("identity embedding must have 2048 features")
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().hd_pool_prepare(self.ctx, n, ctypes.cast(en.data_ptr(), ctypes.POINTER(ctypes.c_int32)), crl.data_ptr(),
-                                                  crf.data_ptr() if crf is not None else None, emb.data_ptr() if emb is not None else None,
-                                                  _stream(self.device)), self.ctx)
+        ptrs, keep = self._cond(en.numel(), cr_latent, cr_face, id_emb)
+        self._call("hd_pool_prepare", en.numel(), _i32p(en), *ptrs, _stream(self.device))
 
     def pool_commit(self, slots, entries):
         """hd_pool_commit: the prepared batch's faces in `slots` (n distinct ints in [0, B)) take the conditioning kept in `entries`
         (n prepared pool entries; one entry may fill several slots)."""
         self.require_loaded()
-        sl = slots_arg(slots, self.batch)
+        n, sp, sl = self._faces(slots)
         en = entries_arg(entries, self.pool_cap, self.batch, False)
-        if en.numel() != sl.numel():
-            raise ValueError(f"{sl.numel()} slots but {en.numel()} entries")
-        i32p = lambda t: ctypes.cast(t.data_ptr(), ctypes.POINTER(ctypes.c_int32))   # noqa: E731
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().hd_pool_commit(self.ctx, sl.numel(), i32p(sl), i32p(en), _stream(self.device)), self.ctx)
+        if en.numel() != n:
+            raise ValueError(f"{n} slots but {en.numel()} entries")
+        self._call("hd_pool_commit", n, sp, _i32p(en), _stream(self.device))
         self.cond_key, self.prior_key = None, None         # the batch no longer matches any one pair of tensors
 
     def set_mask(self, mask, known, noise, slots=None):
@@ -431,24 +378,18 @@ class _Engine:
         if self.batch is None:                             # the argument errors come first
             mask_args(mask, known, noise, torch.as_tensor(mask).shape[0] if mask is not None else 0, self.latent_res)
             raise RuntimeError("no batch is prepared: prepare the batch before giving it a mask")
-        sl = None if slots is None else slots_arg(slots, self.batch)
-        n = self.batch if sl is None else sl.numel()
+        n, sp, sl = self._faces(slots)
         m, k, z = mask_args(mask, known, noise, n, self.latent_res)
         self.require_loaded()
         m, k, z = _f32c(m, self.device), _f32c(k, self.device), _f32c(z, self.device)
-        sp = None if sl is None else ctypes.cast(sl.data_ptr(), ctypes.POINTER(ctypes.c_int32))
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().hd_mask_faces(self.ctx, n, sp, m.data_ptr(), k.data_ptr(), z.data_ptr(), _stream(self.device)), self.ctx)
+        self._call("hd_mask_faces", n, sp, m.data_ptr(), k.data_ptr(), z.data_ptr(), _stream(self.device))
 
     def clear_mask(self, slots=None):
         """Take the masks of the faces in `slots` (None: of every face) away; a no-op without a prepared batch."""
         if self.batch is None or self.ctx is None:
             return
-        sl = None if slots is None else slots_arg(slots, self.batch)
-        n = self.batch if sl is None else sl.numel()
-        sp = None if sl is None else ctypes.cast(sl.data_ptr(), ctypes.POINTER(ctypes.c_int32))
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().hd_mask_faces(self.ctx, n, sp, None, None, None, _stream(self.device)), self.ctx)
+        n, sp, sl = self._faces(slots)
+        self._call("hd_mask_faces", n, sp, None, None, None, _stream(self.device))
 
     def set_guidance(self, target, weight, scale, rows=None, slots=None):
         """hd_guide_faces: the faces in `slots` (None: the whole prepared batch, in order) are guided from now on -- see
@@ -456,49 +397,40 @@ class _Engine:
         if self.batch is None:                             # the argument errors come first
             guidance_args(target, weight, scale, rows, torch.as_tensor(target).shape[0] if target is not None else 0, self.latent_res)
             raise RuntimeError("no batch is prepared: prepare the batch before guiding it")
-        sl = None if slots is None else slots_arg(slots, self.batch)
-        n = self.batch if sl is None else sl.numel()
+        n, sp, sl = self._faces(slots)
         g, w, N, r = guidance_args(target, weight, scale, rows, n, self.latent_res)
         self.require_loaded()
         g = _f32c(g, self.device)
-        i32p = lambda t: None if t is None else ctypes.cast(t.data_ptr(), ctypes.POINTER(ctypes.c_int32))   # noqa: E731
         r0, r1 = (None, None) if r is None else (r[:, 0].contiguous(), r[:, 1].contiguous())
-        with torch.cuda.device(self.device):
-            if not self.guide_on:
-                _lib.check(_lib.lib().hd_guide_config(self.ctx, 1), self.ctx)
-                self.guide_on = True
-            _lib.check(_lib.lib().hd_guide_faces(self.ctx, n, i32p(sl), g.data_ptr(), ctypes.cast(w.data_ptr(), ctypes.POINTER(ctypes.c_float)),
-                                                 i32p(N), i32p(r0), i32p(r1), _stream(self.device)), self.ctx)
+        if not self.guide_on:
+            self._call("hd_guide_config", 1)
+            self.guide_on = True
+        self._call("hd_guide_faces", n, sp, g.data_ptr(), ctypes.cast(w.data_ptr(), ctypes.POINTER(ctypes.c_float)), _i32p(N), _i32p(r0), _i32p(r1),
+                   _stream(self.device))
 
     def clear_guidance(self, slots=None):
         """Stop guiding the faces in `slots` (None: every face); a no-op without a prepared batch."""
         if self.batch is None or self.ctx is None:
             return
-        sl = None if slots is None else slots_arg(slots, self.batch)
-        n = self.batch if sl is None else sl.numel()
-        sp = None if sl is None else ctypes.cast(sl.data_ptr(), ctypes.POINTER(ctypes.c_int32))
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().hd_guide_faces(self.ctx, n, sp, None, None, None, None, None, _stream(self.device)), self.ctx)
+        n, sp, sl = self._faces(slots)
+        self._call("hd_guide_faces", n, sp, None, None, None, None, None, _stream(self.device))
 
     def disable_guidance(self):
         """hd_guide_config(on = 0): no face is guided and the step has no guided launch."""
         self.guide_on = False
         if self.ctx is not None:
-            with torch.cuda.device(self.device):
-                _lib.check(_lib.lib().hd_guide_config(self.ctx, 0), self.ctx)
+            self._call("hd_guide_config", 0)
 
     def enable_previews(self, every=1, snapshots=0):
         """hd_preview_config(on = 1): see FacialRefiner.enable_previews.  Before the model has a device only the setting is kept."""
         self.preview_cfg = preview_args(every, snapshots)
         if self.ctx is not None:
-            with torch.cuda.device(self.device):
-                _lib.check(_lib.lib().hd_preview_config(self.ctx, 1, *self.preview_cfg), self.ctx)
+            self._call("hd_preview_config", 1, *self.preview_cfg)
 
     def disable_previews(self):
         self.preview_cfg = None
         if self.ctx is not None:
-            with torch.cuda.device(self.device):
-                _lib.check(_lib.lib().hd_preview_config(self.ctx, 0, 1, 0), self.ctx)
+            self._call("hd_preview_config", 0, 1, 0)
 
     def previews(self, slots=None, snapshot=None):
         """hd_preview_read: (x0 [n,4,L,L], rows int32 [n]) of the faces in `slots` (None: the whole batch), the latest plane or `snapshot`."""
@@ -507,23 +439,20 @@ class _Engine:
         snap = -1 if snapshot is None else int(snapshot)
         if not -1 <= snap < self.preview_cfg[1] or (snapshot is not None and snap < 0):
             raise ValueError(f"snapshot must be None or lie in [0, {self.preview_cfg[1]}), got {snapshot!r}")
-        sl = None if slots is None else slots_arg(slots, self.batch)
+        n, sp, sl = self._faces(slots)
         self.require_loaded()
         if self.batch is None:
             raise RuntimeError("no batch is prepared: previews belong to a prepared batch")
-        n, L = self.batch if sl is None else sl.numel(), self.latent_res
+        L = self.latent_res
         x0 = torch.empty((n, 4, L, L), dtype=torch.float32, device=self.device)
         rows = torch.empty((n,), dtype=torch.int32, device=self.device)
-        sp = None if sl is None else ctypes.cast(sl.data_ptr(), ctypes.POINTER(ctypes.c_int32))
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().hd_preview_read(self.ctx, n, sp, snap, x0.data_ptr(), rows.data_ptr(), _stream(self.device)), self.ctx)
+        self._call("hd_preview_read", n, sp, snap, x0.data_ptr(), rows.data_ptr(), _stream(self.device))
         return x0, rows
 
     def prepare_unconditional(self, batch):
         self.require_loaded()
         if self.batch != batch:
-            with torch.cuda.device(self.device):
-                _lib.check(_lib.lib().hd_prepare_unconditional(self.ctx, batch, _stream(self.device)), self.ctx)
+            self._call("hd_prepare_unconditional", batch, _stream(self.device))
             self.batch, self.cond_key = batch, None
 
     def prepare_from_priors(self, priors, id_emb):
@@ -540,8 +469,7 @@ class _Engine:
             keep.append(_f32c(p, self.device))
         emb = _f32c(id_emb.reshape(B, -1), self.device)
         ptrs = (ctypes.c_void_p * 5)(*[t.data_ptr() for t in keep])
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().hd_prepare_from_priors(self.ctx, B, ptrs, emb.data_ptr(), _stream(self.device)), self.ctx)
+        self._call("hd_prepare_from_priors", B, ptrs, emb.data_ptr(), _stream(self.device))
         self.batch, self.cond_key = B, None
 
     def timesteps_tensor(self, timesteps, batch):
@@ -565,8 +493,7 @@ class _Engine:
         x = _f32c(latents, self.device)
         t = self.timesteps_tensor(timesteps, B)
         out = torch.empty_like(x)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().hd_eps(self.ctx, x.data_ptr(), t.data_ptr(), t.numel(), out.data_ptr(), _stream(self.device)), self.ctx)
+        self._call("hd_eps", x.data_ptr(), t.data_ptr(), t.numel(), out.data_ptr(), _stream(self.device))
         return out
 
     def check(self, synchronize=True):
@@ -580,8 +507,7 @@ class _Engine:
             return
         if synchronize:
             torch.cuda.current_stream(self.device).synchronize()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().hd_check(self.ctx), self.ctx)
+        self._call("hd_check")
 
     def __del__(self):
         try:
@@ -665,29 +591,9 @@ class FusedDenoiser(_SubModule):
         self._engine.prior_key = None
 
 
-class Denoiser(_Previews, _Guidance, nn.Module):
-    """The unconditional pre-training network (models/denoiser/model.py:32-134): `model(latents, t).sample`, as the
-    sampling loop of pretrain_denoiser.py:101-110 calls it.  State-dict keys are the reference's (no prefix)."""
-
-    def __init__(self, latent_size):
-        super().__init__()
-        if latent_size % 16 != 0 or latent_size < 16:
-            raise ValueError("latent_size must be a multiple of 16")
-        object.__setattr__(self, "_engine", _Engine(latent_size, conditional=False))
-        self.width = 32 * 4
-        self.dtype = torch.float32
-        self.config = _Config()
-        self.config.in_channels = 4
-        self.config.sample_size = latent_size
-
-    def load_state_dict(self, state_dict, strict=True):
-        missing, unexpected = self._engine.load({"denoiser." + k: v for k, v in state_dict.items()}, strict)
-        n = len("denoiser.")
-        return torch.nn.modules.module._IncompatibleKeys([k[n:] for k in missing], [k[n:] for k in unexpected])
-
-    def state_dict(self, *a, **k):
-        n = len("denoiser.")
-        return {key[n:]: v for key, v in (self._engine.state or {}).items()}
+class _EngineModule(nn.Module):
+    """What Denoiser and FacialRefiner share: the device plumbing and the per-face calls of the engine (`self._engine`, set by the
+    subclass's __init__)."""
 
     def to(self, *args, **kwargs):
         device = kwargs.get("device", args[0] if args else None)
@@ -717,6 +623,66 @@ class Denoiser(_Previews, _Guidance, nn.Module):
         """Remove the masks of the faces in `slots` (None: of every face)."""
         self._engine.clear_mask(slots)
 
+    def enable_previews(self, every=1, snapshots=0):
+        """Progress previews: from now on every sampling.sample call also stores each face's denoised estimate x0 of the row it last ran
+        (diffusers' pred_original_sample; a masked face: blended with its known latent), and the estimate of every `every`-th row of the
+        face's own schedule in one of `snapshots` (0..64) snapshot planes.  The final latents do not change by a bit and nothing is
+        recaptured.  A new prepare resets the previews, prepare_slots those of its slots; the setting stays until disable_previews().
+        ValueError for every < 1 or snapshots outside [0, 64]."""
+        self._engine.enable_previews(every, snapshots)
+
+    def disable_previews(self):
+        """Switch the previews off and free their buffers."""
+        self._engine.disable_previews()
+
+    def previews(self, slots=None, snapshot=None):
+        """(x0 [n,4,L,L] fp32, rows [n] int32) on the model's device, in stream order: the latest estimate (snapshot=None) or snapshot
+        plane `snapshot` of the prepared batch's faces in `slots` (None: all, in order), and the table row each was taken at -- -1 (and a
+        zero plane) for a face that has not written it since it was prepared or refilled."""
+        return self._engine.previews(slots, snapshot)
+
+    def set_guidance(self, target, weight, scale, rows=None, slots=None):
+        """Low-pass fidelity guidance: from now on every sampling.sample call pulls the denoised estimate of the prepared batch's faces in
+        `slots` (None: all, in order) towards `target` [n,4,L,L] in the low frequencies -- x0 <- x0 + w (LP_N(target) - LP_N(x0)) on the rows
+        `rows` = (j0, j1) of each face's own schedule (None: all rows) -- with weight w in (0, 1] (a float or [n]) and block size N = scale,
+        a divisor of L (an int or [n]); sampling.low_pass is LP_N.  Switches guidance on for the model when needed (one recapture of the
+        step graphs); the faces stay guided until clear_guidance, the next prepare of a batch, or prepare_slots of their slot.  ValueError
+        for wrong shapes, a weight outside (0, 1], a scale that does not divide L, or rows without 0 <= j0 < j1."""
+        self._engine.set_guidance(target, weight, scale, rows, slots)
+
+    def clear_guidance(self, slots=None):
+        """Stop guiding the faces in `slots` (None: every face); guidance stays switched on."""
+        self._engine.clear_guidance(slots)
+
+    def disable_guidance(self):
+        """Stop guiding every face and switch guidance off: the step loses its extra launch again (one recapture of the step graphs)."""
+        self._engine.disable_guidance()
+
+
+class Denoiser(_EngineModule):
+    """The unconditional pre-training network (models/denoiser/model.py:32-134): `model(latents, t).sample`, as the
+    sampling loop of pretrain_denoiser.py:101-110 calls it.  State-dict keys are the reference's (no prefix)."""
+
+    def __init__(self, latent_size):
+        super().__init__()
+        if latent_size % 16 != 0 or latent_size < 16:
+            raise ValueError("latent_size must be a multiple of 16")
+        object.__setattr__(self, "_engine", _Engine(latent_size, conditional=False))
+        self.width = 32 * 4
+        self.dtype = torch.float32
+        self.config = _Config()
+        self.config.in_channels = 4
+        self.config.sample_size = latent_size
+
+    def load_state_dict(self, state_dict, strict=True):
+        missing, unexpected = self._engine.load({"denoiser." + k: v for k, v in state_dict.items()}, strict)
+        n = len("denoiser.")
+        return torch.nn.modules.module._IncompatibleKeys([k[n:] for k in missing], [k[n:] for k in unexpected])
+
+    def state_dict(self, *a, **k):
+        n = len("denoiser.")
+        return {key[n:]: v for key, v in (self._engine.state or {}).items()}
+
     def forward(self, latents, timesteps):
         e = self._engine
         e.ensure(latents.device)
@@ -726,7 +692,7 @@ class Denoiser(_Previews, _Guidance, nn.Module):
         return UNet2DOutput(e.eps(latents, timesteps))
 
 
-class FacialRefiner(_Previews, _Guidance, nn.Module):
+class FacialRefiner(_EngineModule):
     def __init__(self, latent_res=16, idc_ckpt=None, denoiser_ckpt=None, cache_conditioning=True):
         super().__init__()
         if latent_res % 16 != 0 or latent_res < 16:
@@ -757,23 +723,6 @@ class FacialRefiner(_Previews, _Guidance, nn.Module):
 
     def state_dict(self, *a, **k):
         return dict(self._engine.state or {})
-
-    def to(self, *args, **kwargs):
-        device = kwargs.get("device", args[0] if args else None)
-        if isinstance(device, (str, torch.device, int)):
-            self._engine.ensure(torch.device("cuda", device) if isinstance(device, int) else device)
-        return self
-
-    def cuda(self, device=None):
-        return self.to(torch.device("cuda", device if device is not None else torch.cuda.current_device()))
-
-    @property
-    def engine(self):
-        return self._engine
-
-    def check(self, synchronize=True):
-        """Synchronise and raise RuntimeError if a call since the last check handed back NaN-poisoned results (_Engine.check)."""
-        self._engine.check(synchronize)
 
     def prepare(self, cr_face, cr_latent):
         """Once-per-batch conditioning (FPG, IDC, HCA gates, idc_conv)."""
@@ -830,17 +779,6 @@ class FacialRefiner(_Previews, _Guidance, nn.Module):
         their mask, guidance, previews and multistep history as after prepare_slots.  The entries stay valid.  Continue with
         sample(..., prepare=False)."""
         self._engine.pool_commit(slots, entries)
-
-    def set_mask(self, mask, known, noise, slots=None):
-        """Inpainting: give the prepared batch's faces in `slots` (None: all, in order) a mask [n,L,L] or [n,1,L,L] in [0, 1] (1: resample,
-        0: keep), the known latents [n,4,L,L] and their fixed noise [n,4,L,L] (sampling.inpaint_start returns it).  Every following
-        sampling.sample call blends the kept region back after each step; the masks stay until clear_mask, the next prepare of a batch,
-        or prepare_slots of their slot.  ValueError for wrong shapes or a mask outside [0, 1]."""
-        self._engine.set_mask(mask, known, noise, slots)
-
-    def clear_mask(self, slots=None):
-        """Remove the masks of the faces in `slots` (None: of every face)."""
-        self._engine.clear_mask(slots)
 
     def invalidate_conditioning(self):
         """Forget the cached conditioning (after writing into cr_face / cr_latent through `.data`, numpy or a DLPack alias,
