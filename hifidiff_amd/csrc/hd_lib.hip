@@ -634,7 +634,11 @@ int hd_create_unconditional(hd_ctx** out, int latent_res, int device) {
 int hd_create(hd_ctx** out, int latent_res, int device) {
     if (!out) return HD_ERR_INVALID;
     *out = nullptr;
-    if (latent_res < 16 || latent_res % 16 != 0 || latent_res > 64) { g_create_error = "latent_res must be 16, 32, 48 or 64"; return HD_ERR_INVALID; }
+    // 48 (sides 48, 24, 12, 6, 3) is refused: EpPixShufF32::out_row and sched_from_x0's mask index split a row with shifts and masks
+    if (latent_res != 16 && latent_res != 32 && latent_res != 64) {
+        g_create_error = "latent_res must be 16, 32 or 64 (level sides must be powers of two), got " + std::to_string(latent_res);
+        return HD_ERR_INVALID;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_create_error = "no HIP device available"; return HD_ERR_HIP; }
     if (device < 0 || device >= ndev) { g_create_error = "device index out of range"; return HD_ERR_INVALID; }

@@ -185,11 +185,22 @@ def preview_args(every, snapshots):
     return every, snapshots
 
 
+LATENT_SIDES = (16, 32, 64)
+
+
+def check_latent_res(latent_res, name="latent_res"):
+    """The sizes hd_create takes, refused at construction with its wording: the PixelShuffle epilogue and the per-face mask index split a
+    row index with shifts and masks, so every level side (latent_res >> l, l = 0..4) must be a power of two (latent sizes)."""
+    if latent_res not in LATENT_SIDES:
+        raise ValueError(f"{name} must be 16, 32 or 64 (level sides must be powers of two), got {latent_res!r}")
+    return int(latent_res)
+
+
 class _Engine:
     """Owns the hd_ctx of one (latent_res, device)."""
 
     def __init__(self, latent_res, conditional=True):
-        self.latent_res = int(latent_res)
+        self.latent_res = check_latent_res(latent_res)
         self.conditional = conditional     # False: the unconditional Denoiser (models/denoiser/model.py:32)
         self.ctx = None
         self.device = None
@@ -665,8 +676,7 @@ class Denoiser(_EngineModule):
 
     def __init__(self, latent_size):
         super().__init__()
-        if latent_size % 16 != 0 or latent_size < 16:
-            raise ValueError("latent_size must be a multiple of 16")
+        check_latent_res(latent_size, "latent_size")
         object.__setattr__(self, "_engine", _Engine(latent_size, conditional=False))
         self.width = 32 * 4
         self.dtype = torch.float32
@@ -695,8 +705,7 @@ class Denoiser(_EngineModule):
 class FacialRefiner(_EngineModule):
     def __init__(self, latent_res=16, idc_ckpt=None, denoiser_ckpt=None, cache_conditioning=True):
         super().__init__()
-        if latent_res % 16 != 0 or latent_res < 16:
-            raise ValueError("latent_res must be a multiple of 16")
+        check_latent_res(latent_res)
         object.__setattr__(self, "_engine", _Engine(latent_res))
         self.latent_res = latent_res
         self.cache_conditioning = cache_conditioning

@@ -65,7 +65,9 @@ typedef struct hd_schedule_ms {
 } hd_schedule_ms;
 
 /* FacialRefiner(latent_res) (models/refiner.py:11-16): builds the network description for latent
- * side `latent_res` (16 for 16->128 px, 32 for 32->256 px) on HIP device `device`. */
+ * side `latent_res` (16 for 16->128 px, 32 for 32->256 px, 64 for 64->512 px) on HIP device `device`.
+ * Any other value returns HD_ERR_INVALID before the first HIP call (hd_last_error(NULL) names the accepted
+ * sizes): every level side latent_res >> l, l = 0..4, must be a power of two. */
 int hd_create(hd_ctx** out, int latent_res, int device);
 /* The unconditional pre-training network `Denoiser(latent_size)` (models/denoiser/model.py:32-134; sampled by
  * pretrain_denoiser.py:76-120): the same UNet without priors, HCAs and identity term.  Its state-dict keys are

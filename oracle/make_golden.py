@@ -103,6 +103,28 @@ def gen_l32_loop(args):
 
 
 @torch.no_grad()
+def gen_l64(args):
+    """FacialRefiner(64) (64->512 px: idc_conv 2048->32768, mid at 4x4), one face: eps at t = 500 (section 9 at latent 64) and the
+    first 5 steps of the 50-step DDIM schedule (eta 0, clip 3.0), the reference network inside the restated scheduler."""
+    FacialRefiner = import_reference(args.ref)[0]
+    net = FacialRefiner(64).eval()
+    net.load_state_dict(synth.refiner_state_dict(64), strict=True)
+    x, crl, crf = synth.sample_inputs(1, 64)
+    e = net(x, torch.full((1,), 500), crf, crl).sample
+    assert tuple(e.shape) == (1, 4, 64, 64) and e.dtype == torch.float32
+    np.savez_compressed(os.path.join(args.out, "refiner_eps_L64.npz"), eps_t500=e.numpy())
+    print("wrote refiner_eps_L64.npz", e.shape, float(e.abs().max()))
+    sch = O.DDIMScheduler(clip_sample=True, clip_sample_range=3.0)
+    sch.set_timesteps(50)
+    lat = x.clone()
+    for t in sch.timesteps[:5]:
+        eps = net(lat, torch.full((1,), int(t)), crf, crl).sample
+        lat = sch.step(eps, int(t), lat).prev_sample
+    np.savez_compressed(os.path.join(args.out, "ddim50_first5_L64.npz"), final=lat.numpy())
+    print("wrote ddim50_first5_L64.npz", lat.shape, float(lat.abs().max()))
+
+
+@torch.no_grad()
 def gen_cr(args):
     """CoarseRestoration (models/cr/model.py:33-88) on two synthetic 128x128 faces: output, the nine STN thetas and
     the stage outputs.  The synthetic fc_loc.2 weights are scaled down so that theta stays near the identity the
@@ -234,6 +256,8 @@ def main():
         return gen_cr(args)
     if args.only == "l32loop":
         return gen_l32_loop(args)
+    if args.only == "l64":
+        return gen_l64(args)
     if args.only == "crwild":
         return gen_cr_wild(args)
     if args.only == "ddpmslices":

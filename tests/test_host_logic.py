@@ -37,6 +37,51 @@ def test_no_gpu_means_loud_failure():
     assert rc < 0 and b"HIP" in _lib.lib().hd_last_error(None) or b"device" in _lib.lib().hd_last_error(None)
 
 
+HD_ERR_INVALID = -1                                                    # include/hifidiff_hip.h
+
+
+def test_header_error_codes():
+    header = open(os.path.join(ROOT, "include", "hifidiff_hip.h")).read()
+    assert re.search(r"\bHD_ERR_INVALID\s*=\s*(-?\d+)", header).group(1) == str(HD_ERR_INVALID)
+
+
+@pytest.mark.parametrize("create", ["hd_create", "hd_create_unconditional"])
+@pytest.mark.parametrize("r", [0, 8, 24, 48, 80, 128])
+def test_create_refuses_sizes_the_kernels_cannot_index(create, r):
+    """The PixelShuffle epilogue and the per-face mask index split a row with shifts and masks: a level side that is no power of two
+    (48: sides 48, 24, 12, 6, 3) would store past the level buffer.  Refused before the first HIP call, so this runs without a device."""
+    L = _lib.lib()
+    ctx = ctypes.c_void_p(0xdead)
+    assert getattr(L, create)(ctypes.byref(ctx), r, 0) == HD_ERR_INVALID
+    assert ctx.value is None
+    msg = L.hd_last_error(None).decode()
+    assert all(re.search(r"\b%d\b" % s, msg) for s in (16, 32, 64)) and "48" not in msg.split(", got")[0], msg
+    assert "powers of two" in msg, msg
+
+
+@pytest.mark.parametrize("r", [16, 32, 64])
+def test_create_accepts_the_power_of_two_sizes(r):
+    """16, 32 and 64 pass the size check: without a device the failure is the device's, never HD_ERR_INVALID for the size."""
+    L = _lib.lib()
+    ctx = ctypes.c_void_p()
+    rc = L.hd_create(ctypes.byref(ctx), r, 0)
+    if rc == 0:
+        L.hd_destroy(ctx)
+    else:
+        assert not torch.cuda.is_available() and rc != HD_ERR_INVALID and ctx.value is None, (rc, L.hd_last_error(None))
+        assert b"latent_res" not in L.hd_last_error(None)
+
+
+@pytest.mark.parametrize("r", [48, 80, 96, 0, 24])
+def test_python_constructors_refuse_the_same_sizes(r):
+    from hifidiff_amd.refiner import Denoiser, FacialRefiner, _Engine
+    for make in (FacialRefiner, Denoiser, _Engine, lambda v: _Engine(v, conditional=False)):
+        with pytest.raises(ValueError, match=r"16, 32 or 64 \(level sides must be powers of two\)"):
+            make(r)
+    for ok in (16, 32, 64):
+        assert FacialRefiner(ok).engine.latent_res == ok and Denoiser(ok).engine.latent_res == ok
+
+
 def test_manifest_counts():
     man = arch.refiner_manifest(16)
     assert len(man) == 1460                                            # SURVEY §3.4

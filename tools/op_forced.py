@@ -19,11 +19,15 @@ import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
-from forced import BF16_BOUND, FP32_BOUND, Check, LaunchIO, NafRules, PrefixRun, down_rule, nchw, rows, up_rule     # noqa: E402
+from forced import BF16_BOUND, FP32_BOUND, Check, LaunchIO, NafRules, PrefixRun, down_rule, naf_gemm_rows, nchw, rows, up_rule     # noqa: E402
 from hifidiff_amd import _lib                                  # noqa: E402
 from oracle import hifidiff_oracle as O                         # noqa: E402
 
 PR = O.BF16
+# launches of one eps evaluation in the program with one launch per GEMM: intro, 4 downs, 4 ups, 5 HCA convs, ending, 8 x 5 at the middle
+# level, 16 x 5 at levels 2 / 3 and 8 blocks at levels 0 / 1 -- 2 launches each (fused conv1 or strips + the chain kernel), 4 at latent 64
+# (conv1, the unfused depthwise conv, pool_finish, the chain kernel)
+DENOISER_OPS = {16: 151, 32: 151, 64: 167}
 GATED_LAST = {"denoiser.middle_blks.7": 0, "denoiser.decoders.0.1": 1, "denoiser.decoders.1.1": 2, "denoiser.decoders.2.1": 3, "denoiser.decoders.3.1": 4}
 
 
@@ -94,9 +98,10 @@ class _Step:
         self.ck.rel(i, name, "Xg", "Xg", self.run.buf(f"Xg{l}", B * H * H * C), rows(PR.q((x + add) * (1.0 + wc + ws))), True)
 
 
-def forced_scan(model, P, x, crl, crf, t, report, fp32_bound=FP32_BOUND, bf16_bound=BF16_BOUND):
-    """model: FacialRefiner built under HD_NO_XCD=1 (151 launches at latent 16).  Returns the worst rel-L2 over fp32 outputs and
-    over bf16-stored outputs; report lines carry `<<<<<<` where a bound is exceeded."""
+def forced_scan(model, P, x, crl, crf, t, report, fp32_bound=FP32_BOUND, bf16_bound=BF16_BOUND, info=None):
+    """model: FacialRefiner built under HD_NO_XCD=1 (151 launches at latent 16; latent 32 / 64 have no other program).  Returns the worst
+    rel-L2 over fp32 outputs and over bf16-stored outputs; report lines carry `<<<<<<` where a bound is exceeded.  info (a dict) receives
+    "kinds" {launch kind: worst rel-L2} and "launches" (of the program)."""
     st = _Step(model, P, x, crl, crf, t, report, fp32_bound, bf16_bound)
     ck, run, names, B, latent = st.ck, st.run, st.names, st.B, st.latent
     naf = NafRules(P, ck)
@@ -135,7 +140,22 @@ def forced_scan(model, P, x, crl, crf, t, report, fp32_bound=FP32_BOUND, bf16_bo
                 ck.no_rule(i, name)
     finally:
         st.reset()
+    if info is not None:
+        info["kinds"], info["launches"] = ck.worst, len(names)
     return ck.stored
+
+
+def denoiser_gemm_rows(name, B, latent):
+    """Rows M of the GEMM launch `name` of the denoiser program at batch B (None: the intro / ending convs, which are no GEMMs)."""
+    lv = lambda l: B * (latent >> l) ** 2                       # noqa: E731
+    p = name.split(".")
+    if p[0] == "denoiser":
+        return naf_gemm_rows(p[-1], B, level_of(name, latent)[2])
+    if p[0] == "downs":
+        return lv(int(p[1]) + 1)
+    if p[0] in ("ups", "hcas"):                                  # the up conv's rows are those of its input, the level above
+        return lv(4 - int(p[1]))
+    return None
 
 
 def stage_forced_scan(model, P, x, crl, crf, t, report, fp32_bound=FP32_BOUND, bf16_bound=BF16_BOUND):

@@ -26,17 +26,22 @@ from hifidiff_amd import _lib                                  # noqa: E402
 from oracle import hifidiff_oracle as O                         # noqa: E402
 
 PR = O.BF16
-PROLOGUE_OPS = {16: 160, 32: 160}                               # FPG 1 + 4 x 2 + 12 x 5 + 4 + 5, ResNet-50 56, gates 5 x 5, idc_conv (both latents)
+# FPG 1 + 4 x 2 + 12 x 5 + 4 + 5, ResNet-50 56, gates 5 x 5, idc_conv.  Latent 64: the four blocks of levels 0 / 1 (64 x 64 and 32 x 32 faces)
+# take the unfused depthwise path, conv1 / conv2_gate_pool / pool_finish / the chain kernel: 4 x 4 launches instead of 4 x 2
+PROLOGUE_OPS = {16: 160, 32: 160, 64: 168}
 LOADERS = ("F32", "LN", "BF16", "BF16S", "CONV_F32", "CONV_F32G", "CONV_BF16")
 EPILOGUES = ("BIASF32", "RESID", "GATE", "PIXSHUF", "BIASBF16", "DWGATE", "SCA")
 TILE_ROWS = {0: 128, 1: 64, 2: 64, 3: 32, 4: 32, 5: 128, 6: 256}
-F64_KINDS = ("fpg.intro", "gate.pool", "gate.spatial_mlp.3", "idc.avgpool")
+F64_KINDS = ("fpg.intro", "gate.pool", "gate.spatial_mlp.3", "idc.avgpool", "pool_finish")
 EXACT_KINDS = ("bf16_copy", "idc.input", "idc.max_pool")
-BF16_KINDS = ("conv2_gate_pool.fused", "conv2_gate_pool.strips", "sca.scale_G", "conv4", "idc.conv7x7", "idc.1x1", "idc.3x3", "idc.3x3s2",
+BF16_KINDS = ("conv2_gate_pool.fused", "conv2_gate_pool.strips", "conv2_gate_pool.unfused", "sca.scale_G", "conv4", "idc.conv7x7", "idc.1x1", "idc.3x3", "idc.3x3s2",
               "idc.downsample", "idc.downsample.s2", "idc.conv3")
 KINDS_GATES = {"gate.pool", "gate.channel_mlp.0", "gate.channel_mlp.2", "gate.spatial_mlp.0", "gate.spatial_mlp.3", "idc_conv"}
 KINDS_FPG16 = {"fpg.intro", "conv2_gate_pool.fused", "conv5.chain", "sca.prescale", "sca.scale_G", "conv3", "conv4", "conv5", "down", "up", "stats", "bf16_copy"}
 KINDS_FPG32 = KINDS_FPG16 | {"conv2_gate_pool.strips", "sca.bf16"}            # 32 x 32 / 16 x 16 faces by strips, level 2 with the row scale in conv3's loader
+# latent 64: levels 0 / 1 unfused (64 x 64 / 32 x 32 faces), levels 2 / 3 (256 / 64 pixels per face) with the row scale in conv3's loader: no level of the FPG
+# has few enough pixels for the SCA launch to rescale G
+KINDS_FPG64 = (KINDS_FPG16 - {"sca.prescale", "sca.scale_G"}) | {"conv1", "conv2_gate_pool.unfused", "pool_finish", "sca.bf16"}
 KINDS_IDC = {"idc.input", "idc.max_pool", "idc.avgpool"} | {k for k in BF16_KINDS if k.startswith("idc.")}
 KINDS_FULL16 = KINDS_FPG16 | KINDS_IDC | KINDS_GATES
 
