@@ -16,6 +16,8 @@
                                                           # the 128 x 128 face), keep the coarse restoration everywhere else
     python examples/pipeline.py --fidelity 0.5 [--fidelity-scale 4] [--fidelity-rows 0,30]   # low-pass guidance towards the coarse restoration:
                                                           # its structure and colour stay, the diffusion adds the detail
+    python examples/pipeline.py --color-fix wavelet [--color-weight 0.8]    # after the decode: the image keeps its detail and takes the
+                                                          # coarse restoration's colour (hd_color_fix; also with --stream)
 """
 import argparse
 import os
@@ -24,12 +26,28 @@ import time
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from hifidiff_amd import sampling, schedulers, synth                      # noqa: E402
+from hifidiff_amd import color, sampling, schedulers, synth               # noqa: E402
 from hifidiff_amd.cr import CoarseRestoration                            # noqa: E402
 from hifidiff_amd.refiner import FacialRefiner                           # noqa: E402
 from hifidiff_amd.vae import AutoencoderKL                               # noqa: E402
+
+
+def decode(a, vae, latents, cr_face):
+    """images = vae.decode(latents / 0.18215).sample; with --color-fix the colour-corrected images (hd_color_fix on the decode's stream,
+    the reference resampled inside the call when the sizes differ) and a line with the colour distance to cr_face before and after."""
+    if a.color_fix is None:
+        return vae.decode(latents / 0.18215).sample                    # the reference's call form; decode_scaled(latents) is the fused one
+    images = vae.decode_scaled(latents)
+    # one call does both: vae.decode_scaled(latents, color_ref=cr_face, color_mode=..., color_weight=...); here the plain images are wanted too
+    fixed = color.color_fix(images, cr_face, mode=a.color_fix, weight=a.color_weight)
+    ref = cr_face if cr_face.shape[-1] == images.shape[-1] else F.interpolate(cr_face, images.shape[-1], mode="bicubic", align_corners=False)
+    dist = lambda x: float((x.mean(dim=(-2, -1)) - ref.mean(dim=(-2, -1))).abs().mean())   # noqa: E731
+    print(f"colour fix {a.color_fix}, weight {1.0 if a.color_weight is None else a.color_weight}: mean |channel mean - cr_face's| "
+          f"{dist(images):.4f} before, {dist(fixed):.4f} after")
+    return fixed
 
 
 def main():
@@ -61,7 +79,13 @@ def main():
     ap.add_argument("--fidelity-scale", type=int, default=4, metavar="N",
                     help="--fidelity: block size N of the low-pass filter, a divisor of 16 (1: every element, 16: only each channel's mean)")
     ap.add_argument("--fidelity-rows", default=None, metavar="A,B", help="--fidelity: guide rows A <= j < B of each face's own schedule (default: all)")
+    ap.add_argument("--color-fix", choices=tuple(color.MODES), default=None,
+                    help="colour-correct the decoded images against cr_face: wavelet (five a-trous levels: the image's detail on the "
+                         "reference's low frequencies) or adain (the reference's per-channel mean and deviation); composes with everything")
+    ap.add_argument("--color-weight", type=float, default=None, metavar="W", help="--color-fix: weight of the correction in [0, 1] (default 1)")
     a = ap.parse_args()
+    if a.color_weight is not None and (a.color_fix is None or not 0.0 <= a.color_weight <= 1.0):
+        ap.error("--color-weight needs --color-fix and a value in [0, 1]")
     if a.preview_every is not None and a.preview_every < 1:
         ap.error("--preview-every must be >= 1")
     if a.fidelity is None and (a.fidelity_rows is not None or a.fidelity_scale != 4):
@@ -128,7 +152,7 @@ def main():
         lp = lambda t: sampling.low_pass(t, a.fidelity_scale)         # noqa: E731
         print(f"fidelity {a.fidelity} at N = {a.fidelity_scale}: mean |LP(latent) - LP(cr_latent)| {float((lp(out) - lp(cr_latent)).abs().mean()):.4f}")
     torch.cuda.synchronize(); t3 = time.time()
-    images = vae.decode(out / 0.18215).sample                          # the reference's call form; decode_scaled(out) is the fused one
+    images = decode(a, vae, out, cr_face)
     torch.cuda.synchronize(); t4 = time.time()
     for s in range(0 if snaps is None else snaps.shape[0]):            # the estimate of every N-th row as an image (hd_vae_decode)
         ran = snap_rows[s] >= 0                                        # img2img: a face that started later has not run this row
@@ -185,7 +209,7 @@ def stream(a, cr, vae, model, sch, steps, dev):
                       f"x0 std {float(spread):.3f}")
     torch.cuda.synchronize(); t2 = time.time()
     lat = torch.stack([out[i] for i in ids])
-    images = vae.decode(lat / 0.18215).sample
+    images = decode(a, vae, lat, torch.stack([f for f, _ in reqs]))
     torch.cuda.synchronize(); t3 = time.time()
     print(f"stream of {N} requests (strength 0.2..1.0), {a.batch} slots, refill every {a.refill_every}: coarse restoration + VAE encode "
           f"{1e3 * (t1 - t0):.1f} ms, {steps}-step {a.scheduler} {1e3 * (t2 - t1):.1f} ms ({N / (t2 - t1):.1f} faces/s, {cs.calls} calls, "

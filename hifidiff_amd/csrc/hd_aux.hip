@@ -2,6 +2,9 @@
 // diffusers AutoencoderKL, test_refiner.py:78-83,93) on the refiner path's kernels: weight ingest, workspaces, launch programs
 // and their C-ABI entry points.  Internals: hd_internal.hpp.
 #include "hd_internal.hpp"
+#include "hd_color.hpp"
+
+void set_contextless_error(const std::string& msg);               // hd_lib.hip: the message hd_last_error(NULL) returns
 
 // =============================================================================== CoarseRestoration (§8 f1)
 // models/cr/model.py:73-88: intro -> 4 x [NAF blocks, STN, down] (stage outputs are the skips) -> [8 NAF, STN]
@@ -533,5 +536,50 @@ int hd_vae_decode(hd_ctx* c, int batch, int latent_res, const float* latents, fl
     }
     return run_ops(c, c->ws->vae_dec_prog, reinterpret_cast<hipStream_t>(stream), c->op_limit);
 }
+
+// Colour correction of decoded faces against a reference (hd_color.hpp).  No context: errors go to hd_last_error(NULL), and every
+// argument is checked before the first HIP call.
+#define CF_FAIL(code, ...)                                        \
+    do {                                                          \
+        char _b[256];                                             \
+        snprintf(_b, sizeof(_b), __VA_ARGS__);                    \
+        set_contextless_error(_b);                                \
+        return (code);                                            \
+    } while (0)
+int hd_color_fix(const float* images, float* out, int batch, int res, const float* ref, int ref_res, int ref_vae_range, int mode,
+                 int levels, const float* weight, void* stream) {
+    if (batch < 1) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: batch must be >= 1, got %d", batch);
+    if (res < 64 || res > 512 || res % 64) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: res must be a multiple of 64 in [64, 512], got %d", res);
+    if (ref_res < 64 || ref_res > 512 || ref_res % 64) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: ref_res must be a multiple of 64 in [64, 512], got %d", ref_res);
+    if (mode != 1 && mode != 2) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: mode must be 1 (wavelet) or 2 (AdaIN), got %d", mode);
+    if (mode == 1 && (levels < 1 || levels > CF_MAX_LEVELS)) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: levels must be in [1, %d] in wavelet mode, got %d", CF_MAX_LEVELS, levels);
+    if (ref_vae_range != 0 && ref_vae_range != 1) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: ref_vae_range must be 0 or 1, got %d", ref_vae_range);
+    if (!images) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: images is NULL");
+    if (!out) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: out is NULL");
+    if (!ref) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: ref is NULL");
+    const uintptr_t pi = (uintptr_t)images, po = (uintptr_t)out, pr = (uintptr_t)ref;
+    if ((pi | po | pr | (uintptr_t)weight) % sizeof(float)) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: images, out, ref and weight must be aligned to 4 bytes");
+    if (mode == 2 && (pi | po | pr) % 16) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: images, out and ref must be aligned to 16 bytes in AdaIN mode");
+    const size_t nimg = (size_t)batch * 3 * res * res * sizeof(float), nref = (size_t)batch * 3 * ref_res * ref_res * sizeof(float);
+    if (po < pi + nimg && pi < po + nimg) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: out overlaps images (the tiled kernel reads its neighbours' pixels)");
+    if (po < pr + nref && pr < po + nimg) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: out overlaps ref");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int planes = batch * 3;
+    hipError_t e;
+    if (mode == 1) {
+        const int tiles = res / CF_TILE, halo = (1 << levels) - 1;
+        const int side = CF_TILE + (tiles == 1 ? 0 : tiles == 2 ? halo : 2 * halo);   // the largest staged region of any tile
+        const size_t smem = (size_t)2 * side * side * sizeof(float);
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wavelet_fix_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CF_MAX_SMEM);
+        if (e != hipSuccess) CF_FAIL(HD_ERR_HIP, "hd_color_fix: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+        hipLaunchKernelGGL(wavelet_fix_kernel, dim3(tiles * tiles, planes), dim3(CF_THREADS), smem, s, images, ref, out, weight, res, ref_res, ref_vae_range, levels);
+    } else {
+        hipLaunchKernelGGL(adain_fix_kernel, dim3(planes), dim3(CF_THREADS), 0, s, images, ref, out, weight, res, ref_res, ref_vae_range);
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) CF_FAIL(HD_ERR_HIP, "hd_color_fix: launch failed: %s", hipGetErrorString(e));
+    return HD_OK;
+}
+#undef CF_FAIL
 
 }  // extern "C"

@@ -4,6 +4,8 @@
 #include "hd_internal.hpp"
 
 static std::string g_create_error;
+// what hd_last_error(NULL) returns, for the entry points of hd_aux.hip that take no context (hd_color_fix)
+void set_contextless_error(const std::string& msg) { g_create_error = msg; }
 
 namespace {
 

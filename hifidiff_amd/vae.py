@@ -206,8 +206,13 @@ class AutoencoderKL(nn.Module):
         out = self.decode_scaled(z * self.config.scaling_factor)
         return DecoderOutput(out) if return_dict else (out,)
 
-    def decode_scaled(self, latents):
-        """images = vae.decode(latents / 0.18215).sample with the division inside the library."""
+    def decode_scaled(self, latents, color_ref=None, color_mode="wavelet", color_levels=5, color_weight=None, ref_vae_range=False):
+        """images = vae.decode(latents / 0.18215).sample with the division inside the library.  With `color_ref` [B,3,Rr,Rr] the decoded
+        images are colour-corrected against it on the same stream (color.color_fix: hd_color_fix after hd_vae_decode)."""
+        if color_ref is not None:
+            from . import color
+            return color.color_fix(self.decode_scaled(latents), color_ref, mode=color_mode, levels=color_levels, weight=color_weight,
+                                   ref_vae_range=ref_vae_range)
         self._ready(latents)
         B = latents.shape[0]
         if latents.dim() != 4 or latents.shape[1] != 4 or latents.shape[2] != latents.shape[3] or latents.shape[2] % 8:

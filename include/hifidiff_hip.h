@@ -271,6 +271,34 @@ int hd_guide_config(hd_ctx* ctx, int on);
 int hd_guide_faces(hd_ctx* ctx, int n, const int32_t* slots, const float* target, const float* weight, const int32_t* scale,
                    const int32_t* row_from, const int32_t* row_to, void* stream);
 
+/* Colour correction of decoded faces against a reference image: the step diffusion-based restoration stacks apply after vae.decode
+ * (StableSR's wavelet_color_fix / adain_color_fix, shipped unchanged by DiffBIR, SUPIR and SeeSR).  Low-pass guidance acts on the four
+ * latent channels during sampling; this call bounds the colour of the decoded RGB image.  The reference project has no such step.
+ * images, out [B,3,res,res], ref [B,3,ref_res,ref_res] (device fp32 NCHW); weight: device [B] in [0, 1], or NULL (all 1).  Per face f and
+ * channel plane, with c the image plane, s the reference plane and w the face's weight:
+ *     s <- clamp(s, 0, 1) * 2 - 1                              with ref_vae_range = 1 (to_vae_range, as hd_vae_encode's vae_range)
+ *   mode 1, wavelet with levels = n in 1..5:
+ *     s' = F.interpolate(s, res, mode = "bicubic", align_corners = False)    when ref_res != res (the rule hd_vae_encode uses), else s
+ *     blur_i(x) = F.conv2d(F.pad(x, (r,r,r,r), mode = "replicate"), k, dilation = r),  r = 2^i,  k = [1/4 1/2 1/4]^T [1/4 1/2 1/4]
+ *     B_n = blur_{n-1} o ... o blur_0
+ *     out = c + w * B_n(s' - c)
+ *   StableSR computes high(c) + low(s) with high(c) = sum_i (c_i - blur_i(c_i)), which telescopes to c - B_n(c); every blur_i is linear,
+ *   replicate padding included, so its result is c + B_n(s - c).  Each level runs as a horizontal 3-tap pass then a vertical one, taps
+ *   clamped to the image; one launch stages a 64 x 64 tile with its 2^n - 1 halo in LDS and does all 2n passes there.  A pixel's bits do
+ *   not depend on the tiling.
+ *   mode 2, AdaIN (levels is ignored):
+ *     a   = (c - mean(c)) * std(s) / std(c) + mean(s),   std(x) = sqrt(var_unbiased(x) + 1e-5)
+ *     out = c + w * (a - c)
+ *   with the statistics of s taken at its own resolution (no resampling) and all sums accumulated in fp64.
+ * A face with w == 0 gets c bit for bit in either mode.  The call needs no context, allocates nothing, keeps nothing in global memory and
+ * does not synchronise: it enqueues one launch on `stream`, and images and ref are only read.  out must not overlap images or ref (a tile
+ * reads its neighbours' c).  Errors are reported through hd_last_error(NULL).  HD_ERR_INVALID, naming the argument and before any HIP
+ * call, for batch < 1, res or ref_res not a multiple of 64 in [64, 512] (the VAE boundary's range), a mode other than 1 or 2, levels
+ * outside [1, 5] in wavelet mode, ref_vae_range outside {0, 1}, a NULL images, out or ref, a pointer that is not aligned to 4 bytes (16
+ * bytes for images, out and ref in AdaIN mode), or out overlapping images or ref as byte ranges. */
+int hd_color_fix(const float* images, float* out, int batch, int res, const float* ref, int ref_res, int ref_vae_range,
+                 int mode, int levels, const float* weight, void* stream);
+
 /* Progress previews: the denoised estimate of the row a face last ran, as an output of the sampling loop (diffusers'
  * `pred_original_sample` / `callback_on_step_end`).
  * hd_preview_config(on = 1, every, snapshots): from the next hd_prepare* on -- at once, when a batch is prepared -- the context owns the
