@@ -42,7 +42,7 @@ EXPORTS = [
     "hd_pool_config", "hd_pool_prepare", "hd_pool_commit",
     "hd_sample_faces", "hd_sample_faces_multistep", "hd_sample_spans", "hd_mask_faces", "hd_guide_config", "hd_guide_faces", "hd_color_fix", "hd_preview_config", "hd_preview_read", "hd_scheduler_step",
     "hd_scheduler_step_multistep", "hd_num_ops", "hd_num_chains",
-    "hd_debug_limit_ops", "hd_debug_op_name", "hd_debug_op_info", "hd_debug_read_op", "hd_debug_read", "hd_debug_write", "hd_set_option", "hd_get_option", "hd_check",
+    "hd_debug_limit_ops", "hd_debug_op_name", "hd_debug_op_info", "hd_debug_read_op", "hd_debug_read", "hd_debug_write", "hd_debug_gemm", "hd_set_option", "hd_get_option", "hd_check",
     "hd_set_profiling", "hd_get_profile",
 ]
 
@@ -60,6 +60,21 @@ class Schedule(ctypes.Structure):
 class ScheduleMS(ctypes.Structure):
     _fields_ = [("n_steps", ctypes.c_int32), ("timesteps", ctypes.POINTER(ctypes.c_float)),
                 ("coef", ctypes.POINTER(ctypes.c_float))]
+
+
+class GemmDesc(ctypes.Structure):
+    """hd_gemm_desc: one GEMM launch on the caller's device buffers (hd_debug_gemm)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("M", "hw", "face0", "act", "shuffle_r", "Win", "stats_np", "stats_cnt")] + [("a_scale", ctypes.c_float)] + \
+               [(n, ctypes.c_int32) for n in ("film_face_stride", "film_gain_off", "film_bias_off", "lda", "ldo", "ldr", "reserved")] + \
+               [(n, ctypes.c_void_p) for n in ("A", "stats_in", "film", "rowscale", "resid", "rscale", "gate_c", "gate_s", "add_src", "out", "out16", "outg16", "stats_out")]
+
+
+class GemmNote(ctypes.Structure):
+    """hd_gemm_note: the hd_debug_op_info word of the op and what the launchers started."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("op_info", "family", "rows", "pair", "wk", "cpw", "nt", "wide_form", "threads", "grid_x", "grid_y")]
+
+
+GEMM_DRY_RUN = 1
 
 
 def build(force=False, verbose=False):
@@ -149,6 +164,7 @@ def lib():
     L.hd_debug_read_op.argtypes = [vp, i32, i32, vp, i64]; L.hd_debug_read_op.restype = i64
     L.hd_debug_read.argtypes = [vp, ctypes.c_char_p, vp, i64]; L.hd_debug_read.restype = i64
     L.hd_debug_write.argtypes = [vp, ctypes.c_char_p, vp, i64]
+    L.hd_debug_gemm.argtypes = [vp, ctypes.c_char_p, i32, i32, ctypes.POINTER(GemmDesc), i32, ctypes.POINTER(GemmNote), vp]
     L.hd_set_option.argtypes = [vp, ctypes.c_char_p, i32]
     L.hd_get_option.argtypes = [vp, ctypes.c_char_p]
     L.hd_check.argtypes = [vp]

@@ -136,6 +136,15 @@ struct GemmP {
 #define HD_STAMP(i) do { } while (0)
 #endif
 
+// What the GEMM launchers last launched on this thread (host side only; hd_debug_gemm reports it): family 1 tall (gemm_kernel), 2 deep
+// (gemm_deep_*), 3 skinny, 4 wide (hd_wide.hpp); rows per workgroup; PAIR; the skinny kernel's K split WK, its straight-line chunk count
+// CPW (0: the run-time K loop) and weight cache policy NT; the wide form (1 / 2 / 3 as wide_shape_ok numbers them); threads; grid.
+struct LaunchNote { int family, rows, pair, wk, cpw, nt, wide_form, threads, grid_x, grid_y; };
+inline thread_local LaunchNote g_launch_note = {};
+inline void note_launch(int family, int rows, bool pair, int wk, int cpw, bool nt, int wide_form, int threads, const dim3& grid) {
+    g_launch_note = LaunchNote{family, rows, pair ? 1 : 0, wk, cpw, nt ? 1 : 0, wide_form, threads, (int)grid.x, (int)grid.y};
+}
+
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 // two fp32 -> packed bf16 (round to nearest even) in one v_cvt_pk_bf16_f32; two scalar conversions cost two of them plus a merge
@@ -1837,6 +1846,7 @@ inline hipError_t launch_gemm(const GemmP& p, hipStream_t s) {
         { const hipError_t e = grant_dynamic_lds(reinterpret_cast<const void*>(&gemm_kernel<C, LD, EP>), 160 * 1024, granted); if (e != hipSuccess) return e; }
     }
     dim3 grid((p.M + C::BM - 1) / C::BM, (ncols + C::NCOLS - 1) / C::NCOLS, 1);
+    note_launch(1, C::BM, C::PAIR, 1, 0, false, 0, C::THREADS, grid);
     hipLaunchKernelGGL((gemm_kernel<C, LD, EP>), grid, dim3(C::THREADS), smem, s, p);
     return hipGetLastError();
 }
@@ -1861,6 +1871,7 @@ inline hipError_t launch_gemm_deep(const GemmP& p, hipStream_t s) {
     const int ncols = PAIR ? p.N / 2 : p.N;
     const int smem = C::SMEM + (LD::kGainBiasLds ? 2 * p.Kp * 4 : 0) + 2 * (PAIR ? 8 : 4) * 1024;     // + two B chunk buffers
     dim3 grid((p.M + C::BM - 1) / C::BM, ncols / 32, 1);
+    note_launch(2, C::BM, PAIR, 1, 0, false, 0, PAIR ? 512 : C::THREADS, grid);
     if constexpr (PAIR) {                                  // eight waves: four row tiles x the two gate halves
         if (p.Kp == 1024) hipLaunchKernelGGL((gemm_deep_pair8_kernel<LD, EP, 16, P>), grid, dim3(512), smem, s, p);
         else hipLaunchKernelGGL((gemm_deep_pair8_kernel<LD, EP, 8, P>), grid, dim3(512), smem, s, p);
@@ -1879,6 +1890,7 @@ inline hipError_t launch_skinny_inst(const GemmP& p, hipStream_t s, int smem) {
     }
     const int ncols = (C::TNT == 2) ? p.N / 2 : p.N;
     dim3 grid((p.M + C::BM - 1) / C::BM, (ncols + 31) / 32, 1);
+    note_launch(3, C::BM, C::TNT == 2, C::WK, CPW, NT, 0, C::THREADS, grid);
     hipLaunchKernelGGL((gemm_skinny_kernel<C, LD, EP, NT, CPW>), grid, dim3(C::THREADS), smem, s, p);
     return hipGetLastError();
 }

@@ -393,6 +393,7 @@ struct hd_ctx {
     double last_loop_ms = 0.0;
     int last_steps = 0;
     std::map<std::string, std::pair<void*, std::pair<size_t, int>>> dbg;   // context-lifetime names (film, temb); hd_debug_read looks in Workspace::dbg first
+    std::map<std::string, PackedW> dbg_packed;   // hd_debug_gemm: weights packed on first use, by name ("#s2": the sub-pixel-major packing)
 
     // conditioning pool (hd_pool_config): pool_cap entries, each one face's conditioning in the staging chain's layout -- buffer b of
     // CondCopyP order (5 x (prior, w_c, w_s), idc term, id_emb) is pool_buf[b] [pool_cap][pool_sz[b]], all in the one allocation

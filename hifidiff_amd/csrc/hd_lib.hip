@@ -1960,14 +1960,136 @@ const char* hd_debug_op_name(hd_ctx* c, int which, int i) {
     auto* p = which_program(c, which);
     return (i >= 0 && i < (int)p->size()) ? (*p)[i].name.c_str() : "";
 }
+static int op_info_word(const Op& op) {
+    if (!op.gemm || op.lk < 0) return 0;
+    return ((op.lk + 1) & 0xff) | (((op.ek + 1) & 0xff) << 8) | (((op.mode + 1) & 0xff) << 16) | ((op.gemm->xcd_tile_affine ? 1 : 0) << 24) |
+           ((op.gemm->w_nt ? 1 : 0) << 25);
+}
 int hd_debug_op_info(hd_ctx* c, int which, int i) {
     if (!c) return HD_ERR_INVALID;
     auto* p = which_program(c, which);
     if (i < 0 || i >= (int)p->size()) HD_FAIL(c, HD_ERR_INVALID, "no such op %d", i);
-    const Op& op = (*p)[i];
-    if (!op.gemm || op.lk < 0) return 0;
-    return ((op.lk + 1) & 0xff) | (((op.ek + 1) & 0xff) << 8) | (((op.mode + 1) & 0xff) << 16) | ((op.gemm->xcd_tile_affine ? 1 : 0) << 24) |
-           ((op.gemm->w_nt ? 1 : 0) << 25);
+    return op_info_word((*p)[i]);
+}
+
+// One launch of the shared GEMM kernels on the caller's operands (include/hifidiff_hip.h).  Everything the packer or a launcher does
+// not take is refused here, before add_gemm: a refused case never becomes a launch.
+int hd_debug_gemm(hd_ctx* c, const char* weight, int loader, int epilogue, const hd_gemm_desc* d, int flags, hd_gemm_note* note, void* stream) {
+    if (!c) return HD_ERR_INVALID;
+    if (!weight || !d || !note) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: weight, desc and note must not be NULL");
+    *note = hd_gemm_note{};
+    if (c->finalized) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: ctx is finalized (the entry takes a context whose weights are still raw)");
+    static const int pairs[][2] = {{LK_F32, EK_BIASF32}, {LK_F32, EK_PIXSHUF}, {LK_BF16, EK_RESID}, {LK_BF16S, EK_RESID}, {LK_BF16, EK_BIASBF16},
+                                   {LK_BF16, EK_PIXSHUF}, {LK_BF16, EK_BIASF32}, {LK_LN, EK_GATE}, {LK_LN, EK_BIASF32}};
+    bool known = false;
+    for (const auto& pr : pairs) known = known || (pr[0] == loader && pr[1] == epilogue);
+    if (!known) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: loader %d -> epilogue %d is not a pair the GEMM dispatch builds without face geometry", loader, epilogue);
+    const LdKind lk = (LdKind)loader;
+    const EpKind ek = (EpKind)epilogue;
+    const std::string name = weight;
+    const RawTensor* w = find_raw(c, name + ".weight");
+    if (!w || !w->dev) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: weight %s.weight has not been loaded", weight);
+    if (!(w->shape.size() == 2 || (w->shape.size() == 4 && w->shape[2] == 1 && w->shape[3] == 1)))
+        HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: weight %s.weight must be [N][K] or [N][K][1][1]", weight);
+    const int64_t N64 = w->shape[0], K64 = w->shape[1];
+    if (N64 < 1 || N64 > (1 << 20) || K64 < 8 || K64 > (1 << 16)) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: weight %s.weight: N or K out of range", weight);
+    const int N = (int)N64, K = (int)K64;
+    if (K % 8 != 0) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: K = %d of weight %s is not a multiple of 8", K, weight);
+    const RawTensor* b = find_raw(c, name + ".bias");
+    if (b && ((int64_t)b->numel != N64 || !b->dev)) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: weight %s.bias must have N = %d elements", weight, N);
+    const bool ep_f32 = ek == EK_BIASF32 || ek == EK_RESID || ek == EK_PIXSHUF;
+    if (!b && (ek == EK_RESID || ek == EK_GATE || ek == EK_BIASBF16)) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: weight %s.bias is missing (the epilogue reads it)", weight);
+    if (ek == EK_GATE && N % 64 != 0) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: weight N = %d must be a multiple of 64 for the gate epilogue", N);
+    // ---- the descriptor
+    if (d->M < 1 || d->M > (1 << 24)) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: M = %d out of range", d->M);
+    if (d->act < 0 || d->act > 2 || (d->act != 0 && ek != EK_BIASF32 && ek != EK_BIASBF16)) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: act = %d (0 - 2; BIASF32 and BIASBF16 only)", d->act);
+    const int r = d->shuffle_r;
+    if (!(r == 1 || (r == 2 && ek == EK_PIXSHUF))) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: shuffle_r = %d (1, or 2 with the PIXSHUF epilogue)", r);
+    auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
+    auto bad_ptr = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+    auto misaligned = [](const void* p) { return p != nullptr && (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+#define HD_NEED(field) do { if (bad_ptr(d->field)) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: %s is NULL or not 16-byte aligned", #field); } while (0)
+#define HD_OPT(field) do { if (misaligned(d->field)) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: %s is not 16-byte aligned", #field); } while (0)
+#define HD_UNUSED(field) do { if (d->field != nullptr) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: %s is not read or written by this loader / epilogue pair", #field); } while (0)
+    HD_NEED(A); HD_NEED(out);
+    const int a_elems = lk == LK_F32 ? 4 : 8;                 // elements per 16-byte load of the loader
+    if (d->lda < K) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: lda = %d < K = %d", d->lda, K);
+    if (d->lda % a_elems != 0) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: lda = %d must be a multiple of %d (16-byte row loads)", d->lda, a_elems);
+    const bool faces = lk == LK_BF16S || (lk == LK_LN && d->film_face_stride != 0) || d->outg16 != nullptr;
+    if (faces && (d->hw < 1 || d->M % d->hw != 0)) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: M = %d is not a multiple of hw = %d (rows are mapped to faces)", d->M, d->hw);
+    if (lk == LK_LN) {
+        HD_NEED(stats_in); HD_NEED(film);
+        if (d->stats_np < 1 || d->stats_cnt < 1 || (int64_t)d->stats_np * d->stats_cnt != K)
+            HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: stats_np * stats_cnt = %d * %d != K = %d", d->stats_np, d->stats_cnt, K);
+        if (d->film_gain_off < 0 || d->film_bias_off < 0 || d->film_gain_off % 4 != 0 || d->film_bias_off % 4 != 0 || d->film_face_stride < 0 || d->film_face_stride % 4 != 0)
+            HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: film_gain_off / film_bias_off / film_face_stride must be non-negative multiples of 4");
+        if (d->film_face_stride != 0 && d->face0 < 0) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: face0 = %d", d->face0);
+    } else {
+        HD_UNUSED(stats_in); HD_UNUSED(film);
+    }
+    if (lk == LK_BF16S) HD_NEED(rowscale); else HD_UNUSED(rowscale);
+    const int ncols = ek == EK_GATE ? N / 2 : (r == 2 ? N / 4 : N);
+    if (r == 2) {
+        if (N % 4 != 0 || !pow2(d->Win) || !pow2(d->ldo) || d->ldo != N / 4)
+            HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: PixelShuffle r = 2 needs Win = %d and ldo = %d to be powers of two and ldo = N / 4 = %d", d->Win, d->ldo, N / 4);
+        if ((int64_t)d->M % ((int64_t)d->Win * d->Win) != 0) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: M = %d is not a multiple of Win^2 = %d (PixelShuffle)", d->M, d->Win * d->Win);
+    } else if (d->ldo < ncols) {
+        HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: ldo = %d < %d output columns", d->ldo, ncols);
+    }
+    if (ek == EK_RESID) {
+        HD_NEED(resid); HD_NEED(rscale);
+        if (d->ldr < N) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: ldr = %d < N = %d", d->ldr, N);
+        if (d->outg16) { HD_NEED(outg16); HD_NEED(gate_c); HD_NEED(gate_s); HD_OPT(add_src); }
+        else { HD_UNUSED(gate_c); HD_UNUSED(gate_s); HD_UNUSED(add_src); }
+    } else {
+        HD_UNUSED(rscale); HD_UNUSED(outg16); HD_UNUSED(gate_c); HD_UNUSED(gate_s); HD_UNUSED(add_src);
+        if (ek == EK_BIASBF16) { HD_OPT(resid); if (d->resid && d->ldr < N) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: ldr = %d < N = %d", d->ldr, N); }
+        else if (ek == EK_PIXSHUF) HD_OPT(resid);
+        else HD_UNUSED(resid);
+    }
+    if (ep_f32) {
+        HD_OPT(out16); HD_OPT(stats_out);
+        if (d->stats_out && (N % 32 != 0 || (r == 2 && d->ldo % 32 != 0))) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_gemm: stats_out needs whole 32-column tiles (N = %d, ldo = %d)", N, d->ldo);
+    } else {
+        HD_UNUSED(out16); HD_UNUSED(stats_out);
+    }
+#undef HD_NEED
+#undef HD_OPT
+#undef HD_UNUSED
+    // ---- the packed weight (first use: packed on the null stream, then waited for)
+    HIPCHECK(c, hipSetDevice(c->device));
+    const std::string key = name + (r == 2 ? "#s2" : "");
+    auto it = c->dbg_packed.find(key);
+    if (it == c->dbg_packed.end()) {
+        PackedW pw;
+        PackOpts o;
+        if (r == 2) o.S2 = 4;
+        if (const int rc = pack_weight(c, name, &pw, o)) return rc;
+        HIPCHECK(c, hipDeviceSynchronize());
+        it = c->dbg_packed.emplace(key, pw).first;
+    }
+    GemmP p = base_gemm(it->second, d->M);
+    p.A = d->A; p.lda = d->lda; p.a_scale = lk == LK_F32 ? d->a_scale : 1.f;
+    p.hw = faces ? d->hw : 1; p.face0 = d->face0;
+    p.stats_in = reinterpret_cast<const float2*>(d->stats_in);
+    if (lk == LK_LN) { p.stats_np = d->stats_np; p.stats_cnt = d->stats_cnt; }
+    p.film = d->film; p.film_face_stride = d->film_face_stride; p.film_gain_off = d->film_gain_off; p.film_bias_off = d->film_bias_off;
+    p.rowscale = d->rowscale;
+    p.out = d->out; p.ldo = d->ldo; p.out16 = static_cast<unsigned short*>(d->out16); p.outg16 = static_cast<unsigned short*>(d->outg16);
+    p.stats_out = reinterpret_cast<float2*>(d->stats_out);
+    p.resid = d->resid; p.ldr = d->ldr; p.rscale = d->rscale; p.gate_c = d->gate_c; p.gate_s = d->gate_s; p.add_src = d->add_src;
+    p.act = d->act; p.shuffle_r = r;
+    if (ek == EK_PIXSHUF) { p.bias = nullptr; p.Hin = d->Win; p.Win = d->Win; }
+    std::vector<Op> prog;
+    add_gemm(c, prog, "debug_gemm." + name, p, lk, ek);
+    note->op_info = op_info_word(prog[0]);
+    if (flags & HD_GEMM_DRY_RUN) return HD_OK;
+    g_launch_note = LaunchNote{};
+    if (const int rc = run_ops(c, prog, static_cast<hipStream_t>(stream))) return rc;
+    const LaunchNote& ln = g_launch_note;
+    note->family = ln.family; note->rows = ln.rows; note->pair = ln.pair; note->wk = ln.wk; note->cpw = ln.cpw; note->nt = ln.nt;
+    note->wide_form = ln.wide_form; note->threads = ln.threads; note->grid_x = ln.grid_x; note->grid_y = ln.grid_y;
+    return HD_OK;
 }
 static int64_t read_to_host(hd_ctx* c, const void* dev, size_t n, int is_bf16, float* host_out, int64_t max_elems) {
     if (!host_out) return (int64_t)n;

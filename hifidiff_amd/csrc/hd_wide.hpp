@@ -409,6 +409,7 @@ inline hipError_t launch_gemm_wide_inst(const GemmP& p, hipStream_t s) {
     if (EP::kTile && smem < epi) smem = epi;
     static std::atomic<unsigned long long> granted{0};
     { const hipError_t e = grant_dynamic_lds(reinterpret_cast<const void*>(&gemm_wide_kernel<LN, EP, PAIR, FORM, NST>), 160 * 1024, granted); if (e != hipSuccess) return e; }
+    note_launch(4, C::BM, PAIR, 1, 0, false, FORM + 1, C::THREADS, dim3(p.M / C::BM, ncols / 32, 1));
     hipLaunchKernelGGL((gemm_wide_kernel<LN, EP, PAIR, FORM, NST>), dim3(p.M / C::BM, ncols / 32, 1), dim3(C::THREADS), smem, s, p);
     return hipGetLastError();
 }

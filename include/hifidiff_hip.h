@@ -359,6 +359,59 @@ int64_t hd_debug_read(hd_ctx* ctx, const char* name, float* host_out, int64_t ma
 /* overwrite a named internal buffer from host fp32 (bf16 buffers: rounded to nearest even): tests feed a launch the
  * oracle's value of its input ("teacher forcing") so that its own error is not buried under inherited drift */
 int hd_debug_write(hd_ctx* ctx, const char* name, const float* host_in, int64_t n_elems);
+/* One launch of the shared GEMM kernels on the caller's operands (tests: a GEMM needs no network around it).  `ctx` is a context that
+ * has been created but NOT finalized; `weight` names a pair <weight>.weight [N][K] (or [N][K][1][1]) / <weight>.bias [N] given to
+ * hd_load_weights, packed on first use and cached in the context (PixelShuffle r = 2: the sub-pixel-major packing).  `loader` /
+ * `epilogue` are the kinds of hd_debug_op_info (not + 1); the pairs the library builds without face geometry are accepted: F32 ->
+ * BIASF32 / PIXSHUF, BF16 -> RESID / BIASBF16 / PIXSHUF / BIASF32, BF16S -> RESID, LN -> GATE / BIASF32.  The launch goes through the
+ * library's own launch builder: kernel mode, deep / wide kernel, xcd_tile_affine and w_nt are chosen as for a launch of a program, so
+ * every kernel this entry can start is one some program starts for some batch.  Nothing is allocated per call: every pointer of the
+ * descriptor is a DEVICE pointer the caller owns, 16-byte aligned, NULL where the pair does not read it or the output is not wanted.
+ *   A [M][lda]: fp32 (F32) or bf16 (others); a_scale: F32 only.  BF16S: rowscale [M / hw][K].  LN: stats_in [M][stats_np] (mean, M2)
+ *   partials of stats_cnt elements each, film + film_gain_off / film_bias_off [K] fp32 (film_face_stride != 0: the row of face
+ *   face0 + row / hw at that stride, the per-face kernel), ln_eps 1e-6.
+ *   out [M][ldo]: fp32, or bf16 for GATE ([M][N / 2]) and BIASBF16; out16 (bf16 copy, same ld) and stats_out [M][N / 32] (mean, M2)
+ *   for the fp32 epilogues.  RESID: resid fp32 [M][ldr], rscale [N], and with outg16 also gate_c [M / hw][N], gate_s [M], add_src
+ *   ([M][ldo] or NULL).  BIASBF16: resid bf16 [M][ldr] or NULL.  PIXSHUF: no bias; resid (or NULL) in the layout of out;
+ *   shuffle_r = 2: rows are pixels of Win x Win images, out [4 M][ldo] with ldo = N / 4.  act: 0 none, 1 ReLU, 2 sigmoid (BIASF32, BIASBF16).
+ * HD_ERR_INVALID with a message that names the field, before any launch, for: a finalized context, an unknown weight, a pair outside
+ * the list, K % 8 != 0, lda < K, a pointer the pair reads that is NULL or not 16-byte aligned, stats_np * stats_cnt != K, M % hw != 0
+ * where rows are mapped to faces, PixelShuffle r = 2 with Win or ldo not a power of two or M % Win^2 != 0, and leading dimensions the
+ * kernels cannot address.  `note` receives what the launchers started (zero for a dry run) and the hd_debug_op_info word of the op.
+ * flags: HD_GEMM_DRY_RUN = build the op, return its word, launch nothing. */
+typedef struct hd_gemm_desc {
+    int32_t M, hw, face0, act, shuffle_r, Win, stats_np, stats_cnt;
+    float a_scale;
+    int32_t film_face_stride, film_gain_off, film_bias_off;
+    int32_t lda, ldo, ldr;
+    int32_t reserved;
+    const void* A;
+    const float* stats_in;
+    const float* film;
+    const float* rowscale;
+    const void* resid;
+    const float* rscale;
+    const float* gate_c;
+    const float* gate_s;
+    const float* add_src;
+    void* out;
+    void* out16;
+    void* outg16;
+    float* stats_out;
+} hd_gemm_desc;
+typedef struct hd_gemm_note {
+    int32_t op_info;        /* as hd_debug_op_info */
+    int32_t family;         /* 1 tall, 2 deep-prefetch tall, 3 skinny, 4 wide; 0: nothing was launched */
+    int32_t rows;           /* rows per workgroup */
+    int32_t pair;           /* both gate halves in one workgroup */
+    int32_t wk, cpw, nt;    /* skinny: waves along K, chunks per wave of the straight-line K loop (0: the run-time loop), non-temporal weights */
+    int32_t wide_form;      /* wide: 1 (128 rows), 2 (256), 3 (64) */
+    int32_t threads;
+    int32_t grid_x, grid_y;
+} hd_gemm_note;
+enum { HD_GEMM_DRY_RUN = 1 };
+int hd_debug_gemm(hd_ctx* ctx, const char* weight, int loader, int epilogue, const hd_gemm_desc* desc, int flags, hd_gemm_note* note,
+                  void* stream);
 /* Run-time switches that select between equivalent launch programs of the same arithmetic (tests compare them bit for
  * bit; no reference interface corresponds): "xcd" 1/0 = levels 2 / 3 as XCD-local persistent launches (hd_xcd.hpp) or one
  * launch per GEMM; "face" 1/0 the same for levels 0 / 1 (hd_face.hpp); "xcd_phase_limit" n / "face_block_limit" n = stop
