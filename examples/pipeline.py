@@ -18,6 +18,8 @@
                                                           # its structure and colour stay, the diffusion adds the detail
     python examples/pipeline.py --color-fix wavelet [--color-weight 0.8]    # after the decode: the image keeps its detail and takes the
                                                           # coarse restoration's colour (hd_color_fix; also with --stream)
+    python examples/pipeline.py --metrics [--preview-every 10]    # the reference loop's scores: PSNR / SSIM of the final image against
+                                                          # cr_face, and of every preview against the final image (hd_image_metrics)
 """
 import argparse
 import os
@@ -29,7 +31,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from hifidiff_amd import color, sampling, schedulers, synth               # noqa: E402
+from hifidiff_amd import color, metrics, sampling, schedulers, synth               # noqa: E402
 from hifidiff_amd.cr import CoarseRestoration                            # noqa: E402
 from hifidiff_amd.refiner import FacialRefiner                           # noqa: E402
 from hifidiff_amd.vae import AutoencoderKL                               # noqa: E402
@@ -48,6 +50,13 @@ def decode(a, vae, latents, cr_face):
     print(f"colour fix {a.color_fix}, weight {1.0 if a.color_weight is None else a.color_weight}: mean |channel mean - cr_face's| "
           f"{dist(images):.4f} before, {dist(fixed):.4f} after")
     return fixed
+
+
+def scores(result, target):
+    """Mean PSNR / SSIM over the faces, scored as the reference's evaluation loop does (metrics.evaluate: resampled to the target's size,
+    both min-max normalised over the batch; two hd_image_metrics calls on the current stream)."""
+    ev = metrics.evaluate(result, target)
+    return f"PSNR {float(ev.psnr.mean()):.2f} dB, SSIM {float(ev.ssim.mean()):.4f}"
 
 
 def main():
@@ -83,6 +92,9 @@ def main():
                     help="colour-correct the decoded images against cr_face: wavelet (five a-trous levels: the image's detail on the "
                          "reference's low frequencies) or adain (the reference's per-channel mean and deviation); composes with everything")
     ap.add_argument("--color-weight", type=float, default=None, metavar="W", help="--color-fix: weight of the correction in [0, 1] (default 1)")
+    ap.add_argument("--metrics", action="store_true",
+                    help="score the final images against cr_face (mean PSNR / SSIM over the faces, the reference loop's scoring) and, with "
+                         "--preview-every, every decoded preview against the final images; also with --stream")
     a = ap.parse_args()
     if a.color_weight is not None and (a.color_fix is None or not 0.0 <= a.color_weight <= 1.0):
         ap.error("--color-weight needs --color-fix and a value in [0, 1]")
@@ -159,7 +171,9 @@ def main():
         if bool(ran.any()):
             img = vae.decode(snaps[s][ran] / 0.18215).sample
             print(f"preview {s}: row {int(snap_rows[s][ran].max())} of {steps}, {int(ran.sum())} faces, mean |image - final| "
-                  f"{float((img - images[ran]).abs().mean()):.4f}")
+                  f"{float((img - images[ran]).abs().mean()):.4f}" + (f", {scores(img, images[ran])}" if a.metrics else ""))
+    if a.metrics:
+        print(f"final images against cr_face: {scores(images, cr_face)}")
     print(f"batch {B}: coarse restoration {1e3 * (t1 - t0):.1f} ms, VAE encode {1e3 * (t2 - t1):.1f} ms, {steps}-step {a.scheduler} "
           f"{1e3 * (t3 - t2):.1f} ms, VAE decode {1e3 * (t4 - t3):.1f} ms; latent range [{float(out.min()):.2f}, {float(out.max()):.2f}], "
           f"images {tuple(images.shape)} finite {bool(torch.isfinite(images).all())}")
@@ -209,8 +223,11 @@ def stream(a, cr, vae, model, sch, steps, dev):
                       f"x0 std {float(spread):.3f}")
     torch.cuda.synchronize(); t2 = time.time()
     lat = torch.stack([out[i] for i in ids])
-    images = decode(a, vae, lat, torch.stack([f for f, _ in reqs]))
+    cr_faces = torch.stack([f for f, _ in reqs])
+    images = decode(a, vae, lat, cr_faces)
     torch.cuda.synchronize(); t3 = time.time()
+    if a.metrics:
+        print(f"final images against cr_face: {scores(images, cr_faces)}")
     print(f"stream of {N} requests (strength 0.2..1.0), {a.batch} slots, refill every {a.refill_every}: coarse restoration + VAE encode "
           f"{1e3 * (t1 - t0):.1f} ms, {steps}-step {a.scheduler} {1e3 * (t2 - t1):.1f} ms ({N / (t2 - t1):.1f} faces/s, {cs.calls} calls, "
           f"{cs.refilled} slots refilled{f', {cs.pool_prepared} of them prepared ahead in {cs.pool_calls} calls' if a.prefetch else ''}), VAE decode {1e3 * (t3 - t2):.1f} ms; images {tuple(images.shape)} finite "

@@ -3,6 +3,7 @@
 // and their C-ABI entry points.  Internals: hd_internal.hpp.
 #include "hd_internal.hpp"
 #include "hd_color.hpp"
+#include "hd_metrics.hpp"
 
 void set_contextless_error(const std::string& msg);               // hd_lib.hip: the message hd_last_error(NULL) returns
 
@@ -578,6 +579,90 @@ int hd_color_fix(const float* images, float* out, int batch, int res, const floa
     }
     e = hipGetLastError();
     if (e != hipSuccess) CF_FAIL(HD_ERR_HIP, "hd_color_fix: launch failed: %s", hipGetErrorString(e));
+    return HD_OK;
+}
+// Per-face MSE / SSIM of images against a reference and the per-face value range (hd_metrics.hpp).  No context, as hd_color_fix:
+// errors go to hd_last_error(NULL) and every argument is checked before the first HIP call.
+static bool mt_res_ok(int r) { return r >= 64 && r <= 512 && r % 64 == 0; }
+static bool mt_overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a && b && na && nb && a < b + nb && b < a + na; }
+
+int64_t hd_image_metrics_workspace(int batch, int ref_res, int channels) {
+    if (batch < 1 || batch > 65535) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics_workspace: batch must be in [1, 65535], got %d", batch);
+    if (!mt_res_ok(ref_res)) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics_workspace: ref_res must be a multiple of 64 in [64, 512], got %d", ref_res);
+    if (channels != 1 && channels != 2) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics_workspace: channels must be 1 (rgb) or 2 (y), got %d", channels);
+    const int tiles = ref_res / MT_TILE;
+    return (int64_t)batch * (channels == 1 ? 3 : 1) * tiles * tiles * 2 * (int64_t)sizeof(double);
+}
+
+int hd_image_range(const float* images, int batch, int res, int out_res, float* range_out, void* stream) {
+    if (batch < 1) CF_FAIL(HD_ERR_INVALID, "hd_image_range: batch must be >= 1, got %d", batch);
+    if (!mt_res_ok(res)) CF_FAIL(HD_ERR_INVALID, "hd_image_range: res must be a multiple of 64 in [64, 512], got %d", res);
+    if (!mt_res_ok(out_res)) CF_FAIL(HD_ERR_INVALID, "hd_image_range: out_res must be a multiple of 64 in [64, 512], got %d", out_res);
+    if (!images) CF_FAIL(HD_ERR_INVALID, "hd_image_range: images is NULL");
+    if (!range_out) CF_FAIL(HD_ERR_INVALID, "hd_image_range: range_out is NULL");
+    const uintptr_t pi = (uintptr_t)images, po = (uintptr_t)range_out;
+    if (res == out_res && pi % 16) CF_FAIL(HD_ERR_INVALID, "hd_image_range: images must be aligned to 16 bytes when out_res == res (vector loads)");
+    if (pi % sizeof(float)) CF_FAIL(HD_ERR_INVALID, "hd_image_range: images must be aligned to 4 bytes");
+    if (po % sizeof(float)) CF_FAIL(HD_ERR_INVALID, "hd_image_range: range_out must be aligned to 4 bytes");
+    if (mt_overlap(po, (size_t)batch * 2 * sizeof(float), pi, (size_t)batch * 3 * res * res * sizeof(float)))
+        CF_FAIL(HD_ERR_INVALID, "hd_image_range: range_out overlaps images");
+    hipLaunchKernelGGL(range_kernel, dim3(batch), dim3(MT_RANGE_THREADS), 0, reinterpret_cast<hipStream_t>(stream), images, res, out_res, range_out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) CF_FAIL(HD_ERR_HIP, "hd_image_range: launch failed: %s", hipGetErrorString(e));
+    return HD_OK;
+}
+
+int hd_image_metrics(const float* images, int res, const float* ref, int ref_res, int batch, int channels, float data_range,
+                     const float* images_range, const float* ref_range, double* out, float* ssim_map_out, void* workspace,
+                     int64_t workspace_bytes, void* stream) {
+    if (batch < 1 || batch > 65535) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: batch must be in [1, 65535], got %d", batch);
+    if (!mt_res_ok(res)) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: res must be a multiple of 64 in [64, 512], got %d", res);
+    if (!mt_res_ok(ref_res)) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: ref_res must be a multiple of 64 in [64, 512], got %d", ref_res);
+    if (channels != 1 && channels != 2) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: channels must be 1 (rgb) or 2 (y), got %d", channels);
+    if (!(data_range > 0.f) || !std::isfinite(data_range)) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: data_range must be finite and > 0, got %g", (double)data_range);
+    if (!images) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: images is NULL");
+    if (!ref) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: ref is NULL");
+    if (!out) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: out is NULL");
+    if (!workspace) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: workspace is NULL (hd_image_metrics_workspace gives its size)");
+    const int P = channels == 1 ? 3 : 1, tiles = ref_res / MT_TILE, V = ref_res - (MT_WIN - 1);
+    const int64_t need = (int64_t)batch * P * tiles * tiles * 2 * (int64_t)sizeof(double);
+    if (workspace_bytes < need)
+        CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: workspace_bytes is %lld, this call needs %lld (hd_image_metrics_workspace)", (long long)workspace_bytes, (long long)need);
+    const uintptr_t pi = (uintptr_t)images, pr = (uintptr_t)ref, pir = (uintptr_t)images_range, prr = (uintptr_t)ref_range;
+    const uintptr_t po = (uintptr_t)out, pm = (uintptr_t)ssim_map_out, pw = (uintptr_t)workspace;
+    if ((pi | pr | pir | prr | pm) % sizeof(float))
+        CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: images, ref, images_range, ref_range and ssim_map_out must be aligned to 4 bytes");
+    if ((po | pw) % sizeof(double)) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: out and workspace must be aligned to 8 bytes");
+    const size_t nimg = (size_t)batch * 3 * res * res * sizeof(float), nref = (size_t)batch * 3 * ref_res * ref_res * sizeof(float);
+    const size_t nrange = (size_t)batch * 2 * sizeof(float), nout = (size_t)batch * 2 * sizeof(double);
+    const size_t nmap = (size_t)batch * P * V * V * sizeof(float);
+    const struct { const char* name; uintptr_t p; size_t n; } outs[3] = {{"out", po, nout}, {"ssim_map_out", pm, nmap}, {"workspace", pw, (size_t)need}},
+                                                              ins[4] = {{"images", pi, nimg}, {"ref", pr, nref}, {"images_range", pir, nrange}, {"ref_range", prr, nrange}};
+    for (const auto& o : outs)
+        for (const auto& i : ins)
+            if (mt_overlap(o.p, o.n, i.p, i.n)) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: %s overlaps %s", o.name, i.name);
+    for (int i = 0; i < 3; ++i)
+        for (int j = i + 1; j < 3; ++j)
+            if (mt_overlap(outs[i].p, outs[i].n, outs[j].p, outs[j].n)) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: %s overlaps %s", outs[i].name, outs[j].name);
+    MtWindow win;
+    {   // g[k] = exp(-(k - 5)^2 / (2 * 1.5^2)), normalised in float64
+        double g[MT_WIN], sum = 0.0;
+        for (int k = 0; k < MT_WIN; ++k) { g[k] = std::exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5)); sum += g[k]; }
+        for (int k = 0; k < MT_WIN; ++k) win.g[k] = (float)(g[k] / sum);
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    double* partial = static_cast<double*>(workspace);
+    const dim3 grid(tiles * tiles, P, batch);
+    if (channels == 1)
+        hipLaunchKernelGGL(metrics_kernel<0>, grid, dim3(MT_THREADS), 0, s, images, res, ref, ref_res, data_range, images_range, ref_range, win, partial, ssim_map_out);
+    else
+        hipLaunchKernelGGL(metrics_kernel<1>, grid, dim3(MT_THREADS), 0, s, images, res, ref, ref_res, data_range, images_range, ref_range, win, partial, ssim_map_out);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) CF_FAIL(HD_ERR_HIP, "hd_image_metrics: launch failed: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(metrics_combine_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, partial, batch, P * tiles * tiles,
+                       1.0 / ((double)P * ref_res * ref_res), 1.0 / ((double)P * V * V), out);
+    e = hipGetLastError();
+    if (e != hipSuccess) CF_FAIL(HD_ERR_HIP, "hd_image_metrics: launch failed: %s", hipGetErrorString(e));
     return HD_OK;
 }
 #undef CF_FAIL

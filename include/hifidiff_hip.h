@@ -299,6 +299,45 @@ int hd_guide_faces(hd_ctx* ctx, int n, const int32_t* slots, const float* target
 int hd_color_fix(const float* images, float* out, int batch, int res, const float* ref, int ref_res, int ref_vae_range,
                  int mode, int levels, const float* weight, void* stream);
 
+/* Per-face PSNR and SSIM of images against a reference: what the reference's evaluation loop does with its result (test_refiner.py:113-122:
+ * F.interpolate to the target's size, min-max normalise, pyiqa's psnr and ssim).  pyiqa is third party and absent, so parity with its
+ * defaults is unpinned, like the schedulers'; the formulas below are the contract.  LPIPS and NIQE need learned weights and are not offered.
+ * images [B,3,res,res], ref [B,3,ref_res,ref_res] (device fp32 NCHW; res and ref_res multiples of 64 in [64, 512]).  Everything is scored
+ * at the reference's side Rb = ref_res.  Per face:
+ *   1. a = F.interpolate(images, Rb, mode = "bicubic", align_corners = False) when res != ref_res (no antialiasing, taps clamped to the
+ *      border: the rule hd_vae_encode and hd_color_fix use), else images; b = ref.  The resampling happens while the pixels are loaded.
+ *   2. with images_range / ref_range [B,2] (device fp32: lo, hi per face):  x' = (x - lo) / (hi - lo), and x' = 0 where hi <= lo (torch's
+ *      (x - min) / (max - min) gives NaN there).  NULL: no normalisation of that tensor.
+ *   3. channels = 1 (rgb): the three planes are scored independently, P = 3.
+ *      channels = 2 (y):   one plane Y = (65.481 R + 128.553 G + 24.966 B + 16 L) / 255, L = data_range (BT.601 studio luma), P = 1.
+ *   4. mse  = mean over the P planes and all Rb^2 pixels of (a' - b')^2.  PSNR = 10 log10(L^2 / mse) is left to the caller (+inf at 0).
+ *   5. ssim (Wang et al. 2004) = mean over the P planes and the (Rb - 10)^2 "valid" window positions of
+ *        ((2 mu_a mu_b + C1) (2 s_ab + C2)) / ((mu_a^2 + mu_b^2 + C1) (s_a + s_b + C2)),      C1 = (0.01 L)^2, C2 = (0.03 L)^2,
+ *      mu_a, mu_b, E[a^2], E[b^2], E[ab] the window-weighted moments, s_a = E[a^2] - mu_a^2, s_b likewise, s_ab = E[ab] - mu_a mu_b (no
+ *      unbiased correction), the window g[k] g[l] with g[k] = exp(-(k - 5)^2 / (2 * 1.5^2)), k = 0..10, normalised to sum 1 in float64.
+ * out [B,2] (device fp64): mse, ssim.  ssim_map_out: NULL, or device fp32 [B,P,Rb-10,Rb-10] that receives the map of step 5.
+ * One launch computes everything per (64 x 64 tile, plane, face): a 74 x 74 region of a' and b' is staged in LDS once, the five moment
+ * maps live in registers (fp32 window sums: a horizontal then a vertical 11-tap pass), and the tile's two sums are fp64.  A second, tiny
+ * launch adds each face's tile sums in index order.  No atomics: a face's two numbers and its map have the same bits from call to call
+ * and at every position of every batch.  workspace: device memory of at least hd_image_metrics_workspace(batch, ref_res, channels) bytes
+ * (the tile sums), owned by the caller, overwritten by the call, free to reuse when the call's work on `stream` is done.
+ * hd_image_range: range_out [B,2] (device fp32) = the minimum and maximum over the three channels of each face of images as resampled to
+ * out_res (step 1; out_res == res: the image itself, and then the result is exactly min / max).  One launch, one workgroup per face.
+ * NaN pixels are not propagated (fminf / fmaxf).  Feeding it to images_range / ref_range is `normalize = "face"` of
+ * hifidiff_amd.metrics; the batch-wide pair of the reference's loop is the min / max of these over the faces.
+ * All three calls need no context, allocate nothing and do not synchronise; the two that launch enqueue on `stream` and only read their
+ * inputs.  Errors are reported through hd_last_error(NULL).  HD_ERR_INVALID, naming the argument and before any HIP call, for: batch < 1
+ * (hd_image_metrics: > 65535); res, ref_res or out_res not a multiple of 64 in [64, 512]; channels other than 1 or 2; data_range not
+ * finite or <= 0; a NULL images, ref, out, range_out or workspace; workspace_bytes too small; a pointer not aligned to 4 bytes (out and
+ * workspace: 8 bytes; images of hd_image_range with out_res == res: 16 bytes, it is read as float4); out, ssim_map_out or workspace
+ * overlapping an input or each other, range_out overlapping images, as byte ranges.  hd_image_metrics_workspace returns HD_ERR_INVALID
+ * for arguments hd_image_metrics would refuse. */
+int hd_image_range(const float* images, int batch, int res, int out_res, float* range_out, void* stream);
+int64_t hd_image_metrics_workspace(int batch, int ref_res, int channels);
+int hd_image_metrics(const float* images, int res, const float* ref, int ref_res, int batch, int channels, float data_range,
+                     const float* images_range, const float* ref_range, double* out, float* ssim_map_out, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+
 /* Progress previews: the denoised estimate of the row a face last ran, as an output of the sampling loop (diffusers'
  * `pred_original_sample` / `callback_on_step_end`).
  * hd_preview_config(on = 1, every, snapshots): from the next hd_prepare* on -- at once, when a batch is prepared -- the context owns the
