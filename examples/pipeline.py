@@ -20,6 +20,8 @@
                                                           # coarse restoration's colour (hd_color_fix; also with --stream)
     python examples/pipeline.py --metrics [--preview-every 10]    # the reference loop's scores: PSNR / SSIM of the final image against
                                                           # cr_face, and of every preview against the final image (hd_image_metrics)
+    python examples/pipeline.py --metrics --lpips-weights alexnet.pth,lin.pth    # also LPIPS (hd_lpips) with a local AlexNet file and the lin
+                                                          # layers' file; --lpips-synthetic: synthetic weights, to see the call run
 """
 import argparse
 import os
@@ -52,11 +54,27 @@ def decode(a, vae, latents, cr_face):
     return fixed
 
 
-def scores(result, target):
-    """Mean PSNR / SSIM over the faces, scored as the reference's evaluation loop does (metrics.evaluate: resampled to the target's size,
-    both min-max normalised over the batch; two hd_image_metrics calls on the current stream)."""
-    ev = metrics.evaluate(result, target)
-    return f"PSNR {float(ev.psnr.mean()):.2f} dB, SSIM {float(ev.ssim.mean()):.4f}"
+def scores(result, target, lpips=None):
+    """Mean PSNR / SSIM (and LPIPS, given a loaded model) over the faces, scored as the reference's evaluation loop does
+    (metrics.evaluate: resampled to the target's size, both min-max normalised over the batch; two hd_image_metrics calls and one
+    hd_lpips call on the current stream)."""
+    ev = metrics.evaluate(result, target, lpips=lpips)
+    text = f"PSNR {float(ev.psnr.mean()):.2f} dB, SSIM {float(ev.ssim.mean()):.4f}"
+    return text if ev.lpips is None else text + f", LPIPS {float(ev.lpips.mean()):.4f}"
+
+
+def lpips_model(a, dev):
+    """--lpips-weights A,B: a torchvision AlexNet state dict and the lin layers' state dict, two local files.  --lpips-synthetic:
+    synthetic weights."""
+    if a.lpips_weights is None and not a.lpips_synthetic:
+        return None
+    if a.lpips_weights is not None:
+        m = metrics.LPIPS.from_files(*a.lpips_weights.split(","))
+    else:
+        m = metrics.LPIPS()
+        m.load_state_dict(synth.lpips_state_dict())
+        print("LPIPS: the weights are synthetic; the number is not comparable to published LPIPS")
+    return m.to(dev)
 
 
 def main():
@@ -95,7 +113,15 @@ def main():
     ap.add_argument("--metrics", action="store_true",
                     help="score the final images against cr_face (mean PSNR / SSIM over the faces, the reference loop's scoring) and, with "
                          "--preview-every, every decoded preview against the final images; also with --stream")
+    ap.add_argument("--lpips-weights", default=None, metavar="A,B",
+                    help="--metrics: also LPIPS-AlexNet, with a torchvision AlexNet state dict A and the lin layers' state dict B (local files)")
+    ap.add_argument("--lpips-synthetic", action="store_true",
+                    help="--metrics: also LPIPS with synthetic weights (the number is not comparable to published LPIPS)")
     a = ap.parse_args()
+    if (a.lpips_weights is not None or a.lpips_synthetic) and not a.metrics:
+        ap.error("--lpips-weights / --lpips-synthetic need --metrics")
+    if a.lpips_weights is not None and len(a.lpips_weights.split(",")) != 2:
+        ap.error("--lpips-weights takes two files: A,B")
     if a.color_weight is not None and (a.color_fix is None or not 0.0 <= a.color_weight <= 1.0):
         ap.error("--color-weight needs --color-fix and a value in [0, 1]")
     if a.preview_every is not None and a.preview_every < 1:
@@ -118,6 +144,7 @@ def main():
     model = FacialRefiner(latent_res=16)
     model.load_state_dict(synth.refiner_state_dict(16))  # real use: safetensors.torch.load_file(refiner_ckpt)
     model.to(dev)
+    a.lpips = lpips_model(a, dev)
     if a.scheduler == "ddim":
         sch = schedulers.DDIMScheduler(num_train_timesteps=1000, beta_schedule="scaled_linear", prediction_type="epsilon",
                                        clip_sample_range=3.0)
@@ -171,9 +198,9 @@ def main():
         if bool(ran.any()):
             img = vae.decode(snaps[s][ran] / 0.18215).sample
             print(f"preview {s}: row {int(snap_rows[s][ran].max())} of {steps}, {int(ran.sum())} faces, mean |image - final| "
-                  f"{float((img - images[ran]).abs().mean()):.4f}" + (f", {scores(img, images[ran])}" if a.metrics else ""))
+                  f"{float((img - images[ran]).abs().mean()):.4f}" + (f", {scores(img, images[ran], a.lpips)}" if a.metrics else ""))
     if a.metrics:
-        print(f"final images against cr_face: {scores(images, cr_face)}")
+        print(f"final images against cr_face: {scores(images, cr_face, a.lpips)}")
     print(f"batch {B}: coarse restoration {1e3 * (t1 - t0):.1f} ms, VAE encode {1e3 * (t2 - t1):.1f} ms, {steps}-step {a.scheduler} "
           f"{1e3 * (t3 - t2):.1f} ms, VAE decode {1e3 * (t4 - t3):.1f} ms; latent range [{float(out.min()):.2f}, {float(out.max()):.2f}], "
           f"images {tuple(images.shape)} finite {bool(torch.isfinite(images).all())}")
@@ -227,7 +254,7 @@ def stream(a, cr, vae, model, sch, steps, dev):
     images = decode(a, vae, lat, cr_faces)
     torch.cuda.synchronize(); t3 = time.time()
     if a.metrics:
-        print(f"final images against cr_face: {scores(images, cr_faces)}")
+        print(f"final images against cr_face: {scores(images, cr_faces, a.lpips)}")
     print(f"stream of {N} requests (strength 0.2..1.0), {a.batch} slots, refill every {a.refill_every}: coarse restoration + VAE encode "
           f"{1e3 * (t1 - t0):.1f} ms, {steps}-step {a.scheduler} {1e3 * (t2 - t1):.1f} ms ({N / (t2 - t1):.1f} faces/s, {cs.calls} calls, "
           f"{cs.refilled} slots refilled{f', {cs.pool_prepared} of them prepared ahead in {cs.pool_calls} calls' if a.prefetch else ''}), VAE decode {1e3 * (t3 - t2):.1f} ms; images {tuple(images.shape)} finite "

@@ -280,3 +280,28 @@ def vae_manifest():
     _gn(o, "decoder.conv_norm_out", 128)
     _conv(o, "decoder.conv_out", 3, 128, 3, 3)
     return o
+
+
+# ------------------------------------------------------------------------------------------------ LPIPS (AlexNet, v0.1)
+# torchvision's AlexNet `features` as the `lpips` package slices it (net.slice{n}.{index in features}) and its five 1x1 "lin" layers.
+# The package is absent: these key names are written from memory of its full-model state dict and are unpinned.
+LPIPS_CONVS = (("net.slice1.0", 64, 3, 11, 4, 2), ("net.slice2.3", 192, 64, 5, 1, 2), ("net.slice3.6", 384, 192, 3, 1, 1),
+               ("net.slice4.8", 256, 384, 3, 1, 1), ("net.slice5.10", 256, 256, 3, 1, 1))      # name, Cout, Cin, k, stride, pad
+LPIPS_SHIFT, LPIPS_SCALE = (-.030, -.088, -.188), (.458, .448, .450)
+LPIPS_SCALING_KEYS = ("scaling_layer.shift", "scaling_layer.scale")                            # optional in a state dict, [1,3,1,1]
+
+
+def lpips_manifest():
+    o = OrderedDict()
+    for name, cout, cin, k, _, _ in LPIPS_CONVS:
+        _conv(o, name, cout, cin, k, k)
+    for i, (_, cout, _, _, _, _) in enumerate(LPIPS_CONVS):
+        o[f"lin{i}.model.1.weight"] = ((1, cout, 1, 1), "lpips_lin", cout)
+    return o
+
+
+def lpips_sides(res):
+    """Tap sides (s1, s2, s3) of an input of side res; the five layers have sides s1, s2, s3, s3, s3."""
+    s1 = (res - 7) // 4 + 1
+    s2 = (s1 - 3) // 2 + 1
+    return s1, s2, (s2 - 3) // 2 + 1

@@ -154,6 +154,11 @@ constexpr int kGraphSteps = 10;              // diffusion steps per captured gra
 struct VaeWs { float *X = nullptr, *T = nullptr, *S = nullptr, *mom = nullptr, *Q = nullptr, *K = nullptr, *V = nullptr, *resz = nullptr, *out3 = nullptr;
                unsigned short *H = nullptr, *H2 = nullptr, *Xb = nullptr, *U = nullptr; uint4* in8 = nullptr; double* part = nullptr; int B = 0, R = 0; };
 
+struct LpScale { float shift[3], scale[3]; };          // LPIPS: the scaling layer (hd_lpips.hpp: lpips_input_kernel)
+// LPIPS (hd_lpips.hip): the prepared 2B faces (a faces, then b faces), the five tapped feature maps, the two pooled maps and the
+// distance kernel's partial sums, for B faces scored at side R
+struct LpWs { uint4* in8 = nullptr; unsigned short *f[5] = {}, *pool[2] = {}; double* part = nullptr; int B = 0, R = 0; };
+
 struct Workspace {
     Workspace() = default;
     Workspace(const Workspace&) = delete;
@@ -187,6 +192,11 @@ struct Workspace {
     const void *vae_enc_key[4] = {}, *vae_dec_key[2] = {};
     int vae_enc_flags = -1;
     uint64_t vae_seed = 0;
+    // LPIPS: the buffers, and the launch program with the caller's pointers and flags it captured
+    LpWs lws;
+    std::vector<Op> lpips_prog;
+    const void* lpips_key[6] = {};
+    int lpips_flags = -1;
 };
 
 // Which evaluation a launch of Chain::program is part of.  Every closure of the program derives what it needs from this one value:
@@ -349,6 +359,10 @@ struct hd_ctx {
         const float *enc_nw = nullptr, *enc_nb = nullptr, *dec_nw = nullptr, *dec_nb = nullptr;
         const float *quant_w = nullptr, *quant_b = nullptr, *pq_w = nullptr, *pq_b = nullptr, *ones = nullptr;
     } vw;
+
+    // LPIPS-AlexNet context (hd_lpips_create; hd_lpips.hip): the five convolutions, the 1x1 "lin" weightings, the scaling layer
+    bool lpips = false;
+    struct LpipsW { PackedW conv[5]; const float* lin[5] = {}; LpScale sc; } lw;
 
     // XCD-local persistent stages (hd_xcd.hpp): latent 16, batch <= 64, one chain, one FiLM row for all faces
     struct XStage {
@@ -1125,3 +1139,5 @@ int make_dw_layout(hd_ctx* c, BlockW& bw) {
 // hd_aux.hip
 int finalize_cr(hd_ctx* c);
 int finalize_vae(hd_ctx* c);
+// hd_lpips.hip
+int finalize_lpips(hd_ctx* c);

@@ -715,6 +715,7 @@ int hd_finalize_weights(hd_ctx* c) {
     HIPCHECK(c, hipSetDevice(c->device));
     if (c->cr) return finalize_cr(c);
     if (c->vae) return finalize_vae(c);
+    if (c->lpips) return finalize_lpips(c);
     // ---- strict key / shape check ----
     const auto man = build_manifest(c->L, c->conditional);
     for (const auto& e : man) {
@@ -1033,7 +1034,7 @@ static int finish_prepare(hd_ctx* c, hipStream_t s) {
 
 // Unconditional Denoiser: nothing to condition on -- size the workspace for `batch` faces and build the launch program.
 int hd_prepare_unconditional(hd_ctx* c, int batch, void* stream) {
-    if (c && c->cr) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_unconditional: this context holds CoarseRestoration");
+    if (c && (c->cr || c->lpips)) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_unconditional: this context holds CoarseRestoration or LPIPS");
     if (c && c->conditional) HD_FAIL(c, HD_ERR_INVALID, "hd_prepare_unconditional: this context holds the conditional FusedDenoiser");
     int rc = prepare_common(c, batch);
     if (rc) return rc;
@@ -1763,7 +1764,7 @@ int hd_pool_commit(hd_ctx* c, int n, const int32_t* slots, const int32_t* entrie
 // list (the whole batch, in order) or n distinct slots.
 static int loop_ctx_enter(hd_ctx* c, const char* fn) {
     if (!c) return HD_ERR_INVALID;
-    if (c->cr || c->vae) HD_FAIL(c, HD_ERR_INVALID, "%s: this context holds CoarseRestoration or the VAE (no sampling loop)", fn);
+    if (c->cr || c->vae || c->lpips) HD_FAIL(c, HD_ERR_INVALID, "%s: this context holds CoarseRestoration, the VAE or LPIPS (no sampling loop)", fn);
     return HD_OK;
 }
 static int faces_enter(hd_ctx* c, const char* fn, int n, const int32_t* slots) {
@@ -1945,6 +1946,7 @@ static std::vector<Op>* which_program(hd_ctx* c, int which) {
     static std::vector<Op> empty;
     if (c->cr) return &c->ws->cr_program;
     if (c->vae) return which == 0 ? &c->ws->vae_enc_prog : &c->ws->vae_dec_prog;
+    if (c->lpips) return &c->ws->lpips_prog;
     if (c->ws->chains.empty()) return &empty;
     return which == 0 ? &c->ws->chains[0].program : &c->ws->chains[0].prep_program;
 }

@@ -1,25 +1,30 @@
-"""Per-face PSNR and SSIM of images against a reference: the scores of the reference's evaluation loop (`val_loop`,
-test_refiner.py:113-122: F.interpolate to the target's size, min-max normalise, pyiqa's psnr and ssim).  LPIPS and NIQE need learned
-weights and are not offered.  pyiqa itself is absent, so parity with its defaults is unpinned, like the schedulers'; the formulas in
-include/hifidiff_hip.h (hd_image_metrics) are the contract.
+"""Per-face PSNR, SSIM and LPIPS of images against a reference: the scores of the reference's evaluation loop (`val_loop`,
+test_refiner.py:107-123: F.interpolate to the target's size, min-max normalise, pyiqa's psnr, ssim and lpips).  NIQE needs a fitted
+model file and is not offered.  pyiqa and the `lpips` package are absent, so parity with their defaults is unpinned, like the
+schedulers'; the formulas in include/hifidiff_hip.h (hd_image_metrics, hd_lpips) are the contract.
 
 `image_metrics`, `image_range` and `evaluate` run in libhifidiff_hip.so (hd_image_metrics: a fused windowed-moment stencil and a
 fixed-order fp64 reduction, GPU only, bit-reproducible and independent of a face's position in the batch).  The `*_reference` functions
-state the same formulas in plain torch, in any dtype and on any device: the role `color.*_reference` play for the colour fix."""
+state the same formulas in plain torch, in any dtype and on any device: the role `color.*_reference` play for the colour fix.
+
+`LPIPS` is a module-shaped object in the style of `vae.AutoencoderKL` (AlexNet, v0.1 lin weights, hd_lpips); `lpips_reference` states its
+contract in plain torch.  The weights come from the caller (`load_state_dict`, `from_files`) or, for tests, from `synth`."""
 import collections
+import ctypes
 import math
 
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, arch
 
 CHANNELS = {"rgb": 1, "y": 2}
 NORMALIZE = (None, "face", "batch")
 WINDOW, SIGMA = 11, 1.5
 
-Metrics = collections.namedtuple("Metrics", "mse psnr ssim ssim_map")
-Metrics.__doc__ = "Per-face scores: mse, psnr, ssim are [B]; ssim_map is [B,P,Rb-10,Rb-10] (P = 3 for rgb, 1 for y) or None."
+Metrics = collections.namedtuple("Metrics", "mse psnr ssim ssim_map lpips", defaults=(None,))
+Metrics.__doc__ = ("Per-face scores: mse, psnr, ssim are [B]; ssim_map is [B,P,Rb-10,Rb-10] (P = 3 for rgb, 1 for y) or None; lpips is [B] "
+                   "where a loaded LPIPS model was given, else None.")
 
 
 # ------------------------------------------------------------------------------------------------ reference formulas, plain torch
@@ -201,15 +206,18 @@ def image_metrics(images, ref, channels="y", data_range=1.0, normalize=None, ssi
     return Metrics(mse, psnr_from_mse(mse, float(data_range)), out[:, 1], smap)
 
 
-Evaluation = collections.namedtuple("Evaluation", "psnr ssim")
+Evaluation = collections.namedtuple("Evaluation", "psnr ssim lpips", defaults=(None,))
 
 
-def evaluate(result, target):
-    """The reference loop's scoring as one call (test_refiner.py:113-122): `result` resampled to the target's size, both tensors
+def evaluate(result, target, lpips=None):
+    """The reference loop's scoring as one call (test_refiner.py:107-123): `result` resampled to the target's size, both tensors
     min-max normalised over the whole batch, data_range 1; per-face PSNR over the rgb planes and SSIM on luma (pyiqa's defaults for
-    "psnr" and "ssim", unpinned).  Evaluation(psnr, ssim), float64 [B] on the device."""
-    return Evaluation(image_metrics(result, target, channels="rgb", normalize="batch").psnr,
-                      image_metrics(result, target, channels="y", normalize="batch").ssim)
+    "psnr" and "ssim", unpinned).  lpips: a loaded `LPIPS` model, and then the third score (normalize=True on the batch-normalised
+    tensors, which reach the kernel as their two ranges and are not materialised), else None.  Evaluation(psnr, ssim, lpips), float64
+    [B] on the device."""
+    psnr = image_metrics(result, target, channels="rgb", normalize="batch").psnr
+    ssim = image_metrics(result, target, channels="y", normalize="batch").ssim
+    return Evaluation(psnr, ssim, None if lpips is None else lpips(result, target, normalize=True, input_normalize="batch"))
 
 
 def evaluate_reference(result, target):
@@ -219,3 +227,216 @@ def evaluate_reference(result, target):
     rn = (r - r.min()) / (r.max() - r.min())
     tn = (t - t.min()) / (t.max() - t.min())
     return Evaluation(psnr_reference(rn, tn, 1.0), ssim_reference(rgb_to_y(rn, 1.0), rgb_to_y(tn, 1.0), 1.0))
+
+
+# ------------------------------------------------------------------------------------------------ LPIPS
+def _bf16(x):
+    """The value a kernel stores as bf16 (fp32 arithmetic, then round to nearest even), back in x's dtype."""
+    return x.to(torch.float32).to(torch.bfloat16).to(x.dtype)
+
+
+def lpips_features(state, x, emulate_bf16=False):
+    """The five tapped AlexNet activations of the prepared input x [N,3,R,R] (after the scaling layer), in x's dtype."""
+    q = _bf16 if emulate_bf16 else (lambda t: t)
+    h, feats = q(x), []
+    for i, (name, _, _, _, stride, pad) in enumerate(arch.LPIPS_CONVS):
+        if i in (1, 2):
+            h = F.max_pool2d(h, 3, 2)
+        w, b = state[name + ".weight"].to(device=x.device, dtype=x.dtype), state[name + ".bias"].to(device=x.device, dtype=x.dtype)
+        h = q(torch.relu(F.conv2d(h, q(w), b, stride=stride, padding=pad)))
+        feats.append(h)
+    return feats
+
+
+def lpips_distance(state, fa, fb):
+    """Steps 6 of the contract for the feature lists fa, fb: [N,5] per-layer distances d_k."""
+    out = []
+    for k, (a, b) in enumerate(zip(fa, fb)):
+        w = state["lin%d.model.1.weight" % k].to(device=a.device, dtype=a.dtype).reshape(1, -1, 1, 1)
+        na = a / (a.pow(2).sum(dim=1, keepdim=True).sqrt() + 1e-10)
+        nb = b / (b.pow(2).sum(dim=1, keepdim=True).sqrt() + 1e-10)
+        out.append((w * (na - nb).pow(2)).sum(dim=1).mean(dim=(1, 2)))
+    return torch.stack(out, dim=1)
+
+
+def lpips_prepare(state, x, rng, normalize):
+    """Steps 2 - 4 for a tensor already at the scored size: min-max with rng [B,2] (None: none), 2x - 1, the scaling layer."""
+    if rng is not None:
+        x = normalize_reference(x, rng.to(x.dtype))
+    if normalize:
+        x = 2 * x - 1
+    shift = state.get(arch.LPIPS_SCALING_KEYS[0], torch.tensor(arch.LPIPS_SHIFT, dtype=torch.float64)).to(device=x.device, dtype=x.dtype)
+    scale = state.get(arch.LPIPS_SCALING_KEYS[1], torch.tensor(arch.LPIPS_SCALE, dtype=torch.float64)).to(device=x.device, dtype=x.dtype)
+    return (x - shift.reshape(1, 3, 1, 1)) / scale.reshape(1, 3, 1, 1)
+
+
+def lpips_reference(state, images, ref, normalize=True, input_normalize=None, per_layer=False, emulate_bf16=False):
+    """The contract of hd_lpips (include/hifidiff_hip.h) from torch ops, in the dtype and on the device of `images`: LPIPS-AlexNet v0.1
+    of images [B,3,R,R] against ref [B,3,Rb,Rb] at ref's size.  state: the weights under arch.lpips_manifest's names.  normalize: the
+    inputs are in [0, 1] (2x - 1 first).  input_normalize: None, "face" or "batch" min-max normalisation first, as in `image_metrics`.
+    emulate_bf16: round to bf16 where the kernels do (the conv weights, the prepared input, every stored activation).  Returns [B], or
+    ([B], [B,5]) with per_layer."""
+    if input_normalize not in NORMALIZE:
+        raise ValueError("input_normalize must be None, 'face' or 'batch', got %r" % (input_normalize,))
+    a, b = resample(images, ref.shape[-1]), ref.to(images.dtype)
+    ra = rb = None
+    if input_normalize is not None:
+        ra, rb = range_reference(a), range_reference(b)
+        if input_normalize == "batch":
+            ra, rb = _batch_range(ra), _batch_range(rb)
+    fa = lpips_features(state, lpips_prepare(state, a, ra, normalize), emulate_bf16)
+    fb = lpips_features(state, lpips_prepare(state, b, rb, normalize), emulate_bf16)
+    layers = lpips_distance(state, fa, fb)
+    total = layers.sum(dim=1)
+    return (total, layers) if per_layer else total
+
+
+class LPIPS:
+    """LPIPS-AlexNet v0.1 in libhifidiff_hip.so (hd_lpips).  GPU only.  `load_state_dict` takes the `lpips` package's full-model names
+    (arch.lpips_manifest; unpinned, the package is absent), or a torchvision AlexNet file's `features.{0,3,6,8,10}.*` (`classifier.*` is
+    ignored) together with the lin layers as `lin{k}.model.1.weight` or `lins.{k}.model.1.weight`."""
+
+    _FEATURES = {"features.%s" % n.rsplit(".", 1)[1]: n for n, *_ in arch.LPIPS_CONVS}     # features.0 -> net.slice1.0, ...
+
+    def __init__(self):
+        self._ctx, self._device, self._state, self._loaded, self._keep, self._complete = None, None, None, False, None, False
+
+    @classmethod
+    def from_files(cls, alexnet_path, lin_path):
+        """Two local files (torch.save'd state dicts): the AlexNet features and the lin layers.  No hub access."""
+        sd = {}
+        for path in (alexnet_path, lin_path):
+            part = torch.load(path, map_location="cpu", weights_only=True)
+            if not isinstance(part, dict):
+                raise RuntimeError("%s does not hold a state dict" % path)
+            sd.update(part)
+        m = cls()
+        m.load_state_dict(sd)
+        return m
+
+    @classmethod
+    def _canonical_keys(cls, sd):
+        out = {}
+        for k, v in sd.items():
+            if k.startswith("classifier."):
+                continue
+            head, _, leaf = k.rpartition(".")
+            if head in cls._FEATURES:
+                k = cls._FEATURES[head] + "." + leaf
+            elif k.startswith("lins."):
+                k = "lin" + k[len("lins."):]
+            if not torch.is_tensor(v):
+                continue                                   # non-weight entries (metadata some exporters add)
+            out[k] = v
+        return out
+
+    def load_state_dict(self, sd, strict=True):
+        man = arch.lpips_manifest()
+        sd = self._canonical_keys(sd)
+        shapes = {k: v[0] for k, v in man.items()}
+        if any(k in sd for k in arch.LPIPS_SCALING_KEYS):    # optional, but both or neither
+            shapes.update({k: (1, 3, 1, 1) for k in arch.LPIPS_SCALING_KEYS})
+        missing = [k for k in shapes if k not in sd]
+        unexpected = [k for k in sd if k not in shapes]
+        if strict and (missing or unexpected):
+            raise RuntimeError("Error(s) in loading state_dict for LPIPS: Missing key(s): %s; Unexpected key(s): %s" % (missing[:4], unexpected[:4]))
+        for k, shape in shapes.items():
+            if k in sd and tuple(sd[k].shape) != tuple(shape):
+                raise RuntimeError("size mismatch for %s: got %s, expected %s" % (k, tuple(sd[k].shape), tuple(shape)))
+        self._state = {k: sd[k].detach() for k in shapes if k in sd}
+        self._complete = not missing
+        if self._ctx is not None:
+            self._upload()                                 # a context whose weights are finalized is replaced (self._loaded)
+        return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
+
+    def state_dict(self, *a, **k):
+        return dict(self._state or {})
+
+    def to(self, *args, **kwargs):
+        device = kwargs.get("device", args[0] if args else None)
+        if isinstance(device, (str, torch.device, int)):
+            self._ensure(torch.device("cuda", device) if isinstance(device, int) else torch.device(device))
+        return self
+
+    def cuda(self, device=None):
+        return self.to(torch.device("cuda", device if device is not None else torch.cuda.current_device()))
+
+    def _ensure(self, device):
+        if device.type != "cuda":
+            raise RuntimeError("hifidiff_amd runs on an MI355X (gfx950) GPU only; got device %s (no CPU fallback)" % device)
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        if self._ctx is not None:
+            if idx != self._device.index:
+                raise RuntimeError("this model already lives on cuda:%d" % self._device.index)
+            return
+        ctx = ctypes.c_void_p()
+        _lib.check(_lib.lib().hd_lpips_create(ctypes.byref(ctx), idx))
+        self._ctx, self._device = ctx, torch.device("cuda", idx)
+        if self._state is not None:
+            self._upload()
+
+    def _upload(self):
+        if not self._complete:
+            raise RuntimeError("state dict incomplete: %d tensors loaded" % len(self._state))
+        L = _lib.lib()
+        keep, descs = [], (_lib.TensorDesc * len(self._state))()
+        for i, (k, v) in enumerate(self._state.items()):
+            t = v.to(torch.float32).contiguous()
+            keep.append(t)
+            d = descs[i]
+            d.name, d.data, d.ndim, d.is_device = k.encode(), t.data_ptr(), t.dim(), 1 if t.is_cuda else 0
+            for j, n in enumerate(t.shape):
+                d.shape[j] = n
+        if self._loaded:
+            L.hd_destroy(self._ctx)
+            self._ctx = None
+            self._loaded = False                             # nothing usable until finalize has succeeded
+            ctx = ctypes.c_void_p()
+            _lib.check(L.hd_lpips_create(ctypes.byref(ctx), self._device.index))
+            self._ctx = ctx
+        with torch.cuda.device(self._device):
+            _lib.check(L.hd_load_weights(self._ctx, descs, len(self._state)), self._ctx)
+            _lib.check(L.hd_finalize_weights(self._ctx), self._ctx)
+        self._loaded = True
+
+    def __call__(self, images, ref, normalize=True, input_normalize=None, per_layer=False):
+        """hd_lpips on the current stream of images' device: images [B,3,R,R] against ref [B,3,Rb,Rb] at ref's size (R, Rb multiples of
+        64 in [64, 512]).  normalize: the inputs are in [0, 1].  input_normalize: None, "face" or "batch" min-max normalisation first
+        (hd_image_range; the normalised tensors are not materialised).  Returns float64 [B], or ([B], [B,5]) with per_layer.  The
+        inputs are only read; nothing synchronises."""
+        if input_normalize not in NORMALIZE:
+            raise ValueError("input_normalize must be None, 'face' or 'batch', got %r" % (input_normalize,))
+        _check_images("images", images)
+        _check_images("ref", ref)
+        if images.shape[0] != ref.shape[0]:
+            raise ValueError("images and ref must hold the same number of faces, got %d and %d" % (images.shape[0], ref.shape[0]))
+        _check_device(images)
+        self._ensure(images.device)
+        if not self._loaded:
+            raise RuntimeError("weights are not loaded: call load_state_dict(...) first")
+        dev = self._device
+        a = images.to(dtype=torch.float32).contiguous()
+        b = ref.to(device=dev, dtype=torch.float32).contiguous()
+        B, R, Rb = int(a.shape[0]), int(a.shape[2]), int(b.shape[2])
+        out = torch.empty((B,), dtype=torch.float64, device=dev)
+        layers = torch.empty((B, 5), dtype=torch.float64, device=dev) if per_layer else None
+        if B:
+            with torch.cuda.device(dev):
+                ra = rb = None
+                if input_normalize is not None:
+                    ra, rb = _range(a, Rb), _range(b, Rb)
+                    if input_normalize == "batch":
+                        ra, rb = _batch_range(ra), _batch_range(rb)
+                _lib.check(_lib.lib().hd_lpips(self._ctx, B, a.data_ptr(), R, b.data_ptr(), Rb, 1 if normalize else 0,
+                                               ra.data_ptr() if ra is not None else None, rb.data_ptr() if rb is not None else None,
+                                               out.data_ptr(), layers.data_ptr() if layers is not None else None,
+                                               torch.cuda.current_stream(dev).cuda_stream), self._ctx)
+            self._keep = (a, b, ra, rb, out, layers)         # the launch program holds these pointers until the next call
+        return (out, layers) if per_layer else out
+
+    def __del__(self):
+        try:
+            if self._ctx is not None:
+                _lib.lib().hd_destroy(self._ctx)
+        except Exception:
+            pass

@@ -12,6 +12,7 @@ beta/gamma, conditional_naf.py:100-101, which would turn every NAF block into th
   LayerNorm2d weight / bias : 1 + 0.1 n / 0.1 n
   beta, gamma               : 0.2 n
   BatchNorm weight / bias   : 1 + 0.1 n / 0.1 n ; running_mean 0.1 n ; running_var U(0.75, 1.25)
+  LPIPS lin weight          : U(0, 4/C): non-negative, as the published ones are
 where n is a unit-variance sum of twelve 16-bit uniforms (Irwin-Hall, exact in float32).
 """
 import numpy as np
@@ -81,6 +82,8 @@ def make_tensor(name: str, shape, kind: str, fan_in: int, seed: int = WEIGHT_SEE
         v = np.float32(0.2) * normalish(key, n)
     elif kind == "bn_var":
         v = np.float32(0.75) + np.float32(0.5) * uniform(key, n)
+    elif kind == "lpips_lin":                                   # non-negative, U[0, 4 / C): a layer's weights sum to about 2
+        v = uniform(key, n) * np.float32(4.0 / fan_in)
     elif kind == "bn_count":
         return np.zeros((), dtype=np.int64)
     else:
@@ -134,6 +137,12 @@ def cr_state_dict(seed: int = WEIGHT_SEED, wild: bool = False):
 def vae_state_dict(seed: int = WEIGHT_SEED):
     """Synthetic AutoencoderKL weights (arch.vae_manifest: 83.7 M parameters; the SD-2.1 checkpoint is not reachable offline)."""
     return make_state_dict(arch.vae_manifest(), seed)
+
+
+def lpips_state_dict(seed: int = WEIGHT_SEED):
+    """Synthetic LPIPS-AlexNet weights (arch.lpips_manifest; the published checkpoints are not reachable offline).  Scores made with
+    them are not comparable to published LPIPS."""
+    return make_state_dict(arch.lpips_manifest(), seed)
 
 
 # ---------------------------------------------------------------- synthetic inputs

@@ -301,7 +301,7 @@ int hd_color_fix(const float* images, float* out, int batch, int res, const floa
 
 /* Per-face PSNR and SSIM of images against a reference: what the reference's evaluation loop does with its result (test_refiner.py:113-122:
  * F.interpolate to the target's size, min-max normalise, pyiqa's psnr and ssim).  pyiqa is third party and absent, so parity with its
- * defaults is unpinned, like the schedulers'; the formulas below are the contract.  LPIPS and NIQE need learned weights and are not offered.
+ * defaults is unpinned, like the schedulers'; the formulas below are the contract.  LPIPS is hd_lpips (below); NIQE needs a fitted model file and is not offered.
  * images [B,3,res,res], ref [B,3,ref_res,ref_res] (device fp32 NCHW; res and ref_res multiples of 64 in [64, 512]).  Everything is scored
  * at the reference's side Rb = ref_res.  Per face:
  *   1. a = F.interpolate(images, Rb, mode = "bicubic", align_corners = False) when res != ref_res (no antialiasing, taps clamped to the
@@ -337,6 +337,52 @@ int64_t hd_image_metrics_workspace(int batch, int ref_res, int channels);
 int hd_image_metrics(const float* images, int res, const float* ref, int ref_res, int batch, int channels, float data_range,
                      const float* images_range, const float* ref_range, double* out, float* ssim_map_out, void* workspace,
                      int64_t workspace_bytes, void* stream);
+
+/* Per-face LPIPS (Zhang et al. 2018; AlexNet, v0.1 "lin" weights) of images against a reference: the third score of the reference's
+ * evaluation loop (test_refiner.py:107-123, pyiqa.create_metric("lpips")).  The `lpips` package and pyiqa are third party and absent, so
+ * parity with them is unpinned, like the schedulers' and the VAE's; the formula below, stated from the paper and from memory of the package,
+ * is the contract.  hd_lpips_create makes a context of its own kind, with the life of the others: hd_load_weights, hd_finalize_weights
+ * (strict), hd_destroy.  Its manifest, in the package's full-model names:
+ *   net.slice1.0 [64,3,11,11], net.slice2.3 [192,64,5,5], net.slice3.6 [384,192,3,3], net.slice4.8 [256,384,3,3], net.slice5.10 [256,256,3,3]
+ *   (.weight and .bias [Cout] each);  lin{0..4}.model.1.weight [1,C,1,1], C = 64, 192, 384, 256, 256;  optionally, both or neither,
+ *   scaling_layer.shift and scaling_layer.scale [1,3,1,1].
+ * images [B,3,res,res], ref [B,3,ref_res,ref_res] (device fp32 NCHW; res and ref_res multiples of 64 in [64, 512]).  Everything is scored
+ * at Rb = ref_res.  Per face:
+ *   1. a = F.interpolate(images, Rb, mode = "bicubic", align_corners = False) when res != ref_res (step 1 of hd_image_metrics: the same
+ *      sampling rule), else images; b = ref.
+ *   2. with images_range / ref_range [B,2] (device fp32: lo, hi per face; hd_image_range makes them): x <- (x - lo) / (hi - lo), 0 where
+ *      hi <= lo: step 2 of hd_image_metrics.  NULL: no normalisation of that tensor.
+ *   3. unit_range = 1: x <- 2x - 1 (the package's normalize=True, pyiqa's default: inputs in [0, 1]).  0: the input is taken as in [-1, 1].
+ *   4. the scaling layer: x <- (x - shift_c) / scale_c, shift = (-.030, -.088, -.188), scale = (.458, .448, .450) unless the state dict
+ *      carries its own.
+ *   5. features, with tap sides s1 = (Rb - 7) / 4 + 1, s2 = (s1 - 3) / 2 + 1, s3 = (s2 - 3) / 2 + 1 (integer division; 64: 15 / 7 / 3):
+ *        f1 = relu(conv(x; 3 -> 64, 11 x 11, stride 4, pad 2))            [64, s1, s1]
+ *        f2 = relu(conv(maxpool(f1); 64 -> 192, 5 x 5, pad 2))            [192, s2, s2]
+ *        f3 = relu(conv(maxpool(f2); 192 -> 384, 3 x 3, pad 1))           [384, s3, s3]
+ *        f4 = relu(conv(f3; 384 -> 256, 3 x 3, pad 1)),  f5 = relu(conv(f4; 256 -> 256, 3 x 3, pad 1))
+ *      maxpool = MaxPool2d(3, stride 2) without padding.
+ *   6. per layer k and position p:  n(f) = f / (sqrt(sum_c f_c^2) + 1e-10),   d_k = mean_p sum_c w_kc (n(fa)_c - n(fb)_c)^2, w_k = lin{k}.
+ *   7. lpips = d_1 + ... + d_5.
+ * out [B] (device fp64): lpips.  layers_out: NULL, or device fp64 [B,5] that receives the d_k.
+ * What is rounded to bf16 (round to nearest even): the convolution weights, the prepared input of step 4 and every stored activation
+ * (each f_k after its ReLU, each max-pool output).  Biases, the lin weights and the scaling constants are fp32; the convolutions
+ * accumulate in fp32; steps 1 - 4 and step 6 are fp32 arithmetic on those values; the sums over the positions of a layer and over the
+ * layers are fp64.
+ * The two images of a pair run through the same launches as faces f and B + f of one batch of 2B (input preparation, five convolutions
+ * of the shared GEMM family, two max-pools), then one launch computes the per-workgroup fp64 partial sums of step 6 for all five layers
+ * and a second, tiny one adds them in index order.  No atomics: equal inputs score exactly 0, swapping images and ref (same size, no
+ * normalisation) keeps the bits, and a face has the same bits from call to call and at every slot of a batch of the same size (another
+ * batch size may choose another GEMM tile).  The context owns its workspace per (batch, ref_res) and its launch program, rebuilt when a
+ * pointer or flag changes; hd_num_ops / hd_debug_op_name / hd_debug_limit_ops / hd_debug_read_op (program 0) see it (the fp64 outputs of
+ * the last two launches are read back as their 32-bit words).  The call enqueues on `stream`, only reads its inputs and does not
+ * synchronise; the pointers must stay valid until that work is done.
+ * HD_ERR_INVALID (HD_ERR_NOT_READY for weights that are not finalized), naming the argument and before any HIP call, for: a context of
+ * another kind; batch outside [1, 1024]; res or ref_res not a multiple of 64 in [64, 512]; unit_range other than 0 or 1; a NULL images,
+ * ref or out; images, ref, images_range or ref_range not aligned to 4 bytes, out or layers_out not to 8; out or layers_out overlapping an
+ * input or each other, as byte ranges. */
+int hd_lpips_create(hd_ctx** out, int device);
+int hd_lpips(hd_ctx* ctx, int batch, const float* images, int res, const float* ref, int ref_res, int unit_range,
+             const float* images_range, const float* ref_range, double* out, double* layers_out, void* stream);
 
 /* Progress previews: the denoised estimate of the row a face last ran, as an output of the sampling loop (diffusers'
  * `pred_original_sample` / `callback_on_step_end`).

@@ -73,7 +73,7 @@ def run(case):
     kw = dict(channels=case.channels, data_range=case.L, normalize=case.normalize, ssim_map=True)
     a, b = img.cuda(), ref.cuda()
     got = metrics.image_metrics(a, b, **kw)
-    got = metrics.Metrics(*(t.cpu() for t in got))
+    got = metrics.Metrics(*(None if t is None else t.cpu() for t in got))
     same = torch.equal(a.cpu(), img) and torch.equal(b.cpu(), ref)
     return Run(case, img, ref, got, metrics.image_metrics_reference(img.double(), ref.double(), **kw),
                metrics.image_metrics_reference(img, ref, **kw), same)
