@@ -22,6 +22,11 @@
                                                           # cr_face, and of every preview against the final image (hd_image_metrics)
     python examples/pipeline.py --metrics --lpips-weights alexnet.pth,lin.pth    # also LPIPS (hd_lpips) with a local AlexNet file and the lin
                                                           # layers' file; --lpips-synthetic: synthetic weights, to see the call run
+    python examples/pipeline.py --from-photos 8 [--feather 8]     # photo in, photo out: head boxes of synthetic photos become ln_face
+                                                          # (photo.ingest: Pillow's crop -> 32 -> 128 bicubic, on the GPU), the restored faces
+                                                          # are pasted back into the photos (photo.paste)
+    python examples/pipeline.py --photo group.jpg --box 410,120,380,400 [--box ...] [--save out.png]    # the same for a real file (PIL reads
+                                                          # and writes the file; the resampling runs on the GPU)
 """
 import argparse
 import os
@@ -33,7 +38,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from hifidiff_amd import color, metrics, sampling, schedulers, synth               # noqa: E402
+from hifidiff_amd import color, metrics, photo, sampling, schedulers, synth        # noqa: E402
 from hifidiff_amd.cr import CoarseRestoration                            # noqa: E402
 from hifidiff_amd.refiner import FacialRefiner                           # noqa: E402
 from hifidiff_amd.vae import AutoencoderKL                               # noqa: E402
@@ -77,6 +82,47 @@ def lpips_model(a, dev):
     return m.to(dev)
 
 
+def load_photos(a, dev):
+    """--from-photos N: ceil(N / 4) synthetic 720 x 540 photos with four head boxes each; --photo FILE --box l,t,w,h: a real file.
+    Returns uint8 photos [n,H,W,3] on the GPU and the host's boxes [B,4] and photo indices [B]."""
+    if a.photo is not None:
+        from PIL import Image                                          # file I/O only
+        img = torch.from_numpy(np.asarray(Image.open(a.photo).convert("RGB")).copy())[None]
+        boxes = np.asarray([[int(v) for v in b.split(",")] for b in a.box], dtype=np.int32)
+        return img.to(dev), boxes, np.zeros(len(boxes), dtype=np.int32)
+    n = (a.from_photos + 3) // 4
+    img = torch.from_numpy(np.stack([synth.photo(f"photo/{k}", 540, 720) for k in range(n)]))
+    g = torch.Generator().manual_seed(11)
+    boxes = []
+    for f in range(a.from_photos):                                     # one box per 360 x 270 quarter: no two overlap
+        w, h = (int(v) for v in torch.randint(150, 251, (2,), generator=g))
+        cx, cy = (f % 2) * 360, (f // 2 % 2) * 270
+        boxes.append((cx + int(torch.randint(0, 360 - w + 1, (1,), generator=g)), cy + int(torch.randint(0, 270 - h + 1, (1,), generator=g)), w, h))
+    return img.to(dev), np.asarray(boxes, dtype=np.int32), np.arange(a.from_photos, dtype=np.int32) // 4
+
+
+def paste_back(a, photos, boxes, pidx, ln_face, images):
+    """The restored faces go back into the photos (photo.paste: quantise, Pillow's bicubic to the box, feathered blend).  Prints that no
+    byte outside the boxes moved and the PSNR inside the boxes against the original photo, for the degraded input and for the result."""
+    inside = torch.zeros(photos.shape[:3], dtype=torch.bool, device=photos.device)
+    for (l, t, w, h), p in zip(boxes.tolist(), pidx.tolist()):
+        inside[p, t:t + h, l:l + w] = True
+    before = photo.paste(photos, ln_face, boxes, pidx, feather=a.feather)
+    after = photo.paste(photos, (images.clamp(-1, 1) + 1) / 2, boxes, pidx, feather=a.feather)
+
+    def psnr(x):
+        mse = float(((x[inside].float() - photos[inside].float()) ** 2).mean())
+        return 10 * np.log10(255.0 ** 2 / max(mse, 1e-12))
+    moved = int((after[~inside] != photos[~inside]).sum())
+    print(f"paste-back of {len(boxes)} faces into {photos.shape[0]} photos of {photos.shape[2]} x {photos.shape[1]}, feather {a.feather}: "
+          f"{moved} bytes outside the boxes changed; PSNR inside the boxes against the photo: {psnr(before):.2f} dB with the degraded "
+          f"input pasted, {psnr(after):.2f} dB with the result" + (" (synthetic weights: the result is not a face)" if a.photo is None else ""))
+    if a.save is not None:
+        from PIL import Image
+        Image.fromarray(after[0].cpu().numpy()).save(a.save)
+        print(f"wrote {a.save}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
@@ -117,7 +163,18 @@ def main():
                     help="--metrics: also LPIPS-AlexNet, with a torchvision AlexNet state dict A and the lin layers' state dict B (local files)")
     ap.add_argument("--lpips-synthetic", action="store_true",
                     help="--metrics: also LPIPS with synthetic weights (the number is not comparable to published LPIPS)")
+    ap.add_argument("--from-photos", type=int, default=None, metavar="N",
+                    help="photo in, photo out: N head boxes of synthetic photos are ingested as ln_face (photo.ingest), run through the "
+                         "pipeline and pasted back (photo.paste); replaces --batch")
+    ap.add_argument("--photo", default=None, metavar="FILE", help="as --from-photos for an image file (needs PIL for the file I/O) and --box")
+    ap.add_argument("--box", action="append", default=None, metavar="l,t,w,h", help="--photo: a head box (repeatable; boxes must not overlap)")
+    ap.add_argument("--feather", type=int, default=8, metavar="PX", help="--from-photos / --photo: width of the blended edge of the paste, 0..256")
+    ap.add_argument("--save", default=None, metavar="FILE", help="--from-photos / --photo: write the first photo with the faces pasted back (needs PIL)")
     a = ap.parse_args()
+    if a.photo is not None and not a.box:
+        ap.error("--photo needs at least one --box l,t,w,h")
+    if (a.photo is not None or a.from_photos is not None) and a.stream is not None:
+        ap.error("--from-photos / --photo run the batch pipeline, not --stream")
     if (a.lpips_weights is not None or a.lpips_synthetic) and not a.metrics:
         ap.error("--lpips-weights / --lpips-synthetic need --metrics")
     if a.lpips_weights is not None and len(a.lpips_weights.split(",")) != 2:
@@ -163,7 +220,13 @@ def main():
         return stream(a, cr, vae, model, sch, steps, dev)
 
     B = a.batch
-    ln_face = torch.from_numpy(np.stack([synth.rand(f"ln_face/{f}", (3, 128, 128)) for f in range(B)])).to(dev)
+    photos = None
+    if a.from_photos is not None or a.photo is not None:               # ln_face as every dataset class of the reference builds it, on the GPU
+        photos, boxes, pidx = load_photos(a, dev)
+        B = len(boxes)
+        ln_face = photo.ingest(photos, boxes, pidx, lr=32, res=128)
+    else:
+        ln_face = torch.from_numpy(np.stack([synth.rand(f"ln_face/{f}", (3, 128, 128)) for f in range(B)])).to(dev)
     latent = torch.randn(B, 4, 16, 16, device=dev)
 
     torch.cuda.synchronize(); t0 = time.time()
@@ -201,6 +264,8 @@ def main():
                   f"{float((img - images[ran]).abs().mean()):.4f}" + (f", {scores(img, images[ran], a.lpips)}" if a.metrics else ""))
     if a.metrics:
         print(f"final images against cr_face: {scores(images, cr_face, a.lpips)}")
+    if photos is not None:
+        paste_back(a, photos, boxes, pidx, ln_face, images)
     print(f"batch {B}: coarse restoration {1e3 * (t1 - t0):.1f} ms, VAE encode {1e3 * (t2 - t1):.1f} ms, {steps}-step {a.scheduler} "
           f"{1e3 * (t3 - t2):.1f} ms, VAE decode {1e3 * (t4 - t3):.1f} ms; latent range [{float(out.min()):.2f}, {float(out.max()):.2f}], "
           f"images {tuple(images.shape)} finite {bool(torch.isfinite(images).all())}")

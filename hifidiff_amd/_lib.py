@@ -17,8 +17,8 @@ import torch  # noqa: F401  (load order matters, see above)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhifidiff_hip.so")
 # translation units (compiled in parallel, one hipcc each) and the headers they include
-UNITS = [os.path.join(_HERE, "csrc", f) for f in ("hd_lib.hip", "hd_aux.hip", "hd_stages.hip", "hd_stages_rows.hip", "hd_strip.hip", "hd_dispatch_ln.hip", "hd_dispatch_lnface.hip", "hd_dispatch_bf16.hip", "hd_dispatch_misc.hip", "hd_lpips.hip")]
-SOURCES = UNITS + [os.path.join(_HERE, "csrc", f) for f in ("hd_gemm.hpp", "hd_dispatch.hpp", "hd_kernels.hpp", "hd_chain.hpp", "hd_conv.hpp", "hd_cr.hpp", "hd_vae.hpp", "hd_internal.hpp", "hd_faceset.hpp", "hd_stage_api.hpp", "hd_xcd.hpp", "hd_xcd2.hpp", "hd_face.hpp", "hd_strip.hpp", "hd_wide.hpp", "hd_end.hpp", "hd_color.hpp", "hd_metrics.hpp", "hd_lpips.hpp")]
+UNITS = [os.path.join(_HERE, "csrc", f) for f in ("hd_lib.hip", "hd_aux.hip", "hd_stages.hip", "hd_stages_rows.hip", "hd_strip.hip", "hd_dispatch_ln.hip", "hd_dispatch_lnface.hip", "hd_dispatch_bf16.hip", "hd_dispatch_misc.hip", "hd_lpips.hip", "hd_photo.hip")]
+SOURCES = UNITS + [os.path.join(_HERE, "csrc", f) for f in ("hd_gemm.hpp", "hd_dispatch.hpp", "hd_kernels.hpp", "hd_chain.hpp", "hd_conv.hpp", "hd_cr.hpp", "hd_vae.hpp", "hd_internal.hpp", "hd_faceset.hpp", "hd_stage_api.hpp", "hd_xcd.hpp", "hd_xcd2.hpp", "hd_face.hpp", "hd_strip.hpp", "hd_wide.hpp", "hd_end.hpp", "hd_color.hpp", "hd_metrics.hpp", "hd_lpips.hpp", "hd_photo.hpp")]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "hifidiff_hip.h")
 
 
@@ -40,7 +40,7 @@ EXPORTS = [
     "hd_create", "hd_create_unconditional", "hd_prepare_unconditional", "hd_cr_create", "hd_cr_forward", "hd_vae_create", "hd_vae_encode", "hd_vae_decode", "hd_destroy", "hd_last_error", "hd_load_weights", "hd_finalize_weights", "hd_prepare",
     "hd_prepare_from_priors", "hd_fpg", "hd_idc", "hd_eps", "hd_sample", "hd_sample_multistep", "hd_sample_rows", "hd_sample_rows_multistep", "hd_prepare_slots",
     "hd_pool_config", "hd_pool_prepare", "hd_pool_commit",
-    "hd_sample_faces", "hd_sample_faces_multistep", "hd_sample_spans", "hd_mask_faces", "hd_guide_config", "hd_guide_faces", "hd_color_fix", "hd_image_range", "hd_image_metrics", "hd_image_metrics_workspace", "hd_lpips_create", "hd_lpips", "hd_preview_config", "hd_preview_read", "hd_scheduler_step",
+    "hd_sample_faces", "hd_sample_faces_multistep", "hd_sample_spans", "hd_mask_faces", "hd_guide_config", "hd_guide_faces", "hd_color_fix", "hd_image_range", "hd_image_metrics", "hd_image_metrics_workspace", "hd_lpips_create", "hd_lpips", "hd_face_ingest", "hd_face_ingest_workspace", "hd_face_paste", "hd_face_paste_workspace", "hd_preview_config", "hd_preview_read", "hd_scheduler_step",
     "hd_scheduler_step_multistep", "hd_num_ops", "hd_num_chains",
     "hd_debug_limit_ops", "hd_debug_op_name", "hd_debug_op_info", "hd_debug_read_op", "hd_debug_read", "hd_debug_write", "hd_debug_gemm", "hd_set_option", "hd_get_option", "hd_check",
     "hd_set_profiling", "hd_get_profile",
@@ -158,6 +158,10 @@ def lib():
     L.hd_image_metrics_workspace.argtypes = [i32, i32, i32]; L.hd_image_metrics_workspace.restype = i64
     L.hd_lpips_create.argtypes = [ctypes.POINTER(vp), i32]
     L.hd_lpips.argtypes = [vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.hd_face_ingest_workspace.argtypes = [i32, i32, i32]; L.hd_face_ingest_workspace.restype = i64
+    L.hd_face_ingest.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp]
+    L.hd_face_paste_workspace.argtypes = [i32, i32]; L.hd_face_paste_workspace.restype = i64
+    L.hd_face_paste.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, vp, i64, vp]
     L.hd_preview_config.argtypes = [vp, i32, i32, i32]
     L.hd_preview_read.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_int32), i32, vp, vp, vp]
     L.hd_scheduler_step_multistep.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_float), vp, vp, u64, i32, i64, vp]

@@ -156,6 +156,18 @@ def rand(tag: str, shape, seed: int = INPUT_SEED):
     return uniform(fnv1a64(tag) ^ seed, n).reshape(shape)
 
 
+def photo(tag: str, height: int, width: int, seed: int = INPUT_SEED):
+    """uint8 [height, width, 3] stand-in for a photograph: a bilinear blow-up of a coarse random field plus +-8 levels of noise."""
+    coarse = rand(tag + ".coarse", (height // 16 + 2, width // 16 + 2, 3), seed).astype(np.float64)
+    y, x = np.arange(height) / 16.0, np.arange(width) / 16.0
+    y0, x0 = y.astype(int), x.astype(int)
+    fy, fx = (y - y0)[:, None, None], (x - x0)[None, :, None]
+    smooth = (coarse[y0][:, x0] * (1 - fy) * (1 - fx) + coarse[y0][:, x0 + 1] * (1 - fy) * fx
+              + coarse[y0 + 1][:, x0] * fy * (1 - fx) + coarse[y0 + 1][:, x0 + 1] * fy * fx)
+    noise = rand(tag + ".noise", (height, width, 3), seed).astype(np.float64) - 0.5
+    return np.clip(np.floor(smooth * 255 + noise * 16 + 0.5), 0, 255).astype(np.uint8)
+
+
 def sample_inputs(batch: int, latent_res: int = 16, seed: int = INPUT_SEED, as_torch=True):
     """x_T ~ N(0,1), cr_latent ~ 0.8 N(0,1), cr_face ~ U[0,1]  (SURVEY §8d).
 

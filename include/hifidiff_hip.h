@@ -384,6 +384,54 @@ int hd_lpips_create(hd_ctx** out, int device);
 int hd_lpips(hd_ctx* ctx, int batch, const float* images, int res, const float* ref, int ref_res, int unit_range,
              const float* images_range, const float* ref_range, double* out, double* layers_out, void* stream);
 
+/* Photo in, photo out: head boxes of uint8 photos become the reference's network input, and restored faces go back into the photos.
+ * Every dataset class of the reference builds ln_face as  crop -> resize((32, 32), BICUBIC) -> resize((128, 128), BICUBIC) -> to_tensor
+ * and the ground truth as  crop -> resize((128, 128), BICUBIC) -> to_tensor  (dataset_kface.py:86-98, infer_cr.py:53).  Both, and the
+ * way back, are Pillow's 8-bit two-pass antialiased bicubic resize, which is integer arithmetic on float64 coefficients: results equal
+ * Pillow's byte for byte (tests/golden/photo_pil.npz holds Pillow's own).  The rule, for one axis with `in` input and `out` output
+ * samples, a = -0.5:
+ *     scale = in / out (double);  fs = max(scale, 1);  support = 2 * fs;  ss = 1.0 / fs
+ *     for xx in 0..out-1:
+ *         center = (xx + 0.5) * scale
+ *         xmin = max((int)(center - support + 0.5), 0);  xmax = min((int)(center + support + 0.5), in)        (int) truncates
+ *         k[x] = bicubic((x + xmin - center + 0.5) * ss)   for x in 0..xmax-xmin-1;   k[x] /= sum_x k[x] (added in index order)
+ *         K[x] = (int)(k[x] * 2^22 + (k[x] < 0 ? -0.5 : 0.5))
+ *         dst[xx] = clip8((sum_x src[xmin + x] * K[x] + 2^21) >> 22)                                          int32 sums
+ *     bicubic(x): x = |x|;  x < 1: ((a + 2) x - (a + 3)) x x + 1;   x < 2: (((x - 5) x + 8) x - 4) a;   else 0
+ *   All of k is float64 and no multiply is fused with an add (one fused multiply-add in bicubic or center moves a K by one).  A resize
+ *   runs the horizontal pass first, into a uint8 intermediate (clipped and rounded), and the vertical pass on that; an axis whose size
+ *   does not change is skipped, so a same-size resize is the identity.  The crop comes first: taps never leave the box.
+ * photos [N,height,width,3] device uint8 (HWC, np.asarray of a PIL image); boxes [batch,4] HOST int32 (left, top, width, height), sides in
+ * [1, 2048], inside the photo; photo_index [batch] HOST int32 in [0, N), or NULL (all 0).  The host arrays are read before the call
+ * returns (they travel as launch arguments, 64 faces a launch).
+ * hd_face_ingest: lr in [8, 64]: crop -> (lr, lr) -> (res, res), ln_face;  lr = 0: crop -> (res, res), the ground truth and what a real
+ *   low-resolution crop needs.  res a multiple of 64 in [64, 512].  out [batch,3,res,res] device fp32 = byte / 255 (a true fp32 division,
+ *   as to_tensor); out_u8: NULL, or device [batch,res,res,3] that receives the bytes.  workspace: device memory of at least
+ *   hd_face_ingest_workspace(batch, lr, res) bytes (the (lr, lr) images; 0 and may be NULL with lr = 0).
+ * hd_face_paste: faces [batch,3,res,res] device fp32; photos is updated in place.  Per face:
+ *     q8 = clamp(floor(x * 255 + 0.5), 0, 255)          fp32, the multiply and the add rounded separately; NaN -> 0 (torchvision save_image)
+ *     q  = resize of q8 to (width, height) of the box by the rule above
+ *     d  = min(x, width - 1 - x, y, height - 1 - y);   m = 256 if feather == 0 else min(256, ((2 d + 1) * 256) / (2 feather))   (integers)
+ *     photo = (photo * (256 - m) + q * m + 128) >> 8
+ *   Bytes outside every box are not written.  Two boxes of one call that share a pixel of one photo are refused (boxes that touch are
+ *   fine), so no result depends on an order.  feather in [0, 256].  workspace: at least hd_face_paste_workspace(batch, res) bytes (q8).
+ * One kernel does every resize: a workgroup owns a band of output rows and columns of one face, computes the K of its rows and columns
+ * in fp64 into LDS, runs the horizontal pass over the source rows the band needs into LDS and the vertical pass from there.  Only integers
+ * depend on the banding: a face's bytes do not depend on its batch position, on the other faces or on the tiling.  Launches per call:
+ * ceil(batch / 64) per resize (ingest: two resizes with lr > 0, else one; paste: one, after one launch that makes q8).
+ * Both calls need no context, allocate nothing and do not synchronise; they enqueue on `stream`; the workspace is the caller's, free to
+ * reuse when the call's work on `stream` is done.  Errors are reported through hd_last_error(NULL).  HD_ERR_INVALID, naming the argument
+ * and before any HIP call, for: a NULL photos, boxes, out, faces or (when its size is not 0) workspace; n_photos < 1; height or width
+ * outside [1, 16384]; batch outside [1, 4096]; a box side outside [1, 2048]; a box outside its photo; a photo_index outside [0, N); lr
+ * other than 0 or [8, 64]; res not a multiple of 64 in [64, 512]; feather outside [0, 256]; overlapping boxes (paste); out or faces not
+ * aligned to 4 bytes; workspace_bytes too small.  The workspace queries return HD_ERR_INVALID for a batch, lr or res the calls refuse. */
+int64_t hd_face_ingest_workspace(int batch, int lr, int res);
+int hd_face_ingest(const uint8_t* photos, int n_photos, int height, int width, const int32_t* boxes, const int32_t* photo_index, int batch,
+                   int lr, int res, float* out, uint8_t* out_u8, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t hd_face_paste_workspace(int batch, int res);
+int hd_face_paste(uint8_t* photos, int n_photos, int height, int width, const float* faces, int res, const int32_t* boxes,
+                  const int32_t* photo_index, int batch, int feather, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Progress previews: the denoised estimate of the row a face last ran, as an output of the sampling loop (diffusers'
  * `pred_original_sample` / `callback_on_step_end`).
  * hd_preview_config(on = 1, every, snapshots): from the next hd_prepare* on -- at once, when a batch is prepared -- the context owns the
