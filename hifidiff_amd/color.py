@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from ._context import check_face_images, require_cuda, stream_ptr
 
 MODES = {"wavelet": 1, "adain": 2}
 MAX_LEVELS = 5
@@ -104,9 +105,8 @@ def color_fix(images, ref, mode="wavelet", levels=MAX_LEVELS, weight=None, ref_v
         _check_levels(levels)
     if not torch.is_tensor(images) or not torch.is_tensor(ref):
         raise ValueError("images and ref must be tensors")
-    for name, t in (("images", images), ("ref", ref)):
-        if t.dim() != 4 or t.shape[1] != 3 or t.shape[2] != t.shape[3] or t.shape[2] % 64 or not 64 <= t.shape[2] <= 512:
-            raise ValueError("%s must be (B,3,R,R) with R a multiple of 64 in [64, 512], got %s" % (name, tuple(t.shape)))
+    check_face_images("images", images)
+    check_face_images("ref", ref)
     if images.shape[0] != ref.shape[0]:
         raise ValueError("images and ref must hold the same number of faces, got %d and %d" % (images.shape[0], ref.shape[0]))
     B = int(images.shape[0])
@@ -119,8 +119,7 @@ def color_fix(images, ref, mode="wavelet", levels=MAX_LEVELS, weight=None, ref_v
             raise ValueError("weight must be a number or one value per face, got shape %s" % (tuple(w.shape),))
         if not bool(((w >= 0) & (w <= 1)).all()):
             raise ValueError("weight must lie in [0, 1]")
-    if images.device.type != "cuda":
-        raise RuntimeError("hifidiff_amd runs on an MI355X (gfx950) GPU only; got device %s (no CPU fallback)" % images.device)
+    require_cuda(images.device)
     dev = images.device
     c = images.to(dtype=torch.float32).contiguous()
     s = ref.to(device=dev, dtype=torch.float32).contiguous()
@@ -131,6 +130,5 @@ def color_fix(images, ref, mode="wavelet", levels=MAX_LEVELS, weight=None, ref_v
         w = w.to(device=dev).contiguous()
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().hd_color_fix(c.data_ptr(), out.data_ptr(), B, int(c.shape[2]), s.data_ptr(), int(s.shape[2]),
-                                           1 if ref_vae_range else 0, MODES[mode], int(levels), w.data_ptr() if w is not None else None,
-                                           torch.cuda.current_stream(dev).cuda_stream))
+                                           1 if ref_vae_range else 0, MODES[mode], int(levels), w.data_ptr() if w is not None else None, stream_ptr(dev)))
     return out

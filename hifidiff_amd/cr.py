@@ -14,18 +14,14 @@ import torch
 from torch import nn
 
 from . import _lib, arch
+from ._context import WeightContext, stream_ptr
 
 
-class CoarseRestoration(nn.Module):
+class CoarseRestoration(WeightContext, nn.Module):
     def __init__(self):
         super().__init__()
-        self._ctx = None
-        self._device = None
-        self._state = None
-        self._loaded = False
         self._batch = None
 
-    # ---- nn.Module plumbing ----
     def load_state_dict(self, state_dict, strict=True):
         man = arch.cr_manifest()
         missing = [k for k in man if k not in state_dict]
@@ -45,55 +41,16 @@ class CoarseRestoration(nn.Module):
     def state_dict(self, *a, **k):
         return dict(self._state or {})
 
-    def to(self, *args, **kwargs):
-        device = kwargs.get("device", args[0] if args else None)
-        if isinstance(device, (str, torch.device, int)):
-            self._ensure(torch.device("cuda", device) if isinstance(device, int) else torch.device(device))
-        return self
+    # ---- library plumbing (_context.WeightContext) ----
+    _manifest = staticmethod(arch.cr_manifest)
 
-    def cuda(self, device=None):
-        return self.to(torch.device("cuda", device if device is not None else torch.cuda.current_device()))
-
-    # ---- library plumbing ----
     def _create(self, idx):
         ctx = ctypes.c_void_p()
         _lib.check(_lib.lib().hd_cr_create(ctypes.byref(ctx), idx))
         return ctx
 
-    def _ensure(self, device):
-        if device.type != "cuda":
-            raise RuntimeError("hifidiff_amd runs on an MI355X (gfx950) GPU only; got device %s (no CPU fallback)" % device)
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        if self._ctx is not None:
-            if idx != self._device.index:
-                raise RuntimeError("this model already lives on cuda:%d" % self._device.index)
-            return
-        self._ctx, self._device = self._create(idx), torch.device("cuda", idx)
-        if self._state is not None:
-            self._upload()
-
-    def _upload(self):
-        man = arch.cr_manifest()
-        if any(k not in self._state for k in man):
-            raise RuntimeError("state dict incomplete: %d of %d tensors loaded" % (len(self._state), len(man)))
-        L = _lib.lib()
-        keep, descs = [], (_lib.TensorDesc * len(man))()
-        for i, k in enumerate(man):
-            t = self._state[k].to(torch.float32).contiguous()
-            keep.append(t)
-            d = descs[i]
-            d.name, d.data, d.ndim, d.is_device = k.encode(), t.data_ptr(), t.dim(), 1 if t.is_cuda else 0
-            for j, s in enumerate(t.shape):
-                d.shape[j] = s
-        if self._loaded:                     # re-load: weights are packed once per context
-            L.hd_destroy(self._ctx)
-            self._ctx = None
-            self._loaded, self._batch = False, None          # nothing usable until finalize has succeeded
-            self._ctx = self._create(self._device.index)
-        with torch.cuda.device(self._device):
-            _lib.check(L.hd_load_weights(self._ctx, descs, len(man)), self._ctx)
-            _lib.check(L.hd_finalize_weights(self._ctx), self._ctx)
-        self._loaded, self._batch = True, None
+    def _reset(self):
+        self._batch = None
 
     def forward(self, x):
         self._ensure(x.device)
@@ -109,13 +66,6 @@ class CoarseRestoration(nn.Module):
         out = torch.empty_like(xin)
         with torch.cuda.device(self._device):
             _lib.check(_lib.lib().hd_cr_forward(self._ctx, B, xin.data_ptr(), out.data_ptr(),
-                                                torch.cuda.current_stream(self._device).cuda_stream), self._ctx)
+                                                stream_ptr(self._device)), self._ctx)
         self._keep = (xin, out)              # the launch program holds these pointers until the next call
         return out
-
-    def __del__(self):
-        try:
-            if self._ctx is not None:
-                _lib.lib().hd_destroy(self._ctx)
-        except Exception:
-            pass

@@ -2,40 +2,14 @@
 // diffusers AutoencoderKL, test_refiner.py:78-83,93) on the refiner path's kernels: weight ingest, workspaces, launch programs
 // and their C-ABI entry points.  Internals: hd_internal.hpp.
 #include "hd_internal.hpp"
-#include "hd_color.hpp"
-#include "hd_metrics.hpp"
-
-void set_contextless_error(const std::string& msg);               // hd_lib.hip: the message hd_last_error(NULL) returns
+#include "hd_args.hpp"
 
 // =============================================================================== CoarseRestoration (§8 f1)
 // models/cr/model.py:73-88: intro -> 4 x [NAF blocks, STN, down] (stage outputs are the skips) -> [8 NAF, STN]
 // -> 4 x [(+ skip), NAF blocks, STN, up] -> outro.  Stage s works on level buffers of its own geometry
 // (C = 32 << level, side 128 >> level); NAF blocks, down- and up-convs are the refiner path's launches.
-static int load_naf_block(hd_ctx* c, const std::string& p, int C, BlockW& bw) {
-    bw.name = p; bw.C = C;
-    int r = 0;
-    r |= pack_weight(c, p + ".conv1", &bw.conv1); r |= pack_weight(c, p + ".conv3", &bw.conv3);
-    r |= pack_weight(c, p + ".sca.1", &bw.sca); r |= pack_weight(c, p + ".conv4", &bw.conv4);
-    r |= pack_weight(c, p + ".conv5", &bw.conv5);
-    if (r) return r;
-    bw.dw_w = find_raw(c, p + ".conv2.weight")->dev; bw.dw_b = find_raw(c, p + ".conv2.bias")->dev;
-    bw.beta = find_raw(c, p + ".beta")->dev; bw.gamma = find_raw(c, p + ".gamma")->dev;
-    return make_dw_layout(c, bw);
-}
-
 int finalize_cr(hd_ctx* c) {
-    const auto man = build_cr_manifest();
-    for (const auto& e : man) {
-        const RawTensor* r = find_raw(c, e.first);
-        if (!r) HD_FAIL(c, HD_ERR_WEIGHTS, "Missing key in state_dict: %s", e.first.c_str());
-        if (r->shape != e.second) HD_FAIL(c, HD_ERR_WEIGHTS, "size mismatch for %s", e.first.c_str());
-    }
-    if (c->raw.size() != man.size()) {
-        std::unordered_map<std::string, int> known;
-        for (const auto& e : man) known[e.first] = 1;
-        for (const auto& kv : c->raw)
-            if (!known.count(kv.first)) HD_FAIL(c, HD_ERR_WEIGHTS, "Unexpected key in state_dict: %s", kv.first.c_str());
-    }
+    if (const int bad = check_manifest(c, build_cr_manifest())) return bad;
     cr_stage_list(c->cr_stages);
     int rc = 0, off = 0;
     for (size_t si = 0; si < c->cr_stages.size(); ++si) {
@@ -140,7 +114,7 @@ static int alloc_cr(hd_ctx* c, int B) {
 
 // in / out: [B,3,128,128] fp32 NCHW device pointers of this call (captured by the first and last op)
 static int build_cr_program(hd_ctx* c, const float* in, float* out) {
-    std::vector<Op>& prog = c->ws->cr_program;
+    std::vector<Op>& prog = c->ws->cr_prog.ops;
     prog.clear();
     Chain& ch = c->ws->chains[0];
     const int B = ch.B;
@@ -200,7 +174,6 @@ static int build_cr_program(hd_ctx* c, const float* in, float* out) {
                         }});
         prog.back().out = out; prog.back().out_elems = M * 3;
     }
-    c->ws->cr_in = in; c->ws->cr_out = out;
     return HD_OK;
 }
 
@@ -241,18 +214,7 @@ std::vector<std::pair<std::string, Shape>> build_vae_manifest() {
 }
 
 int finalize_vae(hd_ctx* c) {
-    const auto man = build_vae_manifest();
-    for (const auto& e : man) {
-        const RawTensor* r = find_raw(c, e.first);
-        if (!r) HD_FAIL(c, HD_ERR_WEIGHTS, "Missing key in state_dict: %s", e.first.c_str());
-        if (r->shape != e.second) HD_FAIL(c, HD_ERR_WEIGHTS, "size mismatch for %s", e.first.c_str());
-    }
-    if (c->raw.size() != man.size()) {
-        std::unordered_map<std::string, int> known;
-        for (const auto& e : man) known[e.first] = 1;
-        for (const auto& kv : c->raw)
-            if (!known.count(kv.first)) HD_FAIL(c, HD_ERR_WEIGHTS, "Unexpected key in state_dict: %s", kv.first.c_str());
-    }
+    if (const int bad = check_manifest(c, build_vae_manifest())) return bad;
     auto& w = c->vw;
     int rc = 0;
     auto res = [&](const std::string& p, int cin, int cout, hd_ctx::VaeRes& r) {
@@ -376,7 +338,7 @@ static void vae_attention(hd_ctx* c, std::vector<Op>& prog, const hd_ctx::VaeAtt
 
 static int build_vae_encode(hd_ctx* c, int B, int in_res, int R, const float* images, int vae_range, const float* noise, uint64_t seed,
                             float* moments_out, float* latents_out) {
-    auto& prog = c->ws->vae_enc_prog; prog.clear();
+    auto& prog = c->ws->vae_enc_prog.ops; prog.clear();
     auto& v = c->ws->vws; auto& w = c->vw;
     const float* src = images;
     if (in_res != R) {                                     // F.interpolate(x, R, mode="bicubic", align_corners=False) (test_refiner.py:80)
@@ -426,7 +388,7 @@ static int build_vae_encode(hd_ctx* c, int B, int in_res, int R, const float* im
 }
 
 static int build_vae_decode(hd_ctx* c, int B, int L, const float* latents, float* images_out) {
-    auto& prog = c->ws->vae_dec_prog; prog.clear();
+    auto& prog = c->ws->vae_dec_prog.ops; prog.clear();
     auto& v = c->ws->vws; auto& w = c->vw;
     int H = L;
     {
@@ -485,11 +447,14 @@ int hd_cr_forward(hd_ctx* c, int batch, const float* ln_face, float* cr_face_out
     HIPCHECK(c, hipSetDevice(c->device));
     int rc = alloc_cr(c, batch);
     if (rc) return rc;
-    if (c->ws->cr_program.empty() || c->ws->cr_in != ln_face || c->ws->cr_out != cr_face_out) {
+    CachedProgram& cp = c->ws->cr_prog;
+    const ProgramKey key = {{ln_face, cr_face_out}};
+    if (!cp.matches(key)) {
         rc = build_cr_program(c, ln_face, cr_face_out);
         if (rc) return rc;
+        cp.store(key);
     }
-    return run_ops(c, c->ws->cr_program, reinterpret_cast<hipStream_t>(stream), c->op_limit);
+    return run_ops(c, cp.ops, reinterpret_cast<hipStream_t>(stream), c->op_limit);
 }
 
 // AutoencoderKL boundary.  encode: images [B,3,in_res,in_res] fp32 NCHW -> bicubic to image_res (test_refiner.py:80)
@@ -506,165 +471,36 @@ int hd_vae_encode(hd_ctx* c, int batch, int in_res, int image_res, const float* 
     if (!c) return HD_ERR_INVALID;
     if (!c->vae) HD_FAIL(c, HD_ERR_INVALID, "hd_vae_encode: not an AutoencoderKL context (hd_vae_create)");
     if (!c->finalized) HD_FAIL(c, HD_ERR_NOT_READY, "weights are not loaded/finalized");
-    if (!images || (!moments_out && !latents_out) || batch <= 0 || batch > 1024 || in_res < 8 || image_res < 64 || image_res > 512 || image_res % 64)
+    if (!images || (!moments_out && !latents_out) || batch <= 0 || batch > 1024 || in_res < 8 || !hd_args::res_ok(image_res))
         HD_FAIL(c, HD_ERR_INVALID, "hd_vae_encode: bad arguments (image_res must be a multiple of 64 in [64, 512])");
     HIPCHECK(c, hipSetDevice(c->device));
     int rc = alloc_vae(c, batch, image_res);
     if (rc) return rc;
-    const void* key[4] = {images, noise, moments_out, latents_out};
-    const int flags = in_res * 4 + vae_range * 2;
-    if (c->ws->vae_enc_prog.empty() || memcmp(key, c->ws->vae_enc_key, sizeof(key)) != 0 || flags != c->ws->vae_enc_flags || seed != c->ws->vae_seed) {
+    CachedProgram& cp = c->ws->vae_enc_prog;
+    const ProgramKey key = {{images, noise, moments_out, latents_out}, (uint64_t)(in_res * 4 + vae_range * 2), seed};
+    if (!cp.matches(key)) {
         rc = build_vae_encode(c, batch, in_res, image_res, images, vae_range, noise, seed, moments_out, latents_out);
         if (rc) return rc;
-        memcpy(c->ws->vae_enc_key, key, sizeof(key)); c->ws->vae_enc_flags = flags;
+        cp.store(key);
     }
-    c->ws->vae_seed = seed;
-    return run_ops(c, c->ws->vae_enc_prog, reinterpret_cast<hipStream_t>(stream), c->op_limit);
+    return run_ops(c, cp.ops, reinterpret_cast<hipStream_t>(stream), c->op_limit);
 }
 int hd_vae_decode(hd_ctx* c, int batch, int latent_res, const float* latents, float* images_out, void* stream) {
     if (!c) return HD_ERR_INVALID;
     if (!c->vae) HD_FAIL(c, HD_ERR_INVALID, "hd_vae_decode: not an AutoencoderKL context (hd_vae_create)");
     if (!c->finalized) HD_FAIL(c, HD_ERR_NOT_READY, "weights are not loaded/finalized");
-    if (!latents || !images_out || batch <= 0 || batch > 1024 || latent_res < 8 || latent_res > 64 || latent_res % 8) HD_FAIL(c, HD_ERR_INVALID, "hd_vae_decode: bad arguments");
+    if (!latents || !images_out || batch <= 0 || batch > 1024 || !hd_args::res_ok(8LL * latent_res)) HD_FAIL(c, HD_ERR_INVALID, "hd_vae_decode: bad arguments");
     HIPCHECK(c, hipSetDevice(c->device));
     int rc = alloc_vae(c, batch, latent_res * 8);
     if (rc) return rc;
-    const void* key[2] = {latents, images_out};
-    if (c->ws->vae_dec_prog.empty() || memcmp(key, c->ws->vae_dec_key, sizeof(key)) != 0) {
+    CachedProgram& cp = c->ws->vae_dec_prog;
+    const ProgramKey key = {{latents, images_out}};
+    if (!cp.matches(key)) {
         rc = build_vae_decode(c, batch, latent_res, latents, images_out);
         if (rc) return rc;
-        memcpy(c->ws->vae_dec_key, key, sizeof(key));
+        cp.store(key);
     }
-    return run_ops(c, c->ws->vae_dec_prog, reinterpret_cast<hipStream_t>(stream), c->op_limit);
+    return run_ops(c, cp.ops, reinterpret_cast<hipStream_t>(stream), c->op_limit);
 }
-
-// Colour correction of decoded faces against a reference (hd_color.hpp).  No context: errors go to hd_last_error(NULL), and every
-// argument is checked before the first HIP call.
-#define CF_FAIL(code, ...)                                        \
-    do {                                                          \
-        char _b[256];                                             \
-        snprintf(_b, sizeof(_b), __VA_ARGS__);                    \
-        set_contextless_error(_b);                                \
-        return (code);                                            \
-    } while (0)
-int hd_color_fix(const float* images, float* out, int batch, int res, const float* ref, int ref_res, int ref_vae_range, int mode,
-                 int levels, const float* weight, void* stream) {
-    if (batch < 1) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: batch must be >= 1, got %d", batch);
-    if (res < 64 || res > 512 || res % 64) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: res must be a multiple of 64 in [64, 512], got %d", res);
-    if (ref_res < 64 || ref_res > 512 || ref_res % 64) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: ref_res must be a multiple of 64 in [64, 512], got %d", ref_res);
-    if (mode != 1 && mode != 2) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: mode must be 1 (wavelet) or 2 (AdaIN), got %d", mode);
-    if (mode == 1 && (levels < 1 || levels > CF_MAX_LEVELS)) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: levels must be in [1, %d] in wavelet mode, got %d", CF_MAX_LEVELS, levels);
-    if (ref_vae_range != 0 && ref_vae_range != 1) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: ref_vae_range must be 0 or 1, got %d", ref_vae_range);
-    if (!images) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: images is NULL");
-    if (!out) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: out is NULL");
-    if (!ref) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: ref is NULL");
-    const uintptr_t pi = (uintptr_t)images, po = (uintptr_t)out, pr = (uintptr_t)ref;
-    if ((pi | po | pr | (uintptr_t)weight) % sizeof(float)) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: images, out, ref and weight must be aligned to 4 bytes");
-    if (mode == 2 && (pi | po | pr) % 16) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: images, out and ref must be aligned to 16 bytes in AdaIN mode");
-    const size_t nimg = (size_t)batch * 3 * res * res * sizeof(float), nref = (size_t)batch * 3 * ref_res * ref_res * sizeof(float);
-    if (po < pi + nimg && pi < po + nimg) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: out overlaps images (the tiled kernel reads its neighbours' pixels)");
-    if (po < pr + nref && pr < po + nimg) CF_FAIL(HD_ERR_INVALID, "hd_color_fix: out overlaps ref");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int planes = batch * 3;
-    hipError_t e;
-    if (mode == 1) {
-        const int tiles = res / CF_TILE, halo = (1 << levels) - 1;
-        const int side = CF_TILE + (tiles == 1 ? 0 : tiles == 2 ? halo : 2 * halo);   // the largest staged region of any tile
-        const size_t smem = (size_t)2 * side * side * sizeof(float);
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wavelet_fix_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CF_MAX_SMEM);
-        if (e != hipSuccess) CF_FAIL(HD_ERR_HIP, "hd_color_fix: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-        hipLaunchKernelGGL(wavelet_fix_kernel, dim3(tiles * tiles, planes), dim3(CF_THREADS), smem, s, images, ref, out, weight, res, ref_res, ref_vae_range, levels);
-    } else {
-        hipLaunchKernelGGL(adain_fix_kernel, dim3(planes), dim3(CF_THREADS), 0, s, images, ref, out, weight, res, ref_res, ref_vae_range);
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess) CF_FAIL(HD_ERR_HIP, "hd_color_fix: launch failed: %s", hipGetErrorString(e));
-    return HD_OK;
-}
-// Per-face MSE / SSIM of images against a reference and the per-face value range (hd_metrics.hpp).  No context, as hd_color_fix:
-// errors go to hd_last_error(NULL) and every argument is checked before the first HIP call.
-static bool mt_res_ok(int r) { return r >= 64 && r <= 512 && r % 64 == 0; }
-static bool mt_overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a && b && na && nb && a < b + nb && b < a + na; }
-
-int64_t hd_image_metrics_workspace(int batch, int ref_res, int channels) {
-    if (batch < 1 || batch > 65535) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics_workspace: batch must be in [1, 65535], got %d", batch);
-    if (!mt_res_ok(ref_res)) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics_workspace: ref_res must be a multiple of 64 in [64, 512], got %d", ref_res);
-    if (channels != 1 && channels != 2) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics_workspace: channels must be 1 (rgb) or 2 (y), got %d", channels);
-    const int tiles = ref_res / MT_TILE;
-    return (int64_t)batch * (channels == 1 ? 3 : 1) * tiles * tiles * 2 * (int64_t)sizeof(double);
-}
-
-int hd_image_range(const float* images, int batch, int res, int out_res, float* range_out, void* stream) {
-    if (batch < 1) CF_FAIL(HD_ERR_INVALID, "hd_image_range: batch must be >= 1, got %d", batch);
-    if (!mt_res_ok(res)) CF_FAIL(HD_ERR_INVALID, "hd_image_range: res must be a multiple of 64 in [64, 512], got %d", res);
-    if (!mt_res_ok(out_res)) CF_FAIL(HD_ERR_INVALID, "hd_image_range: out_res must be a multiple of 64 in [64, 512], got %d", out_res);
-    if (!images) CF_FAIL(HD_ERR_INVALID, "hd_image_range: images is NULL");
-    if (!range_out) CF_FAIL(HD_ERR_INVALID, "hd_image_range: range_out is NULL");
-    const uintptr_t pi = (uintptr_t)images, po = (uintptr_t)range_out;
-    if (res == out_res && pi % 16) CF_FAIL(HD_ERR_INVALID, "hd_image_range: images must be aligned to 16 bytes when out_res == res (vector loads)");
-    if (pi % sizeof(float)) CF_FAIL(HD_ERR_INVALID, "hd_image_range: images must be aligned to 4 bytes");
-    if (po % sizeof(float)) CF_FAIL(HD_ERR_INVALID, "hd_image_range: range_out must be aligned to 4 bytes");
-    if (mt_overlap(po, (size_t)batch * 2 * sizeof(float), pi, (size_t)batch * 3 * res * res * sizeof(float)))
-        CF_FAIL(HD_ERR_INVALID, "hd_image_range: range_out overlaps images");
-    hipLaunchKernelGGL(range_kernel, dim3(batch), dim3(MT_RANGE_THREADS), 0, reinterpret_cast<hipStream_t>(stream), images, res, out_res, range_out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) CF_FAIL(HD_ERR_HIP, "hd_image_range: launch failed: %s", hipGetErrorString(e));
-    return HD_OK;
-}
-
-int hd_image_metrics(const float* images, int res, const float* ref, int ref_res, int batch, int channels, float data_range,
-                     const float* images_range, const float* ref_range, double* out, float* ssim_map_out, void* workspace,
-                     int64_t workspace_bytes, void* stream) {
-    if (batch < 1 || batch > 65535) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: batch must be in [1, 65535], got %d", batch);
-    if (!mt_res_ok(res)) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: res must be a multiple of 64 in [64, 512], got %d", res);
-    if (!mt_res_ok(ref_res)) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: ref_res must be a multiple of 64 in [64, 512], got %d", ref_res);
-    if (channels != 1 && channels != 2) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: channels must be 1 (rgb) or 2 (y), got %d", channels);
-    if (!(data_range > 0.f) || !std::isfinite(data_range)) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: data_range must be finite and > 0, got %g", (double)data_range);
-    if (!images) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: images is NULL");
-    if (!ref) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: ref is NULL");
-    if (!out) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: out is NULL");
-    if (!workspace) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: workspace is NULL (hd_image_metrics_workspace gives its size)");
-    const int P = channels == 1 ? 3 : 1, tiles = ref_res / MT_TILE, V = ref_res - (MT_WIN - 1);
-    const int64_t need = (int64_t)batch * P * tiles * tiles * 2 * (int64_t)sizeof(double);
-    if (workspace_bytes < need)
-        CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: workspace_bytes is %lld, this call needs %lld (hd_image_metrics_workspace)", (long long)workspace_bytes, (long long)need);
-    const uintptr_t pi = (uintptr_t)images, pr = (uintptr_t)ref, pir = (uintptr_t)images_range, prr = (uintptr_t)ref_range;
-    const uintptr_t po = (uintptr_t)out, pm = (uintptr_t)ssim_map_out, pw = (uintptr_t)workspace;
-    if ((pi | pr | pir | prr | pm) % sizeof(float))
-        CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: images, ref, images_range, ref_range and ssim_map_out must be aligned to 4 bytes");
-    if ((po | pw) % sizeof(double)) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: out and workspace must be aligned to 8 bytes");
-    const size_t nimg = (size_t)batch * 3 * res * res * sizeof(float), nref = (size_t)batch * 3 * ref_res * ref_res * sizeof(float);
-    const size_t nrange = (size_t)batch * 2 * sizeof(float), nout = (size_t)batch * 2 * sizeof(double);
-    const size_t nmap = (size_t)batch * P * V * V * sizeof(float);
-    const struct { const char* name; uintptr_t p; size_t n; } outs[3] = {{"out", po, nout}, {"ssim_map_out", pm, nmap}, {"workspace", pw, (size_t)need}},
-                                                              ins[4] = {{"images", pi, nimg}, {"ref", pr, nref}, {"images_range", pir, nrange}, {"ref_range", prr, nrange}};
-    for (const auto& o : outs)
-        for (const auto& i : ins)
-            if (mt_overlap(o.p, o.n, i.p, i.n)) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: %s overlaps %s", o.name, i.name);
-    for (int i = 0; i < 3; ++i)
-        for (int j = i + 1; j < 3; ++j)
-            if (mt_overlap(outs[i].p, outs[i].n, outs[j].p, outs[j].n)) CF_FAIL(HD_ERR_INVALID, "hd_image_metrics: %s overlaps %s", outs[i].name, outs[j].name);
-    MtWindow win;
-    {   // g[k] = exp(-(k - 5)^2 / (2 * 1.5^2)), normalised in float64
-        double g[MT_WIN], sum = 0.0;
-        for (int k = 0; k < MT_WIN; ++k) { g[k] = std::exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5)); sum += g[k]; }
-        for (int k = 0; k < MT_WIN; ++k) win.g[k] = (float)(g[k] / sum);
-    }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    double* partial = static_cast<double*>(workspace);
-    const dim3 grid(tiles * tiles, P, batch);
-    if (channels == 1)
-        hipLaunchKernelGGL(metrics_kernel<0>, grid, dim3(MT_THREADS), 0, s, images, res, ref, ref_res, data_range, images_range, ref_range, win, partial, ssim_map_out);
-    else
-        hipLaunchKernelGGL(metrics_kernel<1>, grid, dim3(MT_THREADS), 0, s, images, res, ref, ref_res, data_range, images_range, ref_range, win, partial, ssim_map_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) CF_FAIL(HD_ERR_HIP, "hd_image_metrics: launch failed: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(metrics_combine_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, partial, batch, P * tiles * tiles,
-                       1.0 / ((double)P * ref_res * ref_res), 1.0 / ((double)P * V * V), out);
-    e = hipGetLastError();
-    if (e != hipSuccess) CF_FAIL(HD_ERR_HIP, "hd_image_metrics: launch failed: %s", hipGetErrorString(e));
-    return HD_OK;
-}
-#undef CF_FAIL
 
 }  // extern "C"

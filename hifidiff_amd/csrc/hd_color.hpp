@@ -12,7 +12,7 @@
 // Neither kernel uses global scratch; out must not overlap images or ref (the tiled kernel reads its neighbours' c).
 #pragma once
 #include <hip/hip_runtime.h>
-#include "hd_vae.hpp"
+#include "hd_bicubic.hpp"
 
 namespace hd {
 

@@ -159,6 +159,20 @@ struct LpScale { float shift[3], scale[3]; };          // LPIPS: the scaling lay
 // distance kernel's partial sums, for B faces scored at side R
 struct LpWs { uint4* in8 = nullptr; unsigned short *f[5] = {}, *pool[2] = {}; double* part = nullptr; int B = 0, R = 0; };
 
+// A launch program whose closures captured a call's arguments, with those arguments: it serves a later call only while every
+// pointer, the flag word and the seed are the same.
+struct ProgramKey {
+    const void* ptr[6] = {};
+    uint64_t flags = 0, seed = 0;
+    bool operator==(const ProgramKey& o) const { return memcmp(ptr, o.ptr, sizeof(ptr)) == 0 && flags == o.flags && seed == o.seed; }
+};
+struct CachedProgram {
+    std::vector<Op> ops;
+    ProgramKey key;
+    bool matches(const ProgramKey& k) const { return !ops.empty() && key == k; }
+    void store(const ProgramKey& k) { key = k; }
+};
+
 struct Workspace {
     Workspace() = default;
     Workspace(const Workspace&) = delete;
@@ -181,22 +195,12 @@ struct Workspace {
     unsigned graph_gen = 0;
     const float* graph_film = nullptr;
     int graph_B = 0;
-    // CoarseRestoration: the launch program with the caller's pointers it captured
-    std::vector<Op> cr_program;
-    const float* cr_in = nullptr; float* cr_out = nullptr;
+    // CoarseRestoration, the AutoencoderKL's two directions and LPIPS: each launch program with the caller's arguments it captured
+    CachedProgram cr_prog, vae_enc_prog, vae_dec_prog, lpips_prog;
     float* cr_skip[5] = {};                  // encoder-stage outputs kept for the decoder adds (levels 1..4)
     float *cr_loc1 = nullptr, *cr_loc2 = nullptr, *cr_theta = nullptr;   // STN temporaries
-    // AutoencoderKL: the buffers, and each launch program with what validates it (the caller's pointers, flags and seed it captured)
-    VaeWs vws;
-    std::vector<Op> vae_enc_prog, vae_dec_prog;
-    const void *vae_enc_key[4] = {}, *vae_dec_key[2] = {};
-    int vae_enc_flags = -1;
-    uint64_t vae_seed = 0;
-    // LPIPS: the buffers, and the launch program with the caller's pointers and flags it captured
-    LpWs lws;
-    std::vector<Op> lpips_prog;
-    const void* lpips_key[6] = {};
-    int lpips_flags = -1;
+    VaeWs vws;                               // AutoencoderKL: the buffers
+    LpWs lws;                                // LPIPS: the buffers
 };
 
 // Which evaluation a launch of Chain::program is part of.  Every closure of the program derives what it needs from this one value:
@@ -576,6 +580,21 @@ const RawTensor* find_raw(hd_ctx* c, const std::string& n) {
 // ------------------------------------------------------------------------------ manifest (strict load)
 // Same keys/shapes as FacialRefiner(latent_res).state_dict() — mirrors hifidiff_amd/arch.py.
 using Shape = std::vector<int64_t>;
+// The strict load of every context kind: each manifest entry present with its shape, in manifest order, then no key besides them.
+int check_manifest(hd_ctx* c, const std::vector<std::pair<std::string, Shape>>& man) {
+    for (const auto& e : man) {
+        const RawTensor* r = find_raw(c, e.first);
+        if (!r) HD_FAIL(c, HD_ERR_WEIGHTS, "Missing key in state_dict: %s", e.first.c_str());
+        if (r->shape != e.second) HD_FAIL(c, HD_ERR_WEIGHTS, "size mismatch for %s", e.first.c_str());
+    }
+    if (c->raw.size() != man.size()) {
+        std::unordered_map<std::string, int> known;
+        for (const auto& e : man) known[e.first] = 1;
+        for (const auto& kv : c->raw)
+            if (!known.count(kv.first)) HD_FAIL(c, HD_ERR_WEIGHTS, "Unexpected key in state_dict: %s", kv.first.c_str());
+    }
+    return HD_OK;
+}
 void m_conv(std::vector<std::pair<std::string, Shape>>& m, const std::string& n, int co, int ci, int kh, int kw, bool bias = true) {
     m.push_back({n + ".weight", {co, ci, kh, kw}});
     if (bias) m.push_back({n + ".bias", {co}});
@@ -1133,6 +1152,18 @@ int make_dw_layout(hd_ctx* c, BlockW& bw) {
     return HD_OK;
 }
 
+// One NAF block's weights under the prefix p (the denoiser's, the FPG's and CoarseRestoration's blocks alike)
+int load_naf_block(hd_ctx* c, const std::string& p, int C, BlockW& bw) {
+    bw.name = p; bw.C = C;
+    int r = 0;
+    r |= pack_weight(c, p + ".conv1", &bw.conv1); r |= pack_weight(c, p + ".conv3", &bw.conv3);
+    r |= pack_weight(c, p + ".sca.1", &bw.sca); r |= pack_weight(c, p + ".conv4", &bw.conv4);
+    r |= pack_weight(c, p + ".conv5", &bw.conv5);
+    if (r) return r;
+    bw.dw_w = find_raw(c, p + ".conv2.weight")->dev; bw.dw_b = find_raw(c, p + ".conv2.bias")->dev;
+    bw.beta = find_raw(c, p + ".beta")->dev; bw.gamma = find_raw(c, p + ".gamma")->dev;
+    return make_dw_layout(c, bw);
+}
 
 }  // namespace
 

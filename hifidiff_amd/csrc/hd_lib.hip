@@ -716,32 +716,9 @@ int hd_finalize_weights(hd_ctx* c) {
     if (c->cr) return finalize_cr(c);
     if (c->vae) return finalize_vae(c);
     if (c->lpips) return finalize_lpips(c);
-    // ---- strict key / shape check ----
-    const auto man = build_manifest(c->L, c->conditional);
-    for (const auto& e : man) {
-        const RawTensor* r = find_raw(c, e.first);
-        if (!r) HD_FAIL(c, HD_ERR_WEIGHTS, "Missing key in state_dict: %s", e.first.c_str());
-        if (r->shape != e.second) HD_FAIL(c, HD_ERR_WEIGHTS, "size mismatch for %s", e.first.c_str());
-    }
-    if (c->raw.size() != man.size()) {
-        std::unordered_map<std::string, int> known;
-        for (const auto& e : man) known[e.first] = 1;
-        for (const auto& kv : c->raw)
-            if (!known.count(kv.first)) HD_FAIL(c, HD_ERR_WEIGHTS, "Unexpected key in state_dict: %s", kv.first.c_str());
-    }
+    if (const int bad = check_manifest(c, build_manifest(c->L, c->conditional))) return bad;
     int rc = 0;
     // ---- NAF blocks (denoiser in execution order, then FPG) ----
-    auto load_block = [&](const std::string& p, int C, BlockW& bw) -> int {
-        bw.name = p; bw.C = C;
-        int r = 0;
-        r |= pack_weight(c, p + ".conv1", &bw.conv1); r |= pack_weight(c, p + ".conv3", &bw.conv3);
-        r |= pack_weight(c, p + ".sca.1", &bw.sca); r |= pack_weight(c, p + ".conv4", &bw.conv4);
-        r |= pack_weight(c, p + ".conv5", &bw.conv5);
-        if (r) return r;
-        bw.dw_w = find_raw(c, p + ".conv2.weight")->dev; bw.dw_b = find_raw(c, p + ".conv2.bias")->dev;
-        bw.beta = find_raw(c, p + ".beta")->dev; bw.gamma = find_raw(c, p + ".gamma")->dev;
-        return make_dw_layout(c, bw);
-    };
     const int enc[4] = {2, 2, 4, 8};
     std::vector<std::pair<std::string, int>> order;
     for (int l = 0; l < 4; ++l) for (int j = 0; j < enc[l]; ++j) order.push_back({"denoiser.encoders." + std::to_string(l) + "." + std::to_string(j), WIDTH << l});
@@ -750,7 +727,7 @@ int hd_finalize_weights(hd_ctx* c) {
     int off = 0;
     for (auto& e : order) {
         BlockW bw;
-        rc = load_block(e.first, e.second, bw);
+        rc = load_naf_block(c, e.first, e.second, bw);
         if (rc) return rc;
         bw.film_off = off;
         off += 4 * e.second;
@@ -764,7 +741,7 @@ int hd_finalize_weights(hd_ctx* c) {
     for (int l = 0; l < 4 && c->conditional; ++l)
         for (int j = 0; j < enc[l]; ++j) {
             BlockW bw;
-            rc = load_block("fpg.encoders." + std::to_string(l) + "." + std::to_string(j), WIDTH << l, bw);
+            rc = load_naf_block(c, "fpg.encoders." + std::to_string(l) + "." + std::to_string(j), WIDTH << l, bw);
             if (rc) return rc;
             bw.film_off = off;
             off += 4 * (WIDTH << l);
@@ -1944,9 +1921,9 @@ int hd_preview_read(hd_ctx* c, int n, const int32_t* slots, int snapshot, float*
 
 static std::vector<Op>* which_program(hd_ctx* c, int which) {
     static std::vector<Op> empty;
-    if (c->cr) return &c->ws->cr_program;
-    if (c->vae) return which == 0 ? &c->ws->vae_enc_prog : &c->ws->vae_dec_prog;
-    if (c->lpips) return &c->ws->lpips_prog;
+    if (c->cr) return &c->ws->cr_prog.ops;
+    if (c->vae) return which == 0 ? &c->ws->vae_enc_prog.ops : &c->ws->vae_dec_prog.ops;
+    if (c->lpips) return &c->ws->lpips_prog.ops;
     if (c->ws->chains.empty()) return &empty;
     return which == 0 ? &c->ws->chains[0].program : &c->ws->chains[0].prep_program;
 }

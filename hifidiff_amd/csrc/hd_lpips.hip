@@ -3,7 +3,10 @@
 // include/hifidiff_hip.h; the kernels that are not convolutions are in hd_lpips.hpp.  The `lpips` package and pyiqa are absent: parity
 // with them, and the key names below (from memory of the package's full-model state dict), are unpinned.
 #include "hd_internal.hpp"
+#include "hd_args.hpp"
 #include "hd_lpips.hpp"
+
+using namespace hd_args;
 
 namespace {
 
@@ -71,7 +74,7 @@ void lp_pool(std::vector<Op>& prog, const std::string& name, const unsigned shor
 
 int build_lpips(hd_ctx* c, int B, const float* images, int res, const float* ref, int R, int unit_range, const float* images_range,
                 const float* ref_range, double* out, double* layers_out) {
-    auto& prog = c->ws->lpips_prog; prog.clear();
+    auto& prog = c->ws->lpips_prog.ops; prog.clear();
     auto& v = c->ws->lws; auto& w = c->lw;
     const int N = 2 * B;
     int s[3];
@@ -113,26 +116,13 @@ int build_lpips(hd_ctx* c, int B, const float* images, int res, const float* ref
     return HD_OK;
 }
 
-bool lp_res_ok(int r) { return r >= 64 && r <= 512 && r % 64 == 0; }
-bool lp_overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a && b && na && nb && a < b + nb && b < a + na; }
-
 }  // namespace
 
 int finalize_lpips(hd_ctx* c) {
     auto man = build_lpips_manifest();
     const bool own_scale = find_raw(c, "scaling_layer.shift") || find_raw(c, "scaling_layer.scale");     // optional, but both or neither
     if (own_scale) { man.push_back({"scaling_layer.shift", {1, 3, 1, 1}}); man.push_back({"scaling_layer.scale", {1, 3, 1, 1}}); }
-    for (const auto& e : man) {
-        const RawTensor* r = find_raw(c, e.first);
-        if (!r) HD_FAIL(c, HD_ERR_WEIGHTS, "Missing key in state_dict: %s", e.first.c_str());
-        if (r->shape != e.second) HD_FAIL(c, HD_ERR_WEIGHTS, "size mismatch for %s", e.first.c_str());
-    }
-    if (c->raw.size() != man.size()) {
-        std::unordered_map<std::string, int> known;
-        for (const auto& e : man) known[e.first] = 1;
-        for (const auto& kv : c->raw)
-            if (!known.count(kv.first)) HD_FAIL(c, HD_ERR_WEIGHTS, "Unexpected key in state_dict: %s", kv.first.c_str());
-    }
+    if (const int bad = check_manifest(c, man)) return bad;
     auto& w = c->lw;
     PackOpts pad8; pad8.cin_pad = 8;
     for (int k = 0; k < LP_LAYERS; ++k) {
@@ -165,8 +155,8 @@ int hd_lpips(hd_ctx* c, int batch, const float* images, int res, const float* re
     if (!c->lpips) HD_FAIL(c, HD_ERR_INVALID, "hd_lpips: ctx is not an LPIPS context (hd_lpips_create)");
     if (!c->finalized) HD_FAIL(c, HD_ERR_NOT_READY, "hd_lpips: ctx has no finalized weights (hd_load_weights / hd_finalize_weights)");
     if (batch < 1 || batch > 1024) HD_FAIL(c, HD_ERR_INVALID, "hd_lpips: batch must be in [1, 1024], got %d", batch);
-    if (!lp_res_ok(res)) HD_FAIL(c, HD_ERR_INVALID, "hd_lpips: res must be a multiple of 64 in [64, 512], got %d", res);
-    if (!lp_res_ok(ref_res)) HD_FAIL(c, HD_ERR_INVALID, "hd_lpips: ref_res must be a multiple of 64 in [64, 512], got %d", ref_res);
+    if (!res_ok(res)) HD_FAIL(c, HD_ERR_INVALID, "hd_lpips: res must be a multiple of 64 in [64, 512], got %d", res);
+    if (!res_ok(ref_res)) HD_FAIL(c, HD_ERR_INVALID, "hd_lpips: ref_res must be a multiple of 64 in [64, 512], got %d", ref_res);
     if (unit_range != 0 && unit_range != 1) HD_FAIL(c, HD_ERR_INVALID, "hd_lpips: unit_range must be 0 or 1, got %d", unit_range);
     if (!images) HD_FAIL(c, HD_ERR_INVALID, "hd_lpips: images is NULL");
     if (!ref) HD_FAIL(c, HD_ERR_INVALID, "hd_lpips: ref is NULL");
@@ -177,23 +167,21 @@ int hd_lpips(hd_ctx* c, int batch, const float* images, int res, const float* re
     if ((po | pl) % sizeof(double)) HD_FAIL(c, HD_ERR_INVALID, "hd_lpips: out and layers_out must be aligned to 8 bytes");
     const size_t nimg = (size_t)batch * 3 * res * res * sizeof(float), nref = (size_t)batch * 3 * ref_res * ref_res * sizeof(float);
     const size_t nrange = (size_t)batch * 2 * sizeof(float), nout = (size_t)batch * sizeof(double), nlay = nout * LP_LAYERS;
-    const struct { const char* name; uintptr_t p; size_t n; } outs[2] = {{"out", po, nout}, {"layers_out", pl, nlay}},
-                                                              ins[4] = {{"images", pi, nimg}, {"ref", pr, nref}, {"images_range", pir, nrange}, {"ref_range", prr, nrange}};
-    for (const auto& o : outs)
-        for (const auto& i : ins)
-            if (lp_overlap(o.p, o.n, i.p, i.n)) HD_FAIL(c, HD_ERR_INVALID, "hd_lpips: %s overlaps %s", o.name, i.name);
-    if (lp_overlap(po, nout, pl, nlay)) HD_FAIL(c, HD_ERR_INVALID, "hd_lpips: out overlaps layers_out");
+    const ByteRange outs[2] = {{"out", out, nout}, {"layers_out", layers_out, nlay}},
+                    ins[4] = {{"images", images, nimg}, {"ref", ref, nref}, {"images_range", images_range, nrange}, {"ref_range", ref_range, nrange}};
+    const ByteRange *a, *b;
+    if (first_overlap(outs, 2, ins, 4, &a, &b)) HD_FAIL(c, HD_ERR_INVALID, "hd_lpips: %s overlaps %s", a->name, b->name);
     HIPCHECK(c, hipSetDevice(c->device));
     int rc = alloc_lpips(c, batch, ref_res);
     if (rc) return rc;
-    const void* key[6] = {images, ref, images_range, ref_range, out, layers_out};
-    const int flags = res * 2 + unit_range;
-    if (c->ws->lpips_prog.empty() || memcmp(key, c->ws->lpips_key, sizeof(key)) != 0 || flags != c->ws->lpips_flags) {
+    CachedProgram& cp = c->ws->lpips_prog;
+    const ProgramKey key = {{images, ref, images_range, ref_range, out, layers_out}, (uint64_t)(res * 2 + unit_range)};
+    if (!cp.matches(key)) {
         rc = build_lpips(c, batch, images, res, ref, ref_res, unit_range, images_range, ref_range, out, layers_out);
         if (rc) return rc;
-        memcpy(c->ws->lpips_key, key, sizeof(key)); c->ws->lpips_flags = flags;
+        cp.store(key);
     }
-    return run_ops(c, c->ws->lpips_prog, reinterpret_cast<hipStream_t>(stream), c->op_limit);
+    return run_ops(c, cp.ops, reinterpret_cast<hipStream_t>(stream), c->op_limit);
 }
 
 }  // extern "C"

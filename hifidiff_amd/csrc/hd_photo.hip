@@ -1,48 +1,36 @@
 // hd_photo.hip -- hd_face_ingest / hd_face_paste and their workspace queries: argument checks, the per-face jobs of hd_photo.hpp's resize
 // kernel and its launches.  The contract is in include/hifidiff_hip.h.  No context: errors go to hd_last_error(NULL), and every argument
 // is checked before the first HIP call.
-#include <cstdio>
-#include <string>
 #include <vector>
 
-#include "../../include/hifidiff_hip.h"
+#include "hd_args.hpp"
 #include "hd_photo.hpp"
 
-void set_contextless_error(const std::string& msg);               // hd_lib.hip: the message hd_last_error(NULL) returns
-
 using namespace hd;
+using hd_args::res_ok;
 
 namespace {
 
-#define PH_FAIL(code, ...)                                        \
-    do {                                                          \
-        char _b[256];                                             \
-        snprintf(_b, sizeof(_b), __VA_ARGS__);                    \
-        set_contextless_error(_b);                                \
-        return (code);                                            \
-    } while (0)
-
 constexpr int PH_MAX_BATCH = 4096, PH_MAX_PHOTO_SIDE = 16384, PH_MAX_FEATHER = 256;
 
-bool ph_res_ok(int r) { return r >= 64 && r <= 512 && r % 64 == 0; }
 bool ph_lr_ok(int lr) { return lr == 0 || (lr >= 8 && lr <= 64); }
 
 // what both calls check of the photos and the boxes
 int ph_check_boxes(const char* fn, const void* photos, int n_photos, int height, int width, const int32_t* boxes, const int32_t* photo_index, int batch) {
-    if (!photos) PH_FAIL(HD_ERR_INVALID, "%s: photos is NULL", fn);
-    if (!boxes) PH_FAIL(HD_ERR_INVALID, "%s: boxes is NULL", fn);
-    if (n_photos < 1) PH_FAIL(HD_ERR_INVALID, "%s: n_photos must be >= 1, got %d", fn, n_photos);
-    if (height < 1 || height > PH_MAX_PHOTO_SIDE) PH_FAIL(HD_ERR_INVALID, "%s: height must be in [1, %d], got %d", fn, PH_MAX_PHOTO_SIDE, height);
-    if (width < 1 || width > PH_MAX_PHOTO_SIDE) PH_FAIL(HD_ERR_INVALID, "%s: width must be in [1, %d], got %d", fn, PH_MAX_PHOTO_SIDE, width);
-    if (batch < 1 || batch > PH_MAX_BATCH) PH_FAIL(HD_ERR_INVALID, "%s: batch must be in [1, %d], got %d", fn, PH_MAX_BATCH, batch);
+    if (!photos) HD_ARG_FAIL(HD_ERR_INVALID, "%s: photos is NULL", fn);
+    if (!boxes) HD_ARG_FAIL(HD_ERR_INVALID, "%s: boxes is NULL", fn);
+    if (n_photos < 1) HD_ARG_FAIL(HD_ERR_INVALID, "%s: n_photos must be >= 1, got %d", fn, n_photos);
+    if (height < 1 || height > PH_MAX_PHOTO_SIDE) HD_ARG_FAIL(HD_ERR_INVALID, "%s: height must be in [1, %d], got %d", fn, PH_MAX_PHOTO_SIDE, height);
+    if (width < 1 || width > PH_MAX_PHOTO_SIDE) HD_ARG_FAIL(HD_ERR_INVALID, "%s: width must be in [1, %d], got %d", fn, PH_MAX_PHOTO_SIDE, width);
+    if (batch < 1 || batch > PH_MAX_BATCH) HD_ARG_FAIL(HD_ERR_INVALID, "%s: batch must be in [1, %d], got %d", fn, PH_MAX_BATCH, batch);
     for (int i = 0; i < batch; ++i) {
         const int l = boxes[4 * i], t = boxes[4 * i + 1], w = boxes[4 * i + 2], h = boxes[4 * i + 3];
         if (w < 1 || w > PH_MAX_SIDE || h < 1 || h > PH_MAX_SIDE)
-            PH_FAIL(HD_ERR_INVALID, "%s: boxes[%d]: sides must be in [1, %d], got %d x %d", fn, i, PH_MAX_SIDE, w, h);
+            HD_ARG_FAIL(HD_ERR_INVALID, "%s: boxes[%d]: sides must be in [1, %d], got %d x %d", fn, i, PH_MAX_SIDE, w, h);
         if (l < 0 || t < 0 || l > width - w || t > height - h)
-            PH_FAIL(HD_ERR_INVALID, "%s: boxes[%d] = (%d, %d, %d, %d) does not lie inside the %d x %d photo", fn, i, l, t, w, h, width, height);
+            HD_ARG_FAIL(HD_ERR_INVALID, "%s: boxes[%d] = (%d, %d, %d, %d) does not lie inside the %d x %d photo", fn, i, l, t, w, h, width, height);
         if (photo_index && (photo_index[i] < 0 || photo_index[i] >= n_photos))
-            PH_FAIL(HD_ERR_INVALID, "%s: photo_index[%d] = %d is outside [0, %d)", fn, i, photo_index[i], n_photos);
+            HD_ARG_FAIL(HD_ERR_INVALID, "%s: photo_index[%d] = %d is outside [0, %d)", fn, i, photo_index[i], n_photos);
     }
     return HD_OK;
 }
@@ -71,29 +59,29 @@ hipError_t ph_launch(int batch, JobFn job, const uint8_t* src, uint8_t* dst8, fl
 extern "C" {
 
 int64_t hd_face_ingest_workspace(int batch, int lr, int res) {
-    if (batch < 1 || batch > PH_MAX_BATCH) PH_FAIL(HD_ERR_INVALID, "hd_face_ingest_workspace: batch must be in [1, %d], got %d", PH_MAX_BATCH, batch);
-    if (!ph_lr_ok(lr)) PH_FAIL(HD_ERR_INVALID, "hd_face_ingest_workspace: lr must be 0 or in [8, 64], got %d", lr);
-    if (!ph_res_ok(res)) PH_FAIL(HD_ERR_INVALID, "hd_face_ingest_workspace: res must be a multiple of 64 in [64, 512], got %d", res);
+    if (batch < 1 || batch > PH_MAX_BATCH) HD_ARG_FAIL(HD_ERR_INVALID, "hd_face_ingest_workspace: batch must be in [1, %d], got %d", PH_MAX_BATCH, batch);
+    if (!ph_lr_ok(lr)) HD_ARG_FAIL(HD_ERR_INVALID, "hd_face_ingest_workspace: lr must be 0 or in [8, 64], got %d", lr);
+    if (!res_ok(res)) HD_ARG_FAIL(HD_ERR_INVALID, "hd_face_ingest_workspace: res must be a multiple of 64 in [64, 512], got %d", res);
     return (int64_t)batch * lr * lr * 3;
 }
 
 int64_t hd_face_paste_workspace(int batch, int res) {
-    if (batch < 1 || batch > PH_MAX_BATCH) PH_FAIL(HD_ERR_INVALID, "hd_face_paste_workspace: batch must be in [1, %d], got %d", PH_MAX_BATCH, batch);
-    if (!ph_res_ok(res)) PH_FAIL(HD_ERR_INVALID, "hd_face_paste_workspace: res must be a multiple of 64 in [64, 512], got %d", res);
+    if (batch < 1 || batch > PH_MAX_BATCH) HD_ARG_FAIL(HD_ERR_INVALID, "hd_face_paste_workspace: batch must be in [1, %d], got %d", PH_MAX_BATCH, batch);
+    if (!res_ok(res)) HD_ARG_FAIL(HD_ERR_INVALID, "hd_face_paste_workspace: res must be a multiple of 64 in [64, 512], got %d", res);
     return (int64_t)batch * res * res * 3;
 }
 
 int hd_face_ingest(const uint8_t* photos, int n_photos, int height, int width, const int32_t* boxes, const int32_t* photo_index, int batch,
                    int lr, int res, float* out, uint8_t* out_u8, void* workspace, int64_t workspace_bytes, void* stream) {
     if (const int rc = ph_check_boxes("hd_face_ingest", photos, n_photos, height, width, boxes, photo_index, batch)) return rc;
-    if (!ph_lr_ok(lr)) PH_FAIL(HD_ERR_INVALID, "hd_face_ingest: lr must be 0 or in [8, 64], got %d", lr);
-    if (!ph_res_ok(res)) PH_FAIL(HD_ERR_INVALID, "hd_face_ingest: res must be a multiple of 64 in [64, 512], got %d", res);
-    if (!out) PH_FAIL(HD_ERR_INVALID, "hd_face_ingest: out is NULL");
-    if ((uintptr_t)out % sizeof(float)) PH_FAIL(HD_ERR_INVALID, "hd_face_ingest: out must be aligned to 4 bytes");
+    if (!ph_lr_ok(lr)) HD_ARG_FAIL(HD_ERR_INVALID, "hd_face_ingest: lr must be 0 or in [8, 64], got %d", lr);
+    if (!res_ok(res)) HD_ARG_FAIL(HD_ERR_INVALID, "hd_face_ingest: res must be a multiple of 64 in [64, 512], got %d", res);
+    if (!out) HD_ARG_FAIL(HD_ERR_INVALID, "hd_face_ingest: out is NULL");
+    if ((uintptr_t)out % sizeof(float)) HD_ARG_FAIL(HD_ERR_INVALID, "hd_face_ingest: out must be aligned to 4 bytes");
     const int64_t need = (int64_t)batch * lr * lr * 3;
-    if (need && !workspace) PH_FAIL(HD_ERR_INVALID, "hd_face_ingest: workspace is NULL (hd_face_ingest_workspace gives its size)");
+    if (need && !workspace) HD_ARG_FAIL(HD_ERR_INVALID, "hd_face_ingest: workspace is NULL (hd_face_ingest_workspace gives its size)");
     if (workspace_bytes < need)
-        PH_FAIL(HD_ERR_INVALID, "hd_face_ingest: workspace_bytes is %lld, this call needs %lld (hd_face_ingest_workspace)", (long long)workspace_bytes, (long long)need);
+        HD_ARG_FAIL(HD_ERR_INVALID, "hd_face_ingest: workspace_bytes is %lld, this call needs %lld (hd_face_ingest_workspace)", (long long)workspace_bytes, (long long)need);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     uint8_t* mid = static_cast<uint8_t*>(workspace);
     const int side = lr ? lr : res;                               // the first resize's target
@@ -121,28 +109,28 @@ int hd_face_ingest(const uint8_t* photos, int n_photos, int height, int width, c
     } else {
         e = ph_launch<false>(batch, crop, photos, out_u8, out, 0, s);
     }
-    if (e != hipSuccess) PH_FAIL(HD_ERR_HIP, "hd_face_ingest: launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) HD_ARG_FAIL(HD_ERR_HIP, "hd_face_ingest: launch failed: %s", hipGetErrorString(e));
     return HD_OK;
 }
 
 int hd_face_paste(uint8_t* photos, int n_photos, int height, int width, const float* faces, int res, const int32_t* boxes,
                   const int32_t* photo_index, int batch, int feather, void* workspace, int64_t workspace_bytes, void* stream) {
     if (const int rc = ph_check_boxes("hd_face_paste", photos, n_photos, height, width, boxes, photo_index, batch)) return rc;
-    if (!ph_res_ok(res)) PH_FAIL(HD_ERR_INVALID, "hd_face_paste: res must be a multiple of 64 in [64, 512], got %d", res);
-    if (feather < 0 || feather > PH_MAX_FEATHER) PH_FAIL(HD_ERR_INVALID, "hd_face_paste: feather must be in [0, %d], got %d", PH_MAX_FEATHER, feather);
-    if (!faces) PH_FAIL(HD_ERR_INVALID, "hd_face_paste: faces is NULL");
-    if ((uintptr_t)faces % sizeof(float)) PH_FAIL(HD_ERR_INVALID, "hd_face_paste: faces must be aligned to 4 bytes");
+    if (!res_ok(res)) HD_ARG_FAIL(HD_ERR_INVALID, "hd_face_paste: res must be a multiple of 64 in [64, 512], got %d", res);
+    if (feather < 0 || feather > PH_MAX_FEATHER) HD_ARG_FAIL(HD_ERR_INVALID, "hd_face_paste: feather must be in [0, %d], got %d", PH_MAX_FEATHER, feather);
+    if (!faces) HD_ARG_FAIL(HD_ERR_INVALID, "hd_face_paste: faces is NULL");
+    if ((uintptr_t)faces % sizeof(float)) HD_ARG_FAIL(HD_ERR_INVALID, "hd_face_paste: faces must be aligned to 4 bytes");
     for (int i = 0; i < batch; ++i)
         for (int k = i + 1; k < batch; ++k) {
             if ((photo_index ? photo_index[i] : 0) != (photo_index ? photo_index[k] : 0)) continue;
             const int32_t *a = boxes + 4 * i, *b = boxes + 4 * k;
             if (a[0] < b[0] + b[2] && b[0] < a[0] + a[2] && a[1] < b[1] + b[3] && b[1] < a[1] + a[3])
-                PH_FAIL(HD_ERR_INVALID, "hd_face_paste: boxes[%d] and boxes[%d] overlap in photo %d", i, k, photo_index ? photo_index[i] : 0);
+                HD_ARG_FAIL(HD_ERR_INVALID, "hd_face_paste: boxes[%d] and boxes[%d] overlap in photo %d", i, k, photo_index ? photo_index[i] : 0);
         }
     const int64_t need = (int64_t)batch * res * res * 3;
-    if (!workspace) PH_FAIL(HD_ERR_INVALID, "hd_face_paste: workspace is NULL (hd_face_paste_workspace gives its size)");
+    if (!workspace) HD_ARG_FAIL(HD_ERR_INVALID, "hd_face_paste: workspace is NULL (hd_face_paste_workspace gives its size)");
     if (workspace_bytes < need)
-        PH_FAIL(HD_ERR_INVALID, "hd_face_paste: workspace_bytes is %lld, this call needs %lld (hd_face_paste_workspace)", (long long)workspace_bytes, (long long)need);
+        HD_ARG_FAIL(HD_ERR_INVALID, "hd_face_paste: workspace_bytes is %lld, this call needs %lld (hd_face_paste_workspace)", (long long)workspace_bytes, (long long)need);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     uint8_t* q8 = static_cast<uint8_t*>(workspace);
     const long long npix = (long long)batch * res * res;
@@ -159,7 +147,7 @@ int hd_face_paste(uint8_t* photos, int n_photos, int height, int width, const fl
         };
         e = ph_launch<true>(batch, box, q8, photos, nullptr, feather, s);
     }
-    if (e != hipSuccess) PH_FAIL(HD_ERR_HIP, "hd_face_paste: launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) HD_ARG_FAIL(HD_ERR_HIP, "hd_face_paste: launch failed: %s", hipGetErrorString(e));
     return HD_OK;
 }
 

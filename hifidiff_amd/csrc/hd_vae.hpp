@@ -7,21 +7,13 @@
 // what is not a GEMM.  Activations are channels-last [face, y, x][C].
 #pragma once
 #include <hip/hip_runtime.h>
+#include "hd_bicubic.hpp"
 #include "hd_gemm.hpp"
 #include "hd_kernels.hpp"
 
 namespace hd {
 
-// ---- F.interpolate(x, R, mode="bicubic", align_corners=False) on NCHW fp32 (ATen upsample_bicubic2d: A = -0.75,
-// source index (dst + 0.5) * scale - 0.5, taps clamped to the border) ----
-__device__ __forceinline__ void cubic_coeffs(float t, float* w) {
-    const float A = -0.75f;
-    const float x0 = t + 1.f, x1 = t, x2 = 1.f - t, x3 = 2.f - t;
-    w[0] = ((A * x0 - 5.f * A) * x0 + 8.f * A) * x0 - 4.f * A;
-    w[1] = ((A + 2.f) * x1 - (A + 3.f)) * x1 * x1 + 1.f;
-    w[2] = ((A + 2.f) * x2 - (A + 3.f)) * x2 * x2 + 1.f;
-    w[3] = ((A * x3 - 5.f * A) * x3 + 8.f * A) * x3 - 4.f * A;
-}
+// ---- F.interpolate(x, R, mode="bicubic", align_corners=False) on NCHW fp32 (hd_bicubic.hpp: cubic_coeffs) ----
 static __global__ void bicubic_resize_kernel(const float* __restrict__ in, float* __restrict__ out, int planes, int Hin, int Win, int Hout, int Wout) {
     const size_t total = (size_t)planes * Hout * Wout;
     const float sy = (float)Hin / (float)Hout, sx = (float)Win / (float)Wout;

@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, arch
+from ._context import WeightContext, check_face_images, require_cuda, stream_ptr
 
 CHANNELS = {"rgb": 1, "y": 2}
 NORMALIZE = (None, "face", "batch")
@@ -141,20 +142,14 @@ def _check_mode(channels, data_range, normalize):
 def _check_images(name, t):
     if not torch.is_tensor(t):
         raise ValueError("%s must be a tensor" % name)
-    if t.dim() != 4 or t.shape[1] != 3 or t.shape[2] != t.shape[3] or t.shape[2] % 64 or not 64 <= t.shape[2] <= 512:
-        raise ValueError("%s must be (B,3,R,R) with R a multiple of 64 in [64, 512], got %s" % (name, tuple(t.shape)))
-
-
-def _check_device(t):
-    if t.device.type != "cuda":
-        raise RuntimeError("hifidiff_amd runs on an MI355X (gfx950) GPU only; got device %s (no CPU fallback)" % t.device)
+    check_face_images(name, t)
 
 
 def _range(x, size):
     B = int(x.shape[0])
     out = torch.empty((B, 2), dtype=torch.float32, device=x.device)
     if B:
-        _lib.check(_lib.lib().hd_image_range(x.data_ptr(), B, int(x.shape[2]), int(size), out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream))
+        _lib.check(_lib.lib().hd_image_range(x.data_ptr(), B, int(x.shape[2]), int(size), out.data_ptr(), stream_ptr(x.device)))
     return out
 
 
@@ -165,7 +160,7 @@ def image_range(images, size=None):
     size = int(images.shape[2]) if size is None else size
     if isinstance(size, bool) or not isinstance(size, int) or size % 64 or not 64 <= size <= 512:
         raise ValueError("size must be a multiple of 64 in [64, 512], got %r" % (size,))
-    _check_device(images)
+    require_cuda(images.device)
     with torch.cuda.device(images.device):
         return _range(images.to(dtype=torch.float32).contiguous(), size)
 
@@ -181,7 +176,7 @@ def image_metrics(images, ref, channels="y", data_range=1.0, normalize=None, ssi
     _check_images("ref", ref)
     if images.shape[0] != ref.shape[0]:
         raise ValueError("images and ref must hold the same number of faces, got %d and %d" % (images.shape[0], ref.shape[0]))
-    _check_device(images)
+    require_cuda(images.device)
     dev = images.device
     a = images.to(dtype=torch.float32).contiguous()
     b = ref.to(device=dev, dtype=torch.float32).contiguous()
@@ -201,7 +196,7 @@ def image_metrics(images, ref, channels="y", data_range=1.0, normalize=None, ssi
             _lib.check(L.hd_image_metrics(a.data_ptr(), R, b.data_ptr(), Rb, B, CHANNELS[channels], float(data_range),
                                           ra.data_ptr() if ra is not None else None, rb.data_ptr() if rb is not None else None,
                                           out.data_ptr(), smap.data_ptr() if smap is not None else None, ws.data_ptr(), nbytes,
-                                          torch.cuda.current_stream(dev).cuda_stream))     # ws: freed to the stream it was used on
+                                          stream_ptr(dev)))     # ws: freed to the stream it was used on
     mse = out[:, 0]
     return Metrics(mse, psnr_from_mse(mse, float(data_range)), out[:, 1], smap)
 
@@ -291,7 +286,7 @@ def lpips_reference(state, images, ref, normalize=True, input_normalize=None, pe
     return (total, layers) if per_layer else total
 
 
-class LPIPS:
+class LPIPS(WeightContext):
     """LPIPS-AlexNet v0.1 in libhifidiff_hip.so (hd_lpips).  GPU only.  `load_state_dict` takes the `lpips` package's full-model names
     (arch.lpips_manifest; unpinned, the package is absent), or a torchvision AlexNet file's `features.{0,3,6,8,10}.*` (`classifier.*` is
     ignored) together with the lin layers as `lin{k}.model.1.weight` or `lins.{k}.model.1.weight`."""
@@ -299,7 +294,8 @@ class LPIPS:
     _FEATURES = {"features.%s" % n.rsplit(".", 1)[1]: n for n, *_ in arch.LPIPS_CONVS}     # features.0 -> net.slice1.0, ...
 
     def __init__(self):
-        self._ctx, self._device, self._state, self._loaded, self._keep, self._complete = None, None, None, False, None, False
+        super().__init__()
+        self._complete = False
 
     @classmethod
     def from_files(cls, alexnet_path, lin_path):
@@ -352,52 +348,15 @@ class LPIPS:
     def state_dict(self, *a, **k):
         return dict(self._state or {})
 
-    def to(self, *args, **kwargs):
-        device = kwargs.get("device", args[0] if args else None)
-        if isinstance(device, (str, torch.device, int)):
-            self._ensure(torch.device("cuda", device) if isinstance(device, int) else torch.device(device))
-        return self
-
-    def cuda(self, device=None):
-        return self.to(torch.device("cuda", device if device is not None else torch.cuda.current_device()))
-
-    def _ensure(self, device):
-        if device.type != "cuda":
-            raise RuntimeError("hifidiff_amd runs on an MI355X (gfx950) GPU only; got device %s (no CPU fallback)" % device)
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        if self._ctx is not None:
-            if idx != self._device.index:
-                raise RuntimeError("this model already lives on cuda:%d" % self._device.index)
-            return
+    def _create(self, idx):
         ctx = ctypes.c_void_p()
         _lib.check(_lib.lib().hd_lpips_create(ctypes.byref(ctx), idx))
-        self._ctx, self._device = ctx, torch.device("cuda", idx)
-        if self._state is not None:
-            self._upload()
+        return ctx
 
-    def _upload(self):
+    def _items(self):
         if not self._complete:
             raise RuntimeError("state dict incomplete: %d tensors loaded" % len(self._state))
-        L = _lib.lib()
-        keep, descs = [], (_lib.TensorDesc * len(self._state))()
-        for i, (k, v) in enumerate(self._state.items()):
-            t = v.to(torch.float32).contiguous()
-            keep.append(t)
-            d = descs[i]
-            d.name, d.data, d.ndim, d.is_device = k.encode(), t.data_ptr(), t.dim(), 1 if t.is_cuda else 0
-            for j, n in enumerate(t.shape):
-                d.shape[j] = n
-        if self._loaded:
-            L.hd_destroy(self._ctx)
-            self._ctx = None
-            self._loaded = False                             # nothing usable until finalize has succeeded
-            ctx = ctypes.c_void_p()
-            _lib.check(L.hd_lpips_create(ctypes.byref(ctx), self._device.index))
-            self._ctx = ctx
-        with torch.cuda.device(self._device):
-            _lib.check(L.hd_load_weights(self._ctx, descs, len(self._state)), self._ctx)
-            _lib.check(L.hd_finalize_weights(self._ctx), self._ctx)
-        self._loaded = True
+        return list(self._state.items())         # the optional scaling keys included
 
     def __call__(self, images, ref, normalize=True, input_normalize=None, per_layer=False):
         """hd_lpips on the current stream of images' device: images [B,3,R,R] against ref [B,3,Rb,Rb] at ref's size (R, Rb multiples of
@@ -410,7 +369,7 @@ class LPIPS:
         _check_images("ref", ref)
         if images.shape[0] != ref.shape[0]:
             raise ValueError("images and ref must hold the same number of faces, got %d and %d" % (images.shape[0], ref.shape[0]))
-        _check_device(images)
+        require_cuda(images.device)
         self._ensure(images.device)
         if not self._loaded:
             raise RuntimeError("weights are not loaded: call load_state_dict(...) first")
@@ -430,13 +389,6 @@ class LPIPS:
                 _lib.check(_lib.lib().hd_lpips(self._ctx, B, a.data_ptr(), R, b.data_ptr(), Rb, 1 if normalize else 0,
                                                ra.data_ptr() if ra is not None else None, rb.data_ptr() if rb is not None else None,
                                                out.data_ptr(), layers.data_ptr() if layers is not None else None,
-                                               torch.cuda.current_stream(dev).cuda_stream), self._ctx)
+                                               stream_ptr(dev)), self._ctx)
             self._keep = (a, b, ra, rb, out, layers)         # the launch program holds these pointers until the next call
         return (out, layers) if per_layer else out
-
-    def __del__(self):
-        try:
-            if self._ctx is not None:
-                _lib.lib().hd_destroy(self._ctx)
-        except Exception:
-            pass

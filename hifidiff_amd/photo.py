@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._context import require_cuda, stream_ptr
 
 PRECISION_BITS = 22                                                   # Pillow's 32 - 8 - 2
 MAX_SIDE = 2048
@@ -200,17 +201,12 @@ def _host_i32(a):
     return a, a.ctypes.data_as(ctypes.c_void_p)
 
 
-def _gpu_only(t):
-    if t.device.type != "cuda":
-        raise RuntimeError("hifidiff_amd runs on an MI355X (gfx950) GPU only; got device %s (no CPU fallback)" % t.device)
-
-
 def ingest(photos, boxes, photo_index=None, lr=32, res=128, return_uint8=False):
     """hd_face_ingest on the current stream of photos' device: photos uint8 [N,H,W,3], boxes [B,4] (left, top, width, height) and
     photo_index [B] on the host.  Returns fp32 [B,3,res,res] in [0, 1] (and the uint8 [B,res,res,3] with return_uint8)."""
     b, idx = _check_common(photos, boxes, photo_index)
     _check_sizes(lr, res)
-    _gpu_only(photos)
+    require_cuda(photos.device)
     dev, B = photos.device, len(b)
     out = torch.empty((B, 3, res, res), dtype=torch.float32, device=dev)
     u8 = torch.empty((B, res, res, 3), dtype=torch.uint8, device=dev) if return_uint8 else None
@@ -222,8 +218,7 @@ def ingest(photos, boxes, photo_index=None, lr=32, res=128, return_uint8=False):
         (b, bp), (idx, ip) = _host_i32(b), _host_i32(idx)
         with torch.cuda.device(dev):
             _lib.check(L.hd_face_ingest(p.data_ptr(), int(p.shape[0]), int(p.shape[1]), int(p.shape[2]), bp, ip, B, lr, res, out.data_ptr(),
-                                        u8.data_ptr() if u8 is not None else None, ws.data_ptr(), need,
-                                        torch.cuda.current_stream(dev).cuda_stream))
+                                        u8.data_ptr() if u8 is not None else None, ws.data_ptr(), need, stream_ptr(dev)))
         ws.record_stream(torch.cuda.current_stream(dev))
     return (out, u8) if return_uint8 else out
 
@@ -237,7 +232,7 @@ def paste(photos, faces, boxes, photo_index=None, feather=0, inplace=False):
     pair = boxes_overlap(b, idx)
     if pair is not None:
         raise ValueError("boxes %d and %d overlap in one photo" % pair)
-    _gpu_only(photos)
+    require_cuda(photos.device)
     if inplace and not photos.is_contiguous():
         raise ValueError("inplace needs contiguous photos")
     dev, B = photos.device, len(b)
@@ -251,7 +246,7 @@ def paste(photos, faces, boxes, photo_index=None, feather=0, inplace=False):
         (b, bp), (idx, ip) = _host_i32(b), _host_i32(idx)
         with torch.cuda.device(dev):
             _lib.check(L.hd_face_paste(out.data_ptr(), int(out.shape[0]), int(out.shape[1]), int(out.shape[2]), f.data_ptr(), res, bp, ip, B,
-                                       feather, ws.data_ptr(), need, torch.cuda.current_stream(dev).cuda_stream))
+                                       feather, ws.data_ptr(), need, stream_ptr(dev)))
         ws.record_stream(torch.cuda.current_stream(dev))
         f.record_stream(torch.cuda.current_stream(dev))
     return out

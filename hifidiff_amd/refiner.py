@@ -31,6 +31,7 @@ import torch
 from torch import nn
 
 from . import _lib, arch
+from ._context import WeightContext, stream_ptr
 
 
 class UNet2DOutput:
@@ -40,10 +41,6 @@ class UNet2DOutput:
 
 class _Config:
     pass
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 def _f32c(t, device):
@@ -196,35 +193,24 @@ def check_latent_res(latent_res, name="latent_res"):
     return int(latent_res)
 
 
-class _Engine:
+class _Engine(WeightContext):
     """Owns the hd_ctx of one (latent_res, device)."""
 
+    # the names this module, sampling.py and the tests use for what WeightContext holds (state: the loaded state dict, for state_dict())
+    ctx, device, state, loaded = (property(lambda self, n=n: getattr(self, n), lambda self, v, n=n: setattr(self, n, v))
+                                  for n in ("_ctx", "_device", "_state", "_loaded"))
+    ensure = WeightContext._ensure
+
     def __init__(self, latent_res, conditional=True):
+        super().__init__()
         self.latent_res = check_latent_res(latent_res)
         self.conditional = conditional     # False: the unconditional Denoiser (models/denoiser/model.py:32)
-        self.ctx = None
-        self.device = None
-        self.state = None          # CPU copy of the loaded state dict (for state_dict())
-        self.loaded = False
         self.cond_key = None
         self.batch = None
+        self.prior_key = None
         self.preview_cfg = None    # (every, snapshots) while previews are on: given to every context this engine creates
         self.guide_on = False      # hd_guide_config: given to every context this engine creates
         self.pool_cap = None       # hd_pool_config: the capacity while a pool is on; given to every context this engine creates
-
-    def ensure(self, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("hifidiff_amd runs on an MI355X (gfx950) GPU only; got device %s (no CPU fallback)" % device)
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        if self.ctx is not None:
-            if idx != self.device.index:
-                raise RuntimeError("this model already lives on cuda:%d" % self.device.index)
-            return
-        ctx = self._create(idx)
-        self.ctx, self.device = ctx, torch.device("cuda", idx)
-        if self.state is not None:
-            self._upload()
 
     def _create(self, idx):
         L = _lib.lib()
@@ -238,13 +224,13 @@ class _Engine:
             _lib.check(L.hd_pool_config(ctx, self.pool_cap), ctx)
         return ctx
 
-    def manifest(self):
+    def _manifest(self):
         if self.conditional:
             return arch.refiner_manifest(self.latent_res)
         return arch.denoiser_manifest(self.latent_res, prefix="denoiser", fused=False)
 
     def load(self, sd, strict=True):
-        man = self.manifest()
+        man = self._manifest()
         missing = [k for k in man if k not in sd]
         unexpected = [k for k in sd if k not in man]
         if strict and (missing or unexpected):
@@ -259,34 +245,8 @@ class _Engine:
             self._upload()                                 # a context whose weights are finalized is replaced (self.loaded)
         return missing, unexpected
 
-    def _upload(self):
-        man = self.manifest()
-        if any(k not in self.state for k in man):
-            raise RuntimeError("state dict incomplete: %d of %d tensors loaded" % (len(self.state), len(man)))
-        L = _lib.lib()
-        keep, descs = [], (_lib.TensorDesc * len(man))()
-        for i, k in enumerate(man):
-            t = self.state[k]
-            if t.dtype != torch.int64:
-                t = t.to(torch.float32)
-            t = t.contiguous()
-            keep.append(t)
-            d = descs[i]
-            d.name = k.encode()
-            d.data = t.data_ptr()
-            d.ndim = t.dim()
-            for j, s in enumerate(t.shape):
-                d.shape[j] = s
-            d.is_device = 1 if t.is_cuda else 0
-        if self.loaded:      # re-load: a fresh context is simplest (weights are packed once)
-            L.hd_destroy(self.ctx)
-            self.ctx = None
-            self.loaded, self.cond_key, self.batch, self.prior_key = False, None, None, None      # nothing usable until finalize succeeds
-            self.ctx = self._create(self.device.index)
-        with torch.cuda.device(self.device):
-            _lib.check(L.hd_load_weights(self.ctx, descs, len(man)), self.ctx)
-            _lib.check(L.hd_finalize_weights(self.ctx), self.ctx)
-        self.loaded, self.cond_key, self.batch, self.prior_key = True, None, None, None
+    def _reset(self):
+        self.cond_key, self.batch, self.prior_key = None, None, None
 
     def after_submodule_call(self, batch):
         """`model.fpg(x)` / `model.idc(x)` run on the workspace of THEIR batch size: with another batch than the prepared one
@@ -335,7 +295,7 @@ class _Engine:
         self.require_loaded()
         B = cr_latent.shape[0]
         ptrs, keep = self._cond(B, cr_latent, cr_face, id_emb)
-        self._call("hd_prepare", B, *ptrs, _stream(self.device))
+        self._call("hd_prepare", B, *ptrs, stream_ptr(self.device))
         self.batch, self.cond_key, self.prior_key = B, None, None
 
     def prepare_slots(self, slots, cr_latent, cr_face=None, id_emb=None):
@@ -343,7 +303,7 @@ class _Engine:
         self.require_loaded()
         n, sp, sl = self._faces(slots)
         ptrs, keep = self._cond(n, cr_latent, cr_face, id_emb)
-        self._call("hd_prepare_slots", n, sp, *ptrs, _stream(self.device))
+        self._call("hd_prepare_slots", n, sp, *ptrs, stream_ptr(self.device))
         self.cond_key, self.prior_key = None, None         # the batch no longer matches any one pair of tensors
 
     def enable_pool(self, capacity):
@@ -369,7 +329,7 @@ class _Engine:
             raise RuntimeError("no batch is prepared: call prepare(cr_face, cr_latent) for the whole batch first")
         en = entries_arg(entries, self.pool_cap, min(self.batch, self.pool_cap or 0), True)
         ptrs, keep = self._cond(en.numel(), cr_latent, cr_face, id_emb)
-        self._call("hd_pool_prepare", en.numel(), _i32p(en), *ptrs, _stream(self.device))
+        self._call("hd_pool_prepare", en.numel(), _i32p(en), *ptrs, stream_ptr(self.device))
 
     def pool_commit(self, slots, entries):
         """hd_pool_commit: the prepared batch's faces in `slots` (n distinct ints in [0, B)) take the conditioning kept in `entries`
@@ -379,7 +339,7 @@ class _Engine:
         en = entries_arg(entries, self.pool_cap, self.batch, False)
         if en.numel() != n:
             raise ValueError(f"{n} slots but {en.numel()} entries")
-        self._call("hd_pool_commit", n, sp, _i32p(en), _stream(self.device))
+        self._call("hd_pool_commit", n, sp, _i32p(en), stream_ptr(self.device))
         self.cond_key, self.prior_key = None, None         # the batch no longer matches any one pair of tensors
 
     def set_mask(self, mask, known, noise, slots=None):
@@ -393,14 +353,14 @@ class _Engine:
         m, k, z = mask_args(mask, known, noise, n, self.latent_res)
         self.require_loaded()
         m, k, z = _f32c(m, self.device), _f32c(k, self.device), _f32c(z, self.device)
-        self._call("hd_mask_faces", n, sp, m.data_ptr(), k.data_ptr(), z.data_ptr(), _stream(self.device))
+        self._call("hd_mask_faces", n, sp, m.data_ptr(), k.data_ptr(), z.data_ptr(), stream_ptr(self.device))
 
     def clear_mask(self, slots=None):
         """Take the masks of the faces in `slots` (None: of every face) away; a no-op without a prepared batch."""
         if self.batch is None or self.ctx is None:
             return
         n, sp, sl = self._faces(slots)
-        self._call("hd_mask_faces", n, sp, None, None, None, _stream(self.device))
+        self._call("hd_mask_faces", n, sp, None, None, None, stream_ptr(self.device))
 
     def set_guidance(self, target, weight, scale, rows=None, slots=None):
         """hd_guide_faces: the faces in `slots` (None: the whole prepared batch, in order) are guided from now on -- see
@@ -417,14 +377,14 @@ class _Engine:
             self._call("hd_guide_config", 1)
             self.guide_on = True
         self._call("hd_guide_faces", n, sp, g.data_ptr(), ctypes.cast(w.data_ptr(), ctypes.POINTER(ctypes.c_float)), _i32p(N), _i32p(r0), _i32p(r1),
-                   _stream(self.device))
+                   stream_ptr(self.device))
 
     def clear_guidance(self, slots=None):
         """Stop guiding the faces in `slots` (None: every face); a no-op without a prepared batch."""
         if self.batch is None or self.ctx is None:
             return
         n, sp, sl = self._faces(slots)
-        self._call("hd_guide_faces", n, sp, None, None, None, None, None, _stream(self.device))
+        self._call("hd_guide_faces", n, sp, None, None, None, None, None, stream_ptr(self.device))
 
     def disable_guidance(self):
         """hd_guide_config(on = 0): no face is guided and the step has no guided launch."""
@@ -457,13 +417,13 @@ class _Engine:
         L = self.latent_res
         x0 = torch.empty((n, 4, L, L), dtype=torch.float32, device=self.device)
         rows = torch.empty((n,), dtype=torch.int32, device=self.device)
-        self._call("hd_preview_read", n, sp, snap, x0.data_ptr(), rows.data_ptr(), _stream(self.device))
+        self._call("hd_preview_read", n, sp, snap, x0.data_ptr(), rows.data_ptr(), stream_ptr(self.device))
         return x0, rows
 
     def prepare_unconditional(self, batch):
         self.require_loaded()
         if self.batch != batch:
-            self._call("hd_prepare_unconditional", batch, _stream(self.device))
+            self._call("hd_prepare_unconditional", batch, stream_ptr(self.device))
             self.batch, self.cond_key = batch, None
 
     def prepare_from_priors(self, priors, id_emb):
@@ -480,7 +440,7 @@ class _Engine:
             keep.append(_f32c(p, self.device))
         emb = _f32c(id_emb.reshape(B, -1), self.device)
         ptrs = (ctypes.c_void_p * 5)(*[t.data_ptr() for t in keep])
-        self._call("hd_prepare_from_priors", B, ptrs, emb.data_ptr(), _stream(self.device))
+        self._call("hd_prepare_from_priors", B, ptrs, emb.data_ptr(), stream_ptr(self.device))
         self.batch, self.cond_key = B, None
 
     def timesteps_tensor(self, timesteps, batch):
@@ -504,7 +464,7 @@ class _Engine:
         x = _f32c(latents, self.device)
         t = self.timesteps_tensor(timesteps, B)
         out = torch.empty_like(x)
-        self._call("hd_eps", x.data_ptr(), t.data_ptr(), t.numel(), out.data_ptr(), _stream(self.device))
+        self._call("hd_eps", x.data_ptr(), t.data_ptr(), t.numel(), out.data_ptr(), stream_ptr(self.device))
         return out
 
     def check(self, synchronize=True):
@@ -519,13 +479,6 @@ class _Engine:
         if synchronize:
             torch.cuda.current_stream(self.device).synchronize()
         self._call("hd_check")
-
-    def __del__(self):
-        try:
-            if self.ctx is not None:
-                _lib.lib().hd_destroy(self.ctx)
-        except Exception:
-            pass
 
 
 class _SubModule(nn.Module):
@@ -546,7 +499,7 @@ class ResNet50(_SubModule):
         xin = _f32c(x, e.device)
         out = torch.empty((B, 2048), dtype=torch.float32, device=e.device)
         with torch.cuda.device(e.device):
-            _lib.check(_lib.lib().hd_idc(e.ctx, B, xin.data_ptr(), out.data_ptr(), _stream(e.device)), e.ctx)
+            _lib.check(_lib.lib().hd_idc(e.ctx, B, xin.data_ptr(), out.data_ptr(), stream_ptr(e.device)), e.ctx)
         e.after_submodule_call(B)
         return out.reshape(B, 2048, 1, 1)
 
@@ -565,7 +518,7 @@ class FacialPriorGuidance(_SubModule):
         outs = [torch.empty((B, 2048 >> i, s << i, s << i), dtype=torch.float32, device=e.device) for i in range(5)]
         ptrs = (ctypes.c_void_p * 5)(*[t.data_ptr() for t in outs])
         with torch.cuda.device(e.device):
-            _lib.check(_lib.lib().hd_fpg(e.ctx, B, xin.data_ptr(), ptrs, _stream(e.device)), e.ctx)
+            _lib.check(_lib.lib().hd_fpg(e.ctx, B, xin.data_ptr(), ptrs, stream_ptr(e.device)), e.ctx)
         e.after_submodule_call(B)
         return outs
 
@@ -584,7 +537,7 @@ class FusedDenoiser(_SubModule):
         e.ensure(latents.device)
         # the gates and idc_conv depend on the priors / embedding only (models/fpg/hca.py:26-27, models/denoiser/model.py:245):
         # the loop passes the same objects every step -> computed once (identity + version, strong references: never addresses)
-        k = getattr(e, "prior_key", None)
+        k = e.prior_key
         objs = list(facial_priors) + [identity_embedding]
         # (tensors without a version counter -- torch.inference_mode() -- are never a hit; writes through `.data`, numpy or
         # DLPack aliases do not bump the counter: pass a new tensor object or call invalidate_conditioning() after such a write)
@@ -607,9 +560,7 @@ class _EngineModule(nn.Module):
     subclass's __init__)."""
 
     def to(self, *args, **kwargs):
-        device = kwargs.get("device", args[0] if args else None)
-        if isinstance(device, (str, torch.device, int)):
-            self._engine.ensure(torch.device("cuda", device) if isinstance(device, int) else device)
+        self._engine.to(*args, **kwargs)
         return self
 
     def cuda(self, device=None):

@@ -12,6 +12,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._context import stream_ptr
 
 
 @torch.no_grad()
@@ -381,7 +382,7 @@ def _run(e, x, table, start_steps=None, spans=None, n_iters=None, resume=False, 
         else:
             fn, args = L.hd_sample_rows, (ptr(rows), int(n_iters))
     with torch.cuda.device(e.device):
-        _lib.check(fn(e.ctx, x.data_ptr(), ctypes.byref(sch), *args, nptr, int(seed), torch.cuda.current_stream(e.device).cuda_stream), e.ctx)
+        _lib.check(fn(e.ctx, x.data_ptr(), ctypes.byref(sch), *args, nptr, int(seed), stream_ptr(e.device)), e.ctx)
     if check:
         e.check()
     return x

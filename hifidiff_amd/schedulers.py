@@ -13,6 +13,7 @@ import math
 import torch
 
 from . import _lib
+from ._context import stream_ptr
 
 
 class SchedulerOutput:
@@ -96,7 +97,7 @@ class _Base:
             nptr = noise.data_ptr()
         with torch.cuda.device(x.device):                  # the C function takes no context: launch on x's device and stream
             rc = _lib.lib().hd_scheduler_step(x.data_ptr(), eps.data_ptr(), c, nptr, int(seed), int(step), x.numel(),
-                                              torch.cuda.current_stream(x.device).cuda_stream)
+                                              stream_ptr(x.device))
         _lib.check(rc)
         return SchedulerOutput(x)
 
@@ -246,6 +247,6 @@ class DPMSolverMultistepScheduler(_Base):
             nptr = noise.data_ptr()
         with torch.cuda.device(x.device):
             rc = _lib.lib().hd_scheduler_step_multistep(x.data_ptr(), eps.data_ptr(), c, h.data_ptr(), nptr, int(seed), i, x.numel(),
-                                                        torch.cuda.current_stream(x.device).cuda_stream)
+                                                        stream_ptr(x.device))
         _lib.check(rc)
         return SchedulerOutput(x)

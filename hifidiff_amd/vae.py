@@ -15,6 +15,7 @@ import torch
 from torch import nn
 
 from . import _lib, arch
+from ._context import WeightContext, stream_ptr
 
 
 class DiagonalGaussianDistribution:
@@ -53,11 +54,10 @@ class _Config:
     block_out_channels = arch.VAE_CHANNELS
 
 
-class AutoencoderKL(nn.Module):
+class AutoencoderKL(WeightContext, nn.Module):
     def __init__(self):
         super().__init__()
         self.config = _Config()
-        self._ctx, self._device, self._state, self._loaded, self._keep = None, None, None, False, None
 
     @classmethod
     def from_pretrained(cls, name_or_path, subfolder=None, **kw):
@@ -111,53 +111,13 @@ class AutoencoderKL(nn.Module):
     def state_dict(self, *a, **k):
         return dict(self._state or {})
 
-    def to(self, *args, **kwargs):
-        device = kwargs.get("device", args[0] if args else None)
-        if isinstance(device, (str, torch.device, int)):
-            self._ensure(torch.device("cuda", device) if isinstance(device, int) else torch.device(device))
-        return self
+    # ---- library plumbing (_context.WeightContext) ----
+    _manifest = staticmethod(arch.vae_manifest)
 
-    def cuda(self, device=None):
-        return self.to(torch.device("cuda", device if device is not None else torch.cuda.current_device()))
-
-    def _ensure(self, device):
-        if device.type != "cuda":
-            raise RuntimeError("hifidiff_amd runs on an MI355X (gfx950) GPU only; got device %s (no CPU fallback)" % device)
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        if self._ctx is not None:
-            if idx != self._device.index:
-                raise RuntimeError("this model already lives on cuda:%d" % self._device.index)
-            return
+    def _create(self, idx):
         ctx = ctypes.c_void_p()
         _lib.check(_lib.lib().hd_vae_create(ctypes.byref(ctx), idx))
-        self._ctx, self._device = ctx, torch.device("cuda", idx)
-        if self._state is not None:
-            self._upload()
-
-    def _upload(self):
-        man = arch.vae_manifest()
-        if any(k not in self._state for k in man):
-            raise RuntimeError("state dict incomplete: %d of %d tensors loaded" % (len(self._state), len(man)))
-        L = _lib.lib()
-        keep, descs = [], (_lib.TensorDesc * len(man))()
-        for i, k in enumerate(man):
-            t = self._state[k].to(torch.float32).contiguous()
-            keep.append(t)
-            d = descs[i]
-            d.name, d.data, d.ndim, d.is_device = k.encode(), t.data_ptr(), t.dim(), 1 if t.is_cuda else 0
-            for j, s in enumerate(t.shape):
-                d.shape[j] = s
-        if self._loaded:
-            L.hd_destroy(self._ctx)
-            self._ctx = None
-            self._loaded = False                             # nothing usable until finalize has succeeded
-            ctx = ctypes.c_void_p()
-            _lib.check(L.hd_vae_create(ctypes.byref(ctx), self._device.index))
-            self._ctx = ctx
-        with torch.cuda.device(self._device):
-            _lib.check(L.hd_load_weights(self._ctx, descs, len(man)), self._ctx)
-            _lib.check(L.hd_finalize_weights(self._ctx), self._ctx)
-        self._loaded = True
+        return ctx
 
     def _ready(self, x):
         self._ensure(x.device)
@@ -187,7 +147,7 @@ class AutoencoderKL(nn.Module):
             _lib.check(_lib.lib().hd_vae_encode(self._ctx, B, int(x.shape[2]), R, xin.data_ptr(), 1 if vae_range else 0,
                                                 nz.data_ptr() if nz is not None else None, int(seed),
                                                 out.data_ptr() if want_moments else None, None if want_moments else out.data_ptr(),
-                                                torch.cuda.current_stream(self._device).cuda_stream), self._ctx)
+                                                stream_ptr(self._device)), self._ctx)
         self._keep = (xin, nz, out)                  # the launch program holds these pointers until the next call
         return out
 
@@ -224,13 +184,6 @@ class AutoencoderKL(nn.Module):
         out = torch.empty((B, 3, 8 * Lr, 8 * Lr), dtype=torch.float32, device=self._device)
         with torch.cuda.device(self._device):
             _lib.check(_lib.lib().hd_vae_decode(self._ctx, B, Lr, zin.data_ptr(), out.data_ptr(),
-                                                torch.cuda.current_stream(self._device).cuda_stream), self._ctx)
+                                                stream_ptr(self._device)), self._ctx)
         self._keep = (zin, out)
         return out.clone()
-
-    def __del__(self):
-        try:
-            if self._ctx is not None:
-                _lib.lib().hd_destroy(self._ctx)
-        except Exception:
-            pass

@@ -328,6 +328,46 @@ def test_error_behaviour(gpu, weights16, model2, inputs2):
     assert tuple(sampling.sample(model2, x[:0], crf[:0], crl[:0], sch).shape) == (0, 4, 16, 16)
 
 
+def _strict_load_kinds():
+    from hifidiff_amd import arch
+    return {"refiner": ("hd_create", (16,), lambda: arch.refiner_manifest(16)), "cr": ("hd_cr_create", (), arch.cr_manifest),
+            "vae": ("hd_vae_create", (), arch.vae_manifest), "lpips": ("hd_lpips_create", (), arch.lpips_manifest)}
+
+
+@pytest.mark.parametrize("how", ["missing", "extra", "shape"])
+@pytest.mark.parametrize("kind", ["refiner", "cr", "vae", "lpips"])
+def test_strict_load_in_the_library(gpu, kind, how):
+    """hd_finalize_weights of each context kind refuses a state dict with one key missing, one key too many or one wrong shape, with the
+    one check's messages.  The Python wrappers refuse these before the library sees them, so this drives the C ABI: tensors of the
+    manifest's shapes (all reading one zeroed device buffer: the check never looks at values) go into a fresh context; nothing is launched."""
+    from hifidiff_amd import _lib
+    create, args, manifest = _strict_load_kinds()[kind]
+    shapes = {k: tuple(v[0]) for k, v in manifest().items()}
+    victim = list(shapes)[len(shapes) // 2]
+    if how == "missing":
+        del shapes[victim]
+        want = "Missing key in state_dict: " + victim
+    elif how == "extra":
+        shapes["not.in.the.manifest"] = (3,)
+        want = "Unexpected key in state_dict: not.in.the.manifest"
+    else:
+        shapes[victim] = (int(np.prod(shapes[victim])), 1)
+        want = "size mismatch for " + victim
+    zeros = torch.zeros(max(int(np.prod(s)) for s in shapes.values()), device=gpu)
+    descs = (_lib.TensorDesc * len(shapes))()
+    for d, (k, s) in zip(descs, shapes.items()):
+        d.name, d.data, d.ndim, d.is_device = k.encode(), zeros.data_ptr(), len(s), 1
+        for j, n in enumerate(s):
+            d.shape[j] = n
+    L, ctx = _lib.lib(), ctypes.c_void_p()
+    _lib.check(getattr(L, create)(ctypes.byref(ctx), *args, 0))
+    try:
+        _lib.check(L.hd_load_weights(ctx, descs, len(shapes)), ctx)
+        assert L.hd_finalize_weights(ctx) == -3 and L.hd_last_error(ctx).decode() == want
+    finally:
+        L.hd_destroy(ctx)
+
+
 def test_unconditional_denoiser_against_reference_golden(gpu, weights16):
     """the pre-training `Denoiser` (no priors / HCAs / identity) through the same kernels:
     eps vs the reference's outputs and the emulating oracle, the reference's loop body (eager) and the graph loop."""

@@ -249,13 +249,16 @@ def test_cr_manifest_and_synthetic_weights():
 
 def test_incremental_build_knows_what_each_unit_includes():
     """_lib.build() recompiles a translation unit when a header it includes (directly or not) is newer than its object file: the stage
-    kernels live in hd_stages.hip (hd_face.hpp / hd_xcd.hpp / hd_xcd2.hpp), the host side in hd_lib.hip + hd_aux.hip over hd_internal.hpp,
-    and none of the GEMM launch tables depends on a stage kernel (an edit there must not rebuild them: 2 minutes each)."""
+    kernels live in hd_stages.hip (hd_face.hpp / hd_xcd.hpp / hd_xcd2.hpp), the host side in hd_lib.hip + hd_aux.hip (CoarseRestoration and
+    the VAE boundary) over hd_internal.hpp, the image entry points that need no context in hd_image.hip over hd_args.hpp alone, and none
+    of the GEMM launch tables depends on a stage kernel (an edit there must not rebuild them: 2 minutes each)."""
     import os
     deps = {os.path.basename(u): {os.path.basename(d) for d in _lib.unit_deps(u)} for u in _lib.UNITS}
     assert {"hd_face.hpp", "hd_xcd.hpp", "hd_xcd2.hpp", "hd_stage_api.hpp", "hd_chain.hpp", "hd_gemm.hpp"} <= deps["hd_stages.hip"]
     assert {"hd_internal.hpp", "hd_stage_api.hpp", "hd_gemm.hpp", "hifidiff_hip.h"} <= deps["hd_lib.hip"] and "hd_xcd2.hpp" not in deps["hd_lib.hip"]
-    assert "hd_internal.hpp" in deps["hd_aux.hip"]
+    assert "hd_internal.hpp" in deps["hd_aux.hip"] and "hd_metrics.hpp" not in deps["hd_aux.hip"]
+    assert {"hd_color.hpp", "hd_metrics.hpp", "hd_args.hpp"} <= deps["hd_image.hip"] and not {"hd_internal.hpp", "hd_gemm.hpp"} & deps["hd_image.hip"]
+    assert "hd_args.hpp" in deps["hd_photo.hip"] and "hd_internal.hpp" not in deps["hd_photo.hip"]
     for u in ("hd_dispatch_ln.hip", "hd_dispatch_lnface.hip", "hd_dispatch_bf16.hip", "hd_dispatch_misc.hip"):
         assert deps[u] == {u, "hd_dispatch.hpp", "hd_gemm.hpp", "hd_wide.hpp"}, deps[u]      # hd_wide.hpp: a GEMM kernel of the launch table, not a stage
     assert {"hd_strip.hpp", "hd_chain.hpp", "hd_stage_api.hpp"} <= deps["hd_strip.hip"] and "hd_strip.hpp" not in deps["hd_lib.hip"]
