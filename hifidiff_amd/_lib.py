@@ -42,7 +42,7 @@ EXPORTS = [
     "hd_pool_config", "hd_pool_prepare", "hd_pool_commit",
     "hd_sample_faces", "hd_sample_faces_multistep", "hd_sample_spans", "hd_mask_faces", "hd_guide_config", "hd_guide_faces", "hd_color_fix", "hd_image_range", "hd_image_metrics", "hd_image_metrics_workspace", "hd_lpips_create", "hd_lpips", "hd_face_ingest", "hd_face_ingest_workspace", "hd_face_paste", "hd_face_paste_workspace", "hd_preview_config", "hd_preview_read", "hd_scheduler_step",
     "hd_scheduler_step_multistep", "hd_num_ops", "hd_num_chains",
-    "hd_debug_limit_ops", "hd_debug_op_name", "hd_debug_op_info", "hd_debug_read_op", "hd_debug_read", "hd_debug_write", "hd_debug_gemm", "hd_set_option", "hd_get_option", "hd_check",
+    "hd_debug_limit_ops", "hd_debug_op_name", "hd_debug_op_info", "hd_debug_read_op", "hd_debug_read", "hd_debug_write", "hd_debug_gemm", "hd_debug_conv", "hd_set_option", "hd_get_option", "hd_check",
     "hd_set_profiling", "hd_get_profile",
 ]
 
@@ -75,6 +75,22 @@ class GemmNote(ctypes.Structure):
 
 
 GEMM_DRY_RUN = 1
+
+
+class ConvDesc(ctypes.Structure):
+    """hd_conv_desc: one face-geometry convolution on the caller's device buffers (hd_debug_conv)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("M", "C", "side", "face0", "stats_np", "stats_cnt", "film_off", "film_face_stride")] + \
+               [("T1_elems", ctypes.c_int64)] + \
+               [(n, ctypes.c_void_p) for n in ("X", "out", "out16", "stats_out", "stats_in", "film", "G", "pooled", "pooled16", "T1")]
+
+
+class ConvNote(ctypes.Structure):
+    """hd_conv_note: which kernel hd_debug_conv's builder started (form 1: staged in LDS, 2: patch-gather GEMM) and its shape."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("form", "centre_only", "C", "side", "bm", "mt", "ks", "nt", "strip", "depth", "faces_per_wg", "threads",
+                                              "grid_x", "grid_y", "remap", "hint", "dw_path")] + [("gemm", GemmNote)]
+
+
+CONV_HCA, CONV_DOWN, CONV_DWGATE = 0, 1, 2
 
 
 def build(force=False, verbose=False):
@@ -174,6 +190,7 @@ def lib():
     L.hd_debug_read.argtypes = [vp, ctypes.c_char_p, vp, i64]; L.hd_debug_read.restype = i64
     L.hd_debug_write.argtypes = [vp, ctypes.c_char_p, vp, i64]
     L.hd_debug_gemm.argtypes = [vp, ctypes.c_char_p, i32, i32, ctypes.POINTER(GemmDesc), i32, ctypes.POINTER(GemmNote), vp]
+    L.hd_debug_conv.argtypes = [vp, i32, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ConvDesc), i32, ctypes.POINTER(ConvNote), vp]
     L.hd_set_option.argtypes = [vp, ctypes.c_char_p, i32]
     L.hd_get_option.argtypes = [vp, ctypes.c_char_p]
     L.hd_check.argtypes = [vp]

@@ -20,6 +20,12 @@
 #define HD_CONV_NT_MINC 1024
 #endif
 
+// When hca_conv_kernel applies its XCD-aware block -> (row group, weight tile) map: only where the weights dwarf the activations
+// (measured), the column tiles come in whole groups of eight and there is more than one row group.  One definition for the kernel and
+// for the launcher's note; a macro, so that the kernel's expression stays the one it was compiled from (a predicate function moved
+// instructions in the C >= 1024 kernels).
+#define HD_CONV_XCD_REMAP(C, grid_x, grid_y) ((C) >= 1024 && ((grid_y) & 7) == 0 && (grid_x) > 1)
+
 namespace hd {
 
 struct ConvP {
@@ -69,7 +75,7 @@ __global__ __launch_bounds__((K::THREADS), (K::OCC)) void hca_conv_kernel(const 
     // XCD-aware block -> (row group, weight tile) map (as in gemm_skinny_kernel): the row groups that stream the
     // same weight tile get linear ids that are equal mod 8, i.e. run on one XCD and share the tile through its L2
     int bx = blockIdx.x, tile = blockIdx.y;
-    if (K::C >= 1024 && (gridDim.y & 7) == 0 && gridDim.x > 1) {      // only where the weights dwarf the activations (measured)
+    if (HD_CONV_XCD_REMAP(K::C, gridDim.x, gridDim.y)) {
         const int lin = blockIdx.y * gridDim.x + blockIdx.x, j = lin >> 3;
         bx = j % (int)gridDim.x;
         tile = (j / (int)gridDim.x) * 8 + (lin & 7);
@@ -211,13 +217,22 @@ __global__ __launch_bounds__((K::THREADS), (K::OCC)) void hca_conv_kernel(const 
     }
 }
 
+// What launch_hca_conv last launched on this thread (host side only; hd_debug_conv reports it): the ConvCfg by its parameters, the
+// grid, and whether the kernel's XCD tile remap applies to that grid (HD_CONV_XCD_REMAP, the predicate the kernel itself evaluates).
+// Written on every launch, the programs' included, as g_launch_note is: a dozen host stores, no branch on who is asking.
+struct ConvLaunchNote { int C, S, BM, MT, KS, NT, strip, depth, threads, grid_x, grid_y, remap; };
+inline thread_local ConvLaunchNote g_conv_note = {};
+
 template <class K>
 inline hipError_t launch_hca_conv(const ConvP& p, hipStream_t s) {
     if (K::SMEM > 65536) {
         static std::atomic<unsigned long long> granted{0};
         { const hipError_t e = grant_dynamic_lds(reinterpret_cast<const void*>(&hca_conv_kernel<K>), K::SMEM, granted); if (e != hipSuccess) return e; }
     }
-    hipLaunchKernelGGL((hca_conv_kernel<K>), dim3((p.M + K::BM - 1) / K::BM, K::C / (32 * K::NT)), dim3(K::THREADS), K::SMEM, s, p);
+    const dim3 grid((p.M + K::BM - 1) / K::BM, K::C / (32 * K::NT));
+    g_conv_note = ConvLaunchNote{K::C, K::S, K::BM, K::MT, K::KS, K::NT, K::STRIP ? 1 : 0, K::DEPTH, K::THREADS, (int)grid.x, (int)grid.y,
+                                 HD_CONV_XCD_REMAP(K::C, grid.x, grid.y) ? 1 : 0};
+    hipLaunchKernelGGL((hca_conv_kernel<K>), grid, dim3(K::THREADS), K::SMEM, s, p);
     return hipGetLastError();
 }
 

@@ -80,6 +80,7 @@ struct Op {
     size_t out_elems = 0;
     int out_bf16 = 0;
     int lk = -1, ek = -1, mode = -1; // GEMM launches (add_gemm): loader kind, epilogue kind, final kernel mode; -1 otherwise (hd_debug_op_info)
+    int hint = -1;                   // add_gemm: the mode its caller asked for (-1: none; hd_debug_conv reports it)
 };
 
 struct Level { int C, H, M; float *X, *Y, *T1, *pooled, *S; unsigned short *G, *Xb, *Yb, *Xg, *pooled16; float2 *sx, *sy; };
@@ -868,7 +869,7 @@ void add_gemm(hd_ctx* c, std::vector<Op>& prog, const std::string& name, GemmP p
     Chain* chp = c->ch;
     auto gp = std::make_shared<GemmP>(p);
     op.gemm = gp;
-    op.lk = (int)lk; op.ek = (int)ek; op.mode = t128;
+    op.lk = (int)lk; op.ek = (int)ek; op.mode = t128; op.hint = mode_hint;
     op.skinny_affine = p.xcd_tile_affine && (t128 & 48) == 0 && t128 != 0 && t128 != 1 && t128 != 4;     // bit 16 = deep kernel, bit 32 = wide kernel (launch_tile routes those elsewhere); base modes 0/1/4 are the tall kernel
     op.run = [c, chp, gp, lk, ek, t128, film](hipStream_t s) mutable -> hipError_t {
                         if (film && gp->film == nullptr) {        // denoiser FiLM rows live in the (re-allocatable) table
@@ -887,34 +888,40 @@ void add_gemm(hd_ctx* c, std::vector<Op>& prog, const std::string& name, GemmP p
 // x_np/x_cnt: how the LayerNorm partials of the block input X were produced (C/32 x 32 by a GEMM
 // epilogue, 1 x C by the intro conv or a skip-add); on return they describe conv5's output.
 struct GateOut { const float* gate_c = nullptr; const float* gate_s = nullptr; const float* add = nullptr; };
-void add_naf_block(hd_ctx* c, std::vector<Op>& prog, const BlockW& bw, const Level& lv, const float* static_film, int* x_np,
-                   int* x_cnt, const GateOut* gate = nullptr) {
+// The front of a block's attention half, conv1 -> depthwise 3x3 -> SimpleGate -> G and the pooled mean, in the form the library has for
+// (C, side, M, the statistics' form): one fused launch, one launch by strips, or conv1 + depthwise + pool_finish.  Returns true where the
+// strip form ran: T1 then holds strip sums for the chain kernel to add up, not a pooled mean.  add_naf_block and hd_debug_conv call this.
+// film_face_stride: only with a static_film whose rows are per face (hd_debug_conv); a film patched in at launch brings its own stride.
+bool add_conv1_dwgate(hd_ctx* c, std::vector<Op>& prog, const BlockW& bw, const Level& lv, const float* static_film, int face0, int x_np, int x_cnt,
+                      int film_face_stride = 0) {
     const int C = bw.C, M = lv.M, HW = lv.H * lv.H;
     auto film_fields = [&](GemmP& p, int half) {
-        p.hw = HW; p.face0 = c->ch->face0;
+        p.hw = HW; p.face0 = face0;
         p.film = static_film;                           // nullptr -> patched from the table at launch
+        p.film_face_stride = film_face_stride;
         p.film_bias_off = bw.film_off + (2 * half) * C;
         p.film_gain_off = bw.film_off + (2 * half + 1) * C;
     };
-    bool strip_pool = false;
     static const bool no_fuse = hd_env("HD_NO_DWFUSE") != nullptr, no_chain = hd_env("HD_NO_CHAIN") != nullptr;
     static const bool no_strip = hd_env("HD_NO_STRIP") != nullptr || no_fuse || no_chain;      // the chain kernel adds the strip sums up
-    const bool by_strips = ((C == 128 && lv.H == 32) || (C == 256 && lv.H == 16)) && (*x_np) * (*x_cnt) == C && *x_np <= 16 && !no_strip;
+    const bool by_strips = ((C == 128 && lv.H == 32) || (C == 256 && lv.H == 16)) && x_np * x_cnt == C && x_np <= 16 && !no_strip;
     if (dwgate_ok(HW) && !no_fuse && !by_strips) {
         // LN1 + FiLM -> conv1 (+bias) -> depthwise 3x3 -> SimpleGate -> G, pooled mean: one launch
         GemmP p = base_gemm(bw.conv1, M);
         p.A = lv.Xb; p.lda = C; film_fields(p, 0);
-        p.stats_in = lv.sx; p.stats_np = *x_np; p.stats_cnt = *x_cnt;
+        p.stats_in = lv.sx; p.stats_np = x_np; p.stats_cnt = x_cnt;
         p.out = lv.G; p.ldo = C; p.dw_w = bw.dw_wT; p.dw_b = bw.dw_b; p.pooled = lv.pooled; p.pooled16 = lv.pooled16; p.side = lv.H;
         add_gemm(c, prog, bw.name + ".conv2_gate_pool", p, LK_LN, EK_DWGATE);
-    } else if (by_strips) {
+        return false;
+    }
+    if (by_strips) {
         // 32 x 32 faces at C = 128, 16 x 16 at C = 256 (latent 32, levels 0 / 1): the same fusion by strips of 4 image rows, depthwise conv out of
         // the MFMA accumulators (hd_strip.hpp)
         StripP q{};
         q.faces = M / HW; q.side = lv.H; q.C = C;
-        q.Xb = lv.Xb; q.stats_in = lv.sx; q.stats_np = *x_np; q.stats_cnt = *x_cnt;
+        q.Xb = lv.Xb; q.stats_in = lv.sx; q.stats_np = x_np; q.stats_cnt = x_cnt;
         q.W1 = bw.conv1.w; q.b1 = bw.conv1.bias; q.dw_wT = bw.dw_wT; q.dw_b = bw.dw_b;
-        q.film = static_film; q.film_gain_off = bw.film_off + C; q.film_bias_off = bw.film_off; q.film_face_stride = 0; q.face0 = c->ch->face0; q.ln_eps = 1e-6f;
+        q.film = static_film; q.film_gain_off = bw.film_off + C; q.film_bias_off = bw.film_off; q.film_face_stride = film_face_stride; q.face0 = face0; q.ln_eps = 1e-6f;
         q.G = lv.G; q.pool_part = lv.T1;                          // T1 itself is never written on this path: its first faces x 8 x C floats hold the strip sums
         Chain* chp = c->ch;
         Op op;
@@ -925,34 +932,47 @@ void add_naf_block(hd_ctx* c, std::vector<Op>& prog, const BlockW& bw, const Lev
             return run_strip_dwgate(r, s);
         };
         prog.push_back(op);
-        strip_pool = true;                                        // the chain kernel below adds the strip sums up itself (no pool_finish launch)
-    } else {
-        {   // LN1 + FiLM -> conv1 (+bias) -> T1
-            GemmP p = base_gemm(bw.conv1, M);
-            p.A = lv.Xb; p.lda = C; film_fields(p, 0);
-            p.stats_in = lv.sx; p.stats_np = *x_np; p.stats_cnt = *x_cnt;
-            p.out = lv.T1; p.ldo = 2 * C;
-            add_gemm(c, prog, bw.name + ".conv1", p, LK_LN, EK_BIASF32);
-        }
-        {   // depthwise 3x3 -> SimpleGate -> G, pooled mean
-            const float *T1 = lv.T1, *w = bw.dw_w, *b = bw.dw_b;
-            unsigned short* G = lv.G; float* pooled = lv.pooled;
-            const int H = lv.H, faces = M / HW;
-            float* part = lv.T1 + (size_t)2 * M * C;        // band sums live behind T1 (alloc_chain reserves the room)
-            const int nbands = (H + 7) / 8;
-            prog.push_back({bw.name + ".conv2_gate_pool", [=](hipStream_t s) -> hipError_t {
-                                hipLaunchKernelGGL(dwconv_gate_pool_kernel, dim3(C / 32, faces, nbands), dim3(256), 0, s, T1, w, b, G, part, H, H, C);
-                                return hipGetLastError();
-                            }});
-            prog.back().out = G; prog.back().out_elems = (size_t)M * C; prog.back().out_bf16 = 1;
-            prog.push_back({bw.name + ".pool_finish", [=](hipStream_t s) -> hipError_t {
-                                hipLaunchKernelGGL(dwconv_pool_finish_kernel, dim3((faces * C + 255) / 256), dim3(256), 0, s, part, pooled, faces, nbands, C,
-                                                   1.0f / (float)(H * H));
-                                return hipGetLastError();
-                            }});
-            prog.back().out = pooled; prog.back().out_elems = (size_t)faces * C;
-        }
+        return true;                                              // the chain kernel adds the strip sums up itself (no pool_finish launch)
     }
+    {   // LN1 + FiLM -> conv1 (+bias) -> T1
+        GemmP p = base_gemm(bw.conv1, M);
+        p.A = lv.Xb; p.lda = C; film_fields(p, 0);
+        p.stats_in = lv.sx; p.stats_np = x_np; p.stats_cnt = x_cnt;
+        p.out = lv.T1; p.ldo = 2 * C;
+        add_gemm(c, prog, bw.name + ".conv1", p, LK_LN, EK_BIASF32);
+    }
+    {   // depthwise 3x3 -> SimpleGate -> G, pooled mean
+        const float *T1 = lv.T1, *w = bw.dw_w, *b = bw.dw_b;
+        unsigned short* G = lv.G; float* pooled = lv.pooled;
+        const int H = lv.H, faces = M / HW;
+        float* part = lv.T1 + (size_t)2 * M * C;        // band sums live behind T1 (alloc_chain reserves the room)
+        const int nbands = (H + 7) / 8;
+        prog.push_back({bw.name + ".conv2_gate_pool", [=](hipStream_t s) -> hipError_t {
+                            hipLaunchKernelGGL(dwconv_gate_pool_kernel, dim3(C / 32, faces, nbands), dim3(256), 0, s, T1, w, b, G, part, H, H, C);
+                            return hipGetLastError();
+                        }});
+        prog.back().out = G; prog.back().out_elems = (size_t)M * C; prog.back().out_bf16 = 1;
+        prog.push_back({bw.name + ".pool_finish", [=](hipStream_t s) -> hipError_t {
+                            hipLaunchKernelGGL(dwconv_pool_finish_kernel, dim3((faces * C + 255) / 256), dim3(256), 0, s, part, pooled, faces, nbands, C,
+                                               1.0f / (float)(H * H));
+                            return hipGetLastError();
+                        }});
+        prog.back().out = pooled; prog.back().out_elems = (size_t)faces * C;
+    }
+    return false;
+}
+
+void add_naf_block(hd_ctx* c, std::vector<Op>& prog, const BlockW& bw, const Level& lv, const float* static_film, int* x_np,
+                   int* x_cnt, const GateOut* gate = nullptr) {
+    const int C = bw.C, M = lv.M, HW = lv.H * lv.H;
+    auto film_fields = [&](GemmP& p, int half) {
+        p.hw = HW; p.face0 = c->ch->face0;
+        p.film = static_film;                           // nullptr -> patched from the table at launch
+        p.film_bias_off = bw.film_off + (2 * half) * C;
+        p.film_gain_off = bw.film_off + (2 * half + 1) * C;
+    };
+    static const bool no_fuse = hd_env("HD_NO_DWFUSE") != nullptr, no_chain = hd_env("HD_NO_CHAIN") != nullptr;
+    const bool strip_pool = add_conv1_dwgate(c, prog, bw, lv, static_film, c->ch->face0, *x_np, *x_cnt);
     if ((C == 128 || C == 256) && HW % 32 == 0 && !no_fuse && !no_chain) {        // also behind the unfused depthwise path (latent 32, level 0)
         // levels 0/1: sca -> conv3 -> residual -> LN+FiLM -> conv4 -> gate -> conv5 -> residual in ONE launch (hd_chain.hpp)
         ChainP q{};

@@ -2070,6 +2070,167 @@ int hd_debug_gemm(hd_ctx* c, const char* weight, int loader, int epilogue, const
     note->wide_form = ln.wide_form; note->threads = ln.threads; note->grid_x = ln.grid_x; note->grid_y = ln.grid_y;
     return HD_OK;
 }
+// One launch of a face-geometry convolution on the caller's operands (include/hifidiff_hip.h), through add_hca / add_down: the library
+// picks the kernel from (C, side, M) and the note says what ran.  Everything the packer or a launcher does not take is refused first.
+// HD_CONV_DWGATE: conv1 -> depthwise 3x3 -> SimpleGate -> pool through add_conv1_dwgate, the function add_naf_block calls
+static int debug_dwgate(hd_ctx* c, const char* weight, const char* weight2, const hd_conv_desc* d, int flags, hd_conv_note* note, void* stream) {
+    if (!weight2) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: weight2 (conv2) must not be NULL for HD_CONV_DWGATE");
+    const int C = d->C, side = d->side;
+    if (side < 1 || side > 64 || (side & (side - 1)) != 0) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: side = %d must be a power of two in [1, 64]", side);
+    if (C < 32 || C > 2048 || C % 32 != 0) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: C = %d must be a multiple of 32 in [32, 2048]", C);
+    const int HW = side * side;
+    if (d->M < 1 || d->M > (1 << 16) || d->M % HW != 0)
+        HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: M = %d must be a multiple of side * side = %d in [1, 65536] (rows are pixels of whole faces)", d->M, HW);
+    const int faces = d->M / HW;
+    if (d->stats_np < 1 || d->stats_cnt < 1 || (int64_t)d->stats_np * d->stats_cnt != C)
+        HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: stats_np * stats_cnt = %d * %d != C = %d", d->stats_np, d->stats_cnt, C);
+    if (d->film_off < 0 || d->film_off % 4 != 0 || d->film_face_stride < 0 || d->film_face_stride % 4 != 0)
+        HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: film_off = %d / film_face_stride = %d must be non-negative multiples of 4", d->film_off, d->film_face_stride);
+    if (d->face0 < 0 || d->face0 > (1 << 16)) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: face0 = %d", d->face0);
+    auto bad_ptr = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+#define HD_NEED(field) do { if (bad_ptr(d->field)) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: %s is NULL or not 16-byte aligned", #field); } while (0)
+    HD_NEED(X); HD_NEED(stats_in); HD_NEED(film); HD_NEED(G); HD_NEED(pooled); HD_NEED(T1);
+#undef HD_NEED
+    if (d->pooled16 && (reinterpret_cast<uintptr_t>(d->pooled16) & 15) != 0) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: pooled16 is not 16-byte aligned");
+    if (d->out || d->out16 || d->stats_out) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: out, out16 and stats_out are not written by HD_CONV_DWGATE");
+    const int64_t t1_need = (int64_t)2 * d->M * C + (int64_t)faces * ((side + 7) / 8) * C;
+    if (d->T1_elems < t1_need) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: T1_elems = %lld < %lld", (long long)d->T1_elems, (long long)t1_need);
+    // ---- the weights
+    const std::string n1 = weight, n2 = weight2;
+    const RawTensor *w1 = find_raw(c, n1 + ".weight"), *b1 = find_raw(c, n1 + ".bias"), *w2 = find_raw(c, n2 + ".weight"), *b2 = find_raw(c, n2 + ".bias");
+    if (!w1 || !w1->dev || !(w1->shape == Shape{2 * C, C} || w1->shape == Shape{2 * C, C, 1, 1}))
+        HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: weight %s.weight must be [%d][%d] or [%d][%d][1][1] for C = %d", weight, 2 * C, C, 2 * C, C, C);
+    if (!b1 || !b1->dev || (int64_t)b1->numel != 2 * C) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: weight %s.bias must have %d elements", weight, 2 * C);
+    if (!w2 || !w2->dev || w2->shape != Shape{2 * C, 1, 3, 3})
+        HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: weight2 %s.weight must be [%d][1][3][3] for C = %d", weight2, 2 * C, C);
+    if (!b2 || !b2->dev || (int64_t)b2->numel != 2 * C) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: weight2 %s.bias must have %d elements", weight2, 2 * C);
+    HIPCHECK(c, hipSetDevice(c->device));
+    BlockW bw;
+    bw.name = "debug_conv." + n1; bw.C = C; bw.film_off = d->film_off;
+    auto it = c->dbg_packed.find(n1 + "#conv");
+    if (it == c->dbg_packed.end()) {
+        PackedW pw;
+        if (const int rc = pack_weight(c, n1, &pw)) return rc;
+        HIPCHECK(c, hipDeviceSynchronize());
+        it = c->dbg_packed.emplace(n1 + "#conv", pw).first;
+    }
+    bw.conv1 = it->second;
+    bw.dw_w = w2->dev; bw.dw_b = b2->dev;
+    it = c->dbg_packed.find(n2 + "#dwT");                       // the tap-major copy, kept in the bias slot of a PackedW without a weight
+    if (it == c->dbg_packed.end()) {
+        if (const int rc = make_dw_layout(c, bw)) return rc;
+        HIPCHECK(c, hipDeviceSynchronize());
+        PackedW pw;
+        pw.bias = bw.dw_wT;
+        it = c->dbg_packed.emplace(n2 + "#dwT", pw).first;
+    }
+    bw.dw_wT = it->second.bias;
+    Level lv{};
+    lv.C = C; lv.H = side; lv.M = d->M;
+    lv.Xb = const_cast<unsigned short*>(static_cast<const unsigned short*>(d->X));
+    lv.sx = reinterpret_cast<float2*>(const_cast<float*>(d->stats_in));
+    lv.G = static_cast<unsigned short*>(d->G); lv.pooled = d->pooled; lv.pooled16 = static_cast<unsigned short*>(d->pooled16); lv.T1 = d->T1;
+    std::vector<Op> prog;
+    const bool strips = add_conv1_dwgate(c, prog, bw, lv, d->film, d->face0, d->stats_np, d->stats_cnt, d->film_face_stride);
+    note->dw_path = strips ? 2 : (prog.size() == 3 ? 3 : 1);
+    note->hint = -1;
+    note->gemm.op_info = op_info_word(prog[0]);
+    if (flags & HD_GEMM_DRY_RUN) return HD_OK;
+    g_launch_note = LaunchNote{};
+    if (const int rc = run_ops(c, prog, static_cast<hipStream_t>(stream))) return rc;
+    if (!strips) {
+        const LaunchNote& ln = g_launch_note;
+        hd_gemm_note& g = note->gemm;
+        g.family = ln.family; g.rows = ln.rows; g.pair = ln.pair; g.wk = ln.wk; g.cpw = ln.cpw; g.nt = ln.nt;
+        g.wide_form = ln.wide_form; g.threads = ln.threads; g.grid_x = ln.grid_x; g.grid_y = ln.grid_y;
+        note->threads = ln.threads; note->grid_x = ln.grid_x; note->grid_y = ln.grid_y;
+    }
+    note->form = 3;
+    return HD_OK;
+}
+
+int hd_debug_conv(hd_ctx* c, int kind, const char* weight, const char* weight2, const hd_conv_desc* d, int flags, hd_conv_note* note, void* stream) {
+    if (!c) return HD_ERR_INVALID;
+    if (!weight || !d || !note) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: weight, desc and note must not be NULL");
+    *note = hd_conv_note{};
+    if (c->finalized) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: ctx is finalized (the entry takes a context whose weights are still raw)");
+    if (kind == HD_CONV_DWGATE) return debug_dwgate(c, weight, weight2, d, flags, note, stream);
+    if (kind != HD_CONV_HCA && kind != HD_CONV_DOWN) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: kind = %d (HD_CONV_HCA, HD_CONV_DOWN or HD_CONV_DWGATE)", kind);
+    if (weight2) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: weight2 is not read by kind %d", kind);
+    const bool down = kind == HD_CONV_DOWN;
+    // ---- the geometry
+    const int C = d->C, side = d->side;
+    // (the range of the programs' levels and of the tests: with M <= 2^16 and C <= 2^11 no 32-bit index of a loader or an epilogue wraps)
+    if (side < (down ? 2 : 1) || side > 32 || (side & (side - 1)) != 0)
+        HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: side = %d must be a power of two in [%d, 32]", side, down ? 2 : 1);
+    if (C < 32 || C > 2048 || C % 32 != 0) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: C = %d must be a multiple of 32 in [32, 2048]", C);
+    const int HW = side * side;
+    if (d->M < 1 || d->M > (1 << 16) || d->M % HW != 0)
+        HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: M = %d must be a multiple of side * side = %d in [1, 65536] (rows are pixels of whole faces)", d->M, HW);
+    auto bad_ptr = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+    auto misaligned = [](const void* p) { return p != nullptr && (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+    if (bad_ptr(d->X)) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: X is NULL or not 16-byte aligned");
+    if (bad_ptr(d->out)) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: out is NULL or not 16-byte aligned");
+    if (misaligned(d->out16)) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: out16 is not 16-byte aligned");
+    if (misaligned(d->stats_out)) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: stats_out is not 16-byte aligned");
+    if (!down && d->stats_out) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: stats_out is not written by HD_CONV_HCA");
+    // ---- the weight
+    const std::string name = weight;
+    const RawTensor* w = find_raw(c, name + ".weight");
+    if (!w || !w->dev) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: weight %s.weight has not been loaded", weight);
+    const int N = down ? 2 * C : C, kk = down ? 2 : 3;
+    if (w->shape != Shape{N, C, kk, kk})
+        HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: weight %s.weight must be [%d][%d][%d][%d] for C = %d", weight, N, C, kk, kk, C);
+    const RawTensor* b = find_raw(c, name + ".bias");
+    if (!b || !b->dev || (int64_t)b->numel != N) HD_FAIL(c, HD_ERR_INVALID, "hd_debug_conv: weight %s.bias must have %d elements", weight, N);
+    // ---- the packed weight (first use: packed on the null stream, then waited for)
+    HIPCHECK(c, hipSetDevice(c->device));
+    const bool centre = !down && side == 1;                   // 1x1 map: only the centre tap sees data (as finalize packs hcas of such a level)
+    const std::string key = name + (centre ? "#centre" : "#conv");
+    auto it = c->dbg_packed.find(key);
+    if (it == c->dbg_packed.end()) {
+        PackedW pw;
+        PackOpts o;
+        o.centre_only = centre;
+        if (const int rc = pack_weight(c, name, &pw, o)) return rc;
+        HIPCHECK(c, hipDeviceSynchronize());
+        it = c->dbg_packed.emplace(key, pw).first;
+    }
+    std::vector<Op> prog;
+    if (down) {
+        Level src{}, dst{};
+        src.C = C; src.H = side; src.M = d->M; src.Xb = const_cast<unsigned short*>(static_cast<const unsigned short*>(d->X));
+        dst.C = N; dst.H = side / 2; dst.M = d->M / 4; dst.X = d->out; dst.Xb = static_cast<unsigned short*>(d->out16);
+        dst.sx = reinterpret_cast<float2*>(d->stats_out);
+        add_down(c, prog, "debug_conv." + name, it->second, src, dst);
+    } else {
+        HcaW hw;
+        hw.C = C; hw.fused = it->second; hw.centre_only = centre;
+        add_hca(c, prog, "debug_conv." + name, hw, static_cast<const unsigned short*>(d->X), d->out, static_cast<unsigned short*>(d->out16), d->M, side);
+    }
+    note->centre_only = centre ? 1 : 0;
+    note->hint = prog[0].hint;
+    note->gemm.op_info = op_info_word(prog[0]);
+    if (flags & HD_GEMM_DRY_RUN) return HD_OK;
+    g_launch_note = LaunchNote{};
+    g_conv_note = ConvLaunchNote{};
+    if (const int rc = run_ops(c, prog, static_cast<hipStream_t>(stream))) return rc;
+    if (prog[0].gemm) {
+        const LaunchNote& ln = g_launch_note;
+        hd_gemm_note& g = note->gemm;
+        note->form = 2;
+        g.family = ln.family; g.rows = ln.rows; g.pair = ln.pair; g.wk = ln.wk; g.cpw = ln.cpw; g.nt = ln.nt;
+        g.wide_form = ln.wide_form; g.threads = ln.threads; g.grid_x = ln.grid_x; g.grid_y = ln.grid_y;
+        note->threads = ln.threads; note->grid_x = ln.grid_x; note->grid_y = ln.grid_y;
+    } else {
+        const ConvLaunchNote& cn = g_conv_note;
+        note->form = 1;
+        note->C = cn.C; note->side = cn.S; note->bm = cn.BM; note->mt = cn.MT; note->ks = cn.KS; note->nt = cn.NT; note->strip = cn.strip;
+        note->depth = cn.depth; note->faces_per_wg = (!cn.strip && cn.BM > cn.S * cn.S) ? cn.BM / (cn.S * cn.S) : 1;
+        note->threads = cn.threads; note->grid_x = cn.grid_x; note->grid_y = cn.grid_y; note->remap = cn.remap;
+    }
+    return HD_OK;
+}
 static int64_t read_to_host(hd_ctx* c, const void* dev, size_t n, int is_bf16, float* host_out, int64_t max_elems) {
     if (!host_out) return (int64_t)n;
     if ((int64_t)n > max_elems) HD_FAIL(c, HD_ERR_INVALID, "debug read needs %zu elements", n);

@@ -545,6 +545,65 @@ typedef struct hd_gemm_note {
 enum { HD_GEMM_DRY_RUN = 1 };
 int hd_debug_gemm(hd_ctx* ctx, const char* weight, int loader, int epilogue, const hd_gemm_desc* desc, int flags, hd_gemm_note* note,
                   void* stream);
+/* One launch of a face-geometry convolution on the caller's operands, through the builder the programs call (tests: the kernels whose
+ * rows depend on their neighbours in the face, without a network around them).  `ctx` as for hd_debug_gemm: created, NOT finalized.
+ *   HD_CONV_HCA:  the HCA 3x3 (pad 1) conv C -> C + bias, ReLU, through add_hca.  `weight` names <weight>.weight [C][C][3][3] and
+ *                 <weight>.bias [C] (no BatchNorm is folded).  side == 1 packs the centre tap only, as the programs do for 1 x 1 faces.
+ *                 X bf16 [M][C], rows are pixels of M / side^2 faces; out fp32 [M][C]; out16 bf16 copy or NULL; stats_out NULL.
+ *   HD_CONV_DOWN: the 2x2 stride-2 down-conv C -> 2C + bias through add_down.  <weight>.weight [2C][C][2][2], <weight>.bias [2C].
+ *                 X bf16 [M][C] (faces of side x side); out fp32 [M / 4][2C]; out16 and stats_out [M / 4][2C / 32] (mean, M2) or NULL.
+ * The weight is packed on first use (pack_weight) and cached in the context.  The library picks the kernel from (C, side, M) as for a
+ * launch of a program -- the LDS-staged conv for the (C, side) pairs of add_hca's table, the patch-gather GEMM otherwise -- and `note`
+ * says what ran: form 1 = staged (the ConvCfg by its parameters, faces per workgroup, grid, and whether the kernel's XCD tile remap
+ * applied to that grid), form 2 = patch-gather GEMM (`gemm` as hd_debug_gemm fills it); form 0 and gemm.op_info only after a dry run.
+ *   HD_CONV_DWGATE: the front of a NAF block's attention half, LayerNorm + FiLM -> conv1 (+ bias) -> depthwise 3x3 (pad 1) on both halves
+ *                 -> their product G (bf16) and its mean per face, through the function the block builder calls (add_conv1_dwgate).
+ *                 `weight` names conv1 (<weight>.weight [2C][C] or [2C][C][1][1], .bias [2C]), `weight2` conv2 (<weight2>.weight
+ *                 [2C][1][3][3], .bias [2C]).  X bf16 [M][C]; stats_in [M][stats_np] (mean, M2) partials of stats_cnt elements each;
+ *                 film fp32 with the bias row at film_off and the gain row at film_off + C (film_face_stride != 0: the row of face
+ *                 face0 + row / side^2 at that stride); G bf16 [M][C]; pooled fp32 [M / side^2][C]; pooled16 bf16 copy or NULL (the
+ *                 fused form writes it); T1 fp32 scratch of T1_elems >= 2 M C + faces * ((side + 7) / 8) * C elements.  The library
+ *                 picks the form from (C, side, M, stats_np) and note.dw_path says which: 1 fused into conv1's epilogue (`gemm` says
+ *                 which kernel), 2 by strips (T1 then holds [face][side / 4][C] strip sums and pooled is NOT written: the chain kernel
+ *                 adds them up), 3 unfused (T1 [M][2C] = conv1's output, band sums behind it, pooled by pool_finish).  dw_path is
+ *                 filled by a dry run too.  out, out16 and stats_out are NULL.  side up to 64.
+ * `weight2` is NULL for the other kinds.  Every pointer is a DEVICE pointer the caller owns.
+ * HD_ERR_INVALID with a message that names the field, before any launch, for: a finalized context, an unknown kind, side not a power
+ * of two (or > 32; DOWN: < 2), M < 1, M > 65536 or M % side^2 != 0, C not a multiple of 32 (or > 2048), a pointer that is NULL where it is needed
+ * or not 16-byte aligned, stats_out with HD_CONV_HCA, and a weight or bias that is missing or whose shape does not match (C, kind).
+ * The accepted range is that of the programs' levels (C = 128 .. 2048, faces up to 32 x 32) and of the tests: M * C <= 2^27, so every
+ * index the loaders and epilogues form in 32 bits (row * C + c, K = 9 C) stays below 2^31.
+ * flags: HD_GEMM_DRY_RUN as for hd_debug_gemm. */
+typedef struct hd_conv_desc {
+    int32_t M, C, side;
+    int32_t face0, stats_np, stats_cnt, film_off, film_face_stride;     /* HD_CONV_DWGATE */
+    int64_t T1_elems;
+    const void* X;
+    float* out;
+    void* out16;
+    float* stats_out;
+    const float* stats_in;                                              /* HD_CONV_DWGATE from here on */
+    const float* film;
+    void* G;
+    float* pooled;
+    void* pooled16;
+    float* T1;
+} hd_conv_desc;
+typedef struct hd_conv_note {
+    int32_t form;           /* 1 staged in LDS (hd_conv.hpp), 2 patch-gather GEMM, 3 HD_CONV_DWGATE (see dw_path); 0: nothing was launched */
+    int32_t centre_only;    /* the weight was packed with its centre tap only */
+    int32_t C, side;        /* staged: the ConvCfg that ran ... */
+    int32_t bm, mt, ks, nt, strip, depth;
+    int32_t faces_per_wg;   /* ... whole faces per workgroup (1 where a face is one or more workgroups) */
+    int32_t threads, grid_x, grid_y;
+    int32_t remap;          /* staged: the XCD tile remap's condition held for this grid */
+    int32_t hint;           /* gather: the kernel mode the builder asked add_gemm for (-1: none) */
+    int32_t dw_path;        /* HD_CONV_DWGATE: 1 fused, 2 by strips, 3 unfused (also after a dry run) */
+    hd_gemm_note gemm;      /* gather: as hd_debug_gemm */
+} hd_conv_note;
+enum { HD_CONV_HCA = 0, HD_CONV_DOWN = 1, HD_CONV_DWGATE = 2 };
+int hd_debug_conv(hd_ctx* ctx, int kind, const char* weight, const char* weight2, const hd_conv_desc* desc, int flags, hd_conv_note* note,
+                  void* stream);
 /* Run-time switches that select between equivalent launch programs of the same arithmetic (tests compare them bit for
  * bit; no reference interface corresponds): "xcd" 1/0 = levels 2 / 3 as XCD-local persistent launches (hd_xcd.hpp) or one
  * launch per GEMM; "face" 1/0 the same for levels 0 / 1 (hd_face.hpp); "xcd_phase_limit" n / "face_block_limit" n = stop
